@@ -18,8 +18,14 @@ exits with the worst rank's code.
 A step = one view per rank, forward + backward (+ exchange).  value = total pixels rendered by
 all ranks / max-over-ranks wall time.  Inputs are resident in HBM before the timed region.
 
-Prints ONE JSON line (rank 0) with the contract keys plus "roofline" (dominant kernel) and
-"cpu_baseline" (the CPU oracle timed on a bounded crop of the same view, N=1 only)."""
+A plain run sets up, warms up, times the --steps steps and prints ONE JSON line (rank 0) with the
+contract keys.  Everything else -- "roofline" (dominant kernel), the per-stage table, the graphed
+and clustered-layout child runs, "cpu_baseline" (the CPU oracle timed on a bounded crop of the same
+view, N=1 only) and the full-frame CPU comparison -- runs only with --full.
+
+--dump-outputs DIR writes what the last timed step computed (render, alpha, parameter gradients,
+screen-space absgrad, radii; per-Gaussian arrays as a fixed seeded sample when the whole would
+exceed 64 MB) as DIR/<name>.npy, so that two builds can be compared output for output."""
 from __future__ import annotations
 
 import argparse
@@ -67,13 +73,21 @@ def parse(argv=None):
                          "pulled into a ball of that extent at the centre (captured-scene-like: lists of thousands of entries, "
                          "saturated and unsaturated; scripts/clustered_check.py) | needles:<frac>:<ratio> -- that fraction made "
                          "anisotropic (one axis x ratio, one / 3: the needles and plates densification leaves) | parts joined "
-                         "by + (freegaussian_amd.scenes.apply_layout).  The default run also measures two clustered and two "
+                         "by + (freegaussian_amd.scenes.apply_layout).  --full also measures two clustered and two "
                          "needle layouts in child processes and reports them under `clustered_layouts`; the headline stays the "
                          "uniform scene.")
     ap.add_argument("--no-clustered", action="store_true", help="skip the clustered-layout child runs")
     ap.add_argument("--cpu-crop", type=str, default="480x272")  # ~4 s of oracle time per run on the GPU box
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = pick the faster of 8 and 32 host threads")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: stage pass and per-kernel / roofline figures, graphed and "
+                         "clustered-layout child runs, clocks, CPU baselines with parity against the oracle")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------
@@ -455,6 +469,67 @@ def make_scene(args):
     return scene, None
 
 
+DUMP_BYTES = 64 * 10**6 - 2**16  # --dump-outputs: all files together (the .npy headers inside the margin)
+
+
+def _sample_ids(n, k, seed):
+    """k of range(n), sorted: a fixed seeded sample (the same for the same n, k), or None for all of them."""
+    import numpy as np
+
+    if k >= n:
+        return None
+    return np.sort(np.random.default_rng(seed).choice(n, size=max(k, 1), replace=False))
+
+
+def dump_outputs(out_dir, render, alpha, params, info):
+    """What the last timed step computed, as a caller of the path receives it: ``render`` / ``alpha`` of the view, the
+    gradient of every Gaussian parameter (``grad_<name>``), the screen-space ``means2d_absgrad`` and the ``radii``, as
+    out_dir/<name>.npy in float32.  The images are written whole when they fit in 3/4 of DUMP_BYTES (1080p: 33 MB), else a fixed
+    seeded sample of pixels (rows of ``pixel_ids``); the per-Gaussian arrays share one fixed seeded sample of Gaussians
+    (``gaussian_ids``, float64) sized to the rest.  The samples depend only on the shapes: same arguments, same rows."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    written = 0
+
+    def save(name, t):
+        nonlocal written
+        a = t if isinstance(t, np.ndarray) else t.detach().float().cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written += a.nbytes
+
+    _, H, W, _ = render.shape
+    images = {"render": render[0].reshape(H * W, -1), "alpha": alpha[0].reshape(H * W, -1)}
+    px_bytes = sum(4 * v.shape[1] for v in images.values())
+    img_budget = DUMP_BYTES * 3 // 4
+    pix = None if H * W * px_bytes <= img_budget else _sample_ids(H * W, img_budget // (px_bytes + 8), seed=0)
+    if pix is None:
+        save("render", render[0])
+        save("alpha", alpha[0])
+    else:
+        idx = torch.from_numpy(pix).to(render.device)
+        for name, v in images.items():
+            save(name, v[idx])
+        save("pixel_ids", pix.astype(np.float64))
+
+    per_gauss = {}
+    for name, p in params.params.items():
+        per_gauss["grad_" + name] = p.grad if p.grad is not None else params.grad_views[name]
+    absgrad = getattr(info["means2d"], "absgrad", None)
+    if absgrad is not None:
+        per_gauss["means2d_absgrad"] = absgrad[0]
+    per_gauss["radii"] = info["radii"][0]
+    n = params.n
+    g_bytes = sum(4 * (v.numel() // n) for v in per_gauss.values()) + 8
+    gid = _sample_ids(n, (DUMP_BYTES - written) // g_bytes, seed=1)
+    idx = None if gid is None else torch.from_numpy(gid).to(params.flat.device)
+    for name, v in per_gauss.items():
+        save(name, v if idx is None else v[idx])
+    if gid is not None:
+        save("gaussian_ids", gid.astype(np.float64))
+
+
 def graph_only(args):
     """Child-process leg: the step replayed as one hipGraph; prints one JSON object."""
     import torch
@@ -519,7 +594,7 @@ def clustered_children(args):
         if left < 20:
             res_all[lay] = {"error": "skipped: the children's shared time budget is spent (FG_BENCH_CHILD_BUDGET_S)"}
             continue
-        cmd = [sys.executable, os.path.abspath(__file__), "--layout", lay, "--steps", "40", "--warmup", "10", "--settle-s",
+        cmd = [sys.executable, os.path.abspath(__file__), "--full", "--layout", lay, "--steps", "40", "--warmup", "10", "--settle-s",
                str(max(args.settle_s, 1.0)), "--no-cpu-baseline", "--no-graph", "--n-gauss", str(args.n_gauss), "--width", str(args.width),
                "--height", str(args.height), "--sh-degree", str(args.sh_degree)]  # fmt: skip
         try:
@@ -555,14 +630,16 @@ def main(argv=None):
                          | {"n_gpus": int(os.environ.get("WORLD_SIZE", "1")), "gpus_arg": args.gpus}), flush=True)  # fmt: skip
         return
 
+    # (the child runs below are part of --full only: a plain run measures the headline and nothing else)
     clustered = None
-    if (int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.layout == "uniform" and not args.no_clustered and not under_profiler()):
+    if (args.full and int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.layout == "uniform" and not args.no_clustered
+            and not under_profiler()):  # fmt: skip
         import torch  # (importing torch and counting devices does not initialise the GPU)
 
         if torch.cuda.device_count() > 0:
             clustered = clustered_children(args)  # (before this process initialises the GPU)
     graphed = None
-    if int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_graph and not under_profiler():
+    if args.full and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_graph and not under_profiler():
         # the same step captured in one hipGraph (graphed.GraphedRaster), measured in a CHILD process (a failed capture
         # aborts the process; the headline line must survive), alone on the device like the children above.
         # Informational: the headline is the eager path, whose kernels can be timed individually.
@@ -632,6 +709,7 @@ def main(argv=None):
     marks = []  # per step: HIP events at start / after forward / after backward / after the exchange
     counter = [0]
     last_info = [None]
+    last_out = [None]  # (render, alpha) of the latest step: what --dump-outputs writes
 
     def step(timed=False):
         view = rank % N_VIEWS if args.fixed_view else (rank + counter[0]) % N_VIEWS
@@ -664,6 +742,7 @@ def main(argv=None):
         # still referenced and asked the device for a new one -- the 4.6 / 15.7 ms steps of the clustered lines
         # (`path_events_in_timed_region.pool_new_buffers` = 1).)
         last_info[0] = info
+        last_out[0] = (r, a)
         return info, view
 
     def fence():
@@ -699,18 +778,19 @@ def main(argv=None):
     # constant of tens of milliseconds -- behind an idle stretch (a collection, an event summary) the dominant
     # kernel ran 0.39 ms and was still getting faster 48 steps later (0.31-0.34 ms; FG_BENCH_SERIES=1 prints the
     # series), so a 20-step region behind a pause timed the ramp, not the path.  Order: collection, calibration,
-    # settle (--settle-s seconds of steps, no host synchronisation inside), stage pass, a shorter second settle behind
-    # the stage pass's summary, fence, timed region.  Step counts are the same on every rank (rank 0 decides).
+    # settle (--settle-s seconds of steps, no host synchronisation inside), with --full a stage pass and a shorter second
+    # settle behind the stage pass's summary, fence, timed region.  Step counts are the same on every rank (rank 0 decides).
     gc.collect()
     gc.disable()  # a generation-2 collection inside a 50 ms timed region is a 1-3 ms outlier, not a property of the path
     settle_steps = 0
+    events_all = args.full and args.stage_events == "all"  # (a plain run records no HIP events at all)
 
     def settle(seconds, per_step):
         n = torch.tensor([max(8, int(seconds / per_step))], device=dev)
         if world > 1:
             dist.broadcast(n, 0)
         for _ in range(int(n.item())):
-            step(timed=args.stage_events == "all")
+            step(timed=events_all)
         return int(n.item())
 
     per_step = 1e-3
@@ -722,27 +802,29 @@ def main(argv=None):
         fence()
         per_step = max((time.perf_counter() - t_cal) / 8, 1e-5)
         settle_steps = 8 + settle(args.settle_s, per_step)
-    # Stage pass (untimed): HIP events around EVERY C-ABI call and around forward / backward / exchange of
-    # every step.  Sixteen event records per step cost ~0.06 ms of a ~1 ms step (measured: 1.045 ms with
-    # them, 0.987 without), so the timed region below carries events around the dominant kernel only --
-    # the two the roofline's duration needs -- and the stage table comes from this pass over the same views.
-    stage_steps = min(args.steps, 24) if args.stage_events != "none" else 0
-    ops.default_context.stage_timer = ops.StageTimer()
-    t_pass = time.perf_counter()  # (the device is busy with the settle steps: this interval includes their tail)
-    for _ in range(stage_steps):
-        step(timed=True)
-    fence()
-    stage_pass_ms = (time.perf_counter() - t_pass) / max(stage_steps, 1) * 1e3
-    stages = ops.default_context.stage_timer.summary() if stage_steps else {}
-    ops.default_context.stage_timer = None
-    kernel_names = ("fg_raster_bwd", "fg_raster_fwd", "fg_raster_composite_bwd", "fg_raster_composite_fwd",
-                    "fg_preprocess_fwd", "fg_preprocess_bwd", "fg_bin_prepare", "fg_bin_emit_sort_capacity")
-    cand = {s: v for s, v in stages.items() if s in kernel_names}
-    dominant = max(cand, key=lambda s: cand[s]) if cand else "fg_raster_bwd"
-    only = {"all": None, "dominant": {dominant}, "none": set()}[args.stage_events]
-    ops.default_context.stage_timer = ops.StageTimer(only=only)
-    if args.settle_s > 0:
-        settle_steps += settle(max(args.settle_s / 3, 0.2), per_step)
+    stage_steps, stage_pass_ms, stages, dominant = 0, 0.0, {}, None
+    if args.full:
+        # Stage pass (untimed): HIP events around EVERY C-ABI call and around forward / backward / exchange of
+        # every step.  Sixteen event records per step cost ~0.06 ms of a ~1 ms step (measured: 1.045 ms with
+        # them, 0.987 without), so the timed region below carries events around the dominant kernel only --
+        # the two the roofline's duration needs -- and the stage table comes from this pass over the same views.
+        stage_steps = min(args.steps, 24) if args.stage_events != "none" else 0
+        ops.default_context.stage_timer = ops.StageTimer()
+        t_pass = time.perf_counter()  # (the device is busy with the settle steps: this interval includes their tail)
+        for _ in range(stage_steps):
+            step(timed=True)
+        fence()
+        stage_pass_ms = (time.perf_counter() - t_pass) / max(stage_steps, 1) * 1e3
+        stages = ops.default_context.stage_timer.summary() if stage_steps else {}
+        ops.default_context.stage_timer = None
+        kernel_names = ("fg_raster_bwd", "fg_raster_fwd", "fg_raster_composite_bwd", "fg_raster_composite_fwd",
+                        "fg_preprocess_fwd", "fg_preprocess_bwd", "fg_bin_prepare", "fg_bin_emit_sort_capacity")
+        cand = {s: v for s, v in stages.items() if s in kernel_names}
+        dominant = max(cand, key=lambda s: cand[s]) if cand else "fg_raster_bwd"
+        only = {"all": None, "dominant": {dominant}, "none": set()}[args.stage_events]
+        ops.default_context.stage_timer = ops.StageTimer(only=only)
+        if args.settle_s > 0:
+            settle_steps += settle(max(args.settle_s / 3, 0.2), per_step)
     redo0 = ops.default_context.capacity_redos
 
     def path_events():
@@ -757,19 +839,25 @@ def main(argv=None):
         ops.default_context.stage_timer = ops.StageTimer(only=only, prewarm=(args.steps + 2) * max(len(only), 1) if only else 0)
     fence()
     events0 = path_events()
+    # the timed region's views follow from the step index alone (the settle's step count follows the clocks): the same
+    # arguments give the same last step, whose outputs --dump-outputs writes
+    counter[0] = 0
     t0 = time.perf_counter()
     views_seen = []
     host_marks = [t0]
     for _ in range(args.steps):
-        info, view = step(timed=args.stage_events == "all")
+        info, view = step(timed=events_all)
         views_seen.append(view)
         host_marks.append(time.perf_counter())
     fence()
     dt_local = time.perf_counter() - t0
     events1 = path_events()
     gc.enable()
-    timed_stages = ops.default_context.stage_timer.summary()
-    dom_series = [a.elapsed_time(b) for a, b in ops.default_context.stage_timer.events.get(dominant, [])]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *last_out[0], params, info)
+    timer = ops.default_context.stage_timer
+    timed_stages = timer.summary() if timer is not None else {}
+    dom_series = [a.elapsed_time(b) for a, b in timer.events.get(dominant, [])] if timer is not None else []
     ops.default_context.stage_timer = None
     if os.environ.get("FG_BENCH_SERIES"):  # per-step durations of the dominant kernel and host marks (diagnosis)
         print("[bench] dominant kernel ms per timed step:", [round(x, 4) for x in dom_series], file=sys.stderr)
@@ -793,7 +881,44 @@ def main(argv=None):
         dist.all_gather_object(rank_devices, mine)
     dt = float(t.item())
 
+    def emit(out):
+        if rank == 0:
+            if world > 1 or force:
+                # RCCL writes a version banner through C stdio on its first collective; on a pipe that buffer is flushed when
+                # the process exits -- BEHIND this line.  Flush it now: the result stays the last line of stdout.
+                import ctypes
+
+                ctypes.CDLL(None).fflush(None)
+            print(json.dumps(out), flush=True)
+        if world > 1 or force:
+            dist.barrier()
+            dist.destroy_process_group()
+
     N = args.n_gauss
+    P = W * H
+    step_s = dt / args.steps
+    workload = ((f"north-star cfg4: {N} Gaussians" if scene_prov is None else f"TRAINED scene ({N} Gaussians, its own cameras)")
+                + f", {W}x{H}, SH degree {args.sh_degree}, 1 view per rank per step, "
+                + ("view = rank (fixed)" if args.fixed_view else f"view = (rank + step) mod {N_VIEWS} around the 8-view ring")
+                + ", fwd+bwd, RGB, absgrad" + (f", {'RCCL' if backend == 'nccl' else backend} gradient exchange ({exchange})" if world > 1 else ""))  # fmt: skip
+    head = {
+        "metric": "Mpixels/s fwd+bwd @ 1M Gaussians 1080p",
+        "value": world * args.steps * P / dt / 1e6,
+        "unit": "Mpix/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": step_s * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic",
+    }
+    if not args.full:
+        # a plain run: the headline and what it was measured on; everything below is --full's
+        return emit(dict(head, config={"workload": workload, "layout": args.layout, "N": N, "P": P, "parallelism": f"view-dp{world}"}))
+
     scene_stats = None
     if scene_prov is not None:
         from freegaussian_amd.scenes import scene_statistics
@@ -802,7 +927,6 @@ def main(argv=None):
     V = int((info["radii"] > 0).sum())
     I_raster = int(info["raster_flatten_ids"].numel())  # entries the compositing walks (footprint rectangles)
     I = int(info["flatten_ids"].numel())  # the reference's list length (radius boxes): SURVEY section 8d's I
-    P = W * H
     T = info["tile_width"] * info["tile_height"]
     k = (args.sh_degree + 1) ** 2
     nbits = 32 + max(T - 1, 1).bit_length()
@@ -910,25 +1034,10 @@ def main(argv=None):
         "mpix_per_s_per_gpu_from_median": P / max(pct(t_fb, 0.5) * 1e-3, 1e-9) / 1e6,
         "from": "timed region" if args.stage_events == "all" else f"stage pass of {stage_steps} untimed steps before the timed region",
     }  # fmt: skip
-    step_s = dt / args.steps
     out = {
-        "metric": "Mpixels/s fwd+bwd @ 1M Gaussians 1080p",
-        "value": world * args.steps * P / dt / 1e6,
-        "unit": "Mpix/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": step_s * 1e3,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic",
+        **head,
         "config": {
-            "workload": (f"north-star cfg4: {N} Gaussians" if scene_prov is None else f"TRAINED scene ({N} Gaussians, its own cameras)")
-            + f", {W}x{H}, SH degree {args.sh_degree}, 1 view per rank per step, "
-            + ("view = rank (fixed)" if args.fixed_view else f"view = (rank + step) mod {N_VIEWS} around the 8-view ring")
-            + ", fwd+bwd, RGB, absgrad" + (f", {'RCCL' if backend == 'nccl' else backend} gradient exchange ({exchange})" if world > 1 else ""),
+            "workload": workload,
             "layout": args.layout,
             **({} if scene_prov is None else {"scene": scene_prov, "scene_statistics": scene_stats}),
             "N": N, "V": V, "I": I, "P": P, "T": T, "k": k,
@@ -1020,20 +1129,10 @@ def main(argv=None):
         out["graphed"] = graphed
     if clustered is not None:
         out["clustered_layouts"] = clustered
-    if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(scene, view, args.cpu_crop, args.sh_degree, args.cpu_threads)
-            out["cpu_full_frame"] = cpu_full_frame(scene, view, args.sh_degree)
-        if world > 1 or force:
-            # RCCL writes a version banner through C stdio on its first collective; on a pipe that buffer is flushed when the
-            # process exits -- BEHIND this line.  Flush it now: the result stays the last line of stdout.
-            import ctypes
-
-            ctypes.CDLL(None).fflush(None)
-        print(json.dumps(out), flush=True)
-    if world > 1 or force:
-        dist.barrier()
-        dist.destroy_process_group()
+    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        out["cpu_baseline"] = cpu_baseline(scene, view, args.cpu_crop, args.sh_degree, args.cpu_threads)
+        out["cpu_full_frame"] = cpu_full_frame(scene, view, args.sh_degree)
+    emit(out)
 
 
 if __name__ == "__main__":

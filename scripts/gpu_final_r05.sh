@@ -4,7 +4,7 @@
 tag=${1:-r05_final}
 out=gpurun_out/$tag
 mkdir -p $out
-timeout 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $out/driver_command_cold.json 2> $out/driver_command_cold.err
+timeout 600 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/driver_command_cold.json 2> $out/driver_command_cold.err
 python3 -c "
 import json; d=json.loads(open('$out/driver_command_cold.json').read().strip().splitlines()[-1]); print('driver command, cold box:', round(d['value'],1), 'Mpix/s', round(d['ms_per_step'],4), 'ms; cpu_baseline grad max', d['cpu_baseline']['grad_rel_l2_hip_vs_oracle_max'], 'full frame', d['cpu_full_frame']['grad_rel_l2_hip_vs_oracle_max'], 'graphed', d.get('graphed',{}).get('ms_per_step')); print({k:(v.get('ms_per_step_median'), v.get('error')) for k,v in d.get('clustered_layouts',{}).items()})"
 bash scripts/gpu_check.sh $tag

@@ -8,7 +8,7 @@ mkdir -p $out
 export TMPDIR=/tmp
 R=$PWD
 T=data/trained_scene_r06.npz
-timeout 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $out/driver_command_cold.json 2> $out/driver_command_cold.err
+timeout 600 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/driver_command_cold.json 2> $out/driver_command_cold.err
 python3 -c "
 import json; d=json.loads([l for l in open('$out/driver_command_cold.json').read().strip().splitlines() if l.startswith('{')][-1]); print('driver command, cold box:', round(d['value'],1), 'Mpix/s', round(d['ms_per_step'],4), 'ms; cpu_baseline grad max', d['cpu_baseline']['grad_rel_l2_hip_vs_oracle_max'], 'full frame', d['cpu_full_frame']['grad_rel_l2_hip_vs_oracle_max'], 'graphed', d.get('graphed',{}).get('ms_per_step'), d['host_step_ms'], d['path_events_in_timed_region']); print({k:(v.get('ms_per_step'), v.get('ms_per_step_median'), v.get('host_step_ms_p99'), v.get('error')) for k,v in d.get('clustered_layouts',{}).items()})"
 bash scripts/gpu_check.sh $tag
@@ -17,7 +17,7 @@ tail -8 gpurun_out/${tag}_pmc.txt | cut -c1-160
 cd /tmp
 for lay in clustered:0.5:0.4 clustered:0.8:0.2 needles:0.3:10 trained:$R/$T; do
   tag2=$(echo $lay | sed 's/[:.+\/]/_/g' | cut -c1-24)
-  timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$out/prof_$tag2 -o stats -- python3 $R/bench.py --layout $lay --steps 40 --warmup 10 --no-cpu-baseline --no-graph --no-clustered > $R/$out/prof_$tag2.json 2> $R/$out/prof_$tag2.err
+  timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$out/prof_$tag2 -o stats -- python3 $R/bench.py --full --layout $lay --steps 40 --warmup 10 --no-cpu-baseline --no-graph --no-clustered > $R/$out/prof_$tag2.json 2> $R/$out/prof_$tag2.err
   find $R/$out/prof_$tag2 -name "*kernel_stats*" -exec cp {} $R/$out/kernel_stats_$tag2.csv \;
   rm -rf $R/$out/prof_$tag2
   echo "== $lay"; python3 - <<PY

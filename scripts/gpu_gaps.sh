@@ -5,7 +5,7 @@ tag=${1:-gaps}; shift
 out=gpurun_out/$tag
 mkdir -p $out
 export TMPDIR=/tmp
-timeout 400 rocprofv3 --kernel-trace --output-format csv -d $out/prof -o t -- python3 bench.py --steps 40 --warmup 10 --no-cpu-baseline --no-graph "$@" > $out/bench.json 2> $out/err.log
+timeout 400 rocprofv3 --kernel-trace --output-format csv -d $out/prof -o t -- python3 bench.py --full --steps 40 --warmup 10 --no-cpu-baseline --no-graph "$@" > $out/bench.json 2> $out/err.log
 f=$(find $out/prof -name "*kernel_trace.csv" | head -1)
 python scripts/trace_gaps.py $f > $out/gaps.txt 2>&1
 rm -f $f

@@ -8,7 +8,7 @@ mkdir -p $out
 export TMPDIR=/tmp
 for d in 0 1 2 3; do
   for c in FETCH_SIZE WRITE_SIZE; do
-    timeout 300 rocprofv3 --pmc $c --output-format csv -d $out/pmc_d${d}_$c -o c -- python3 bench.py --sh-degree $d --steps 3 --warmup 2 --no-cpu-baseline --no-graph > /dev/null 2> $out/pmc_d${d}_$c.err
+    timeout 300 rocprofv3 --pmc $c --output-format csv -d $out/pmc_d${d}_$c -o c -- python3 bench.py --full --sh-degree $d --steps 3 --warmup 2 --no-cpu-baseline --no-graph > /dev/null 2> $out/pmc_d${d}_$c.err
   done
 done
 python3 - <<PY
@@ -34,6 +34,6 @@ for sz in "100000 50 480 270" "300000 50 960 540" "1000000 30 1920 1080"; do tim
 timeout 600 python scripts/half_strip_estimate.py 2>/dev/null | tee $out/half_strip_estimate.txt | tail -4
 bash scripts/gpu_sizes.sh 2>/dev/null | tee $out/sizes.txt
 for b in depthfirst supertile depthfirst supertile; do
-  FG_BINNING=$b timeout 300 python bench.py --steps 50 --warmup 10 --no-cpu-baseline --no-graph 2>/dev/null | python3 -c "
+  FG_BINNING=$b timeout 300 python bench.py --full --steps 50 --warmup 10 --no-cpu-baseline --no-graph 2>/dev/null | python3 -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('$b', round(d['value'],1), round(d['ms_per_step'],4), d['stage_ms'])" | tee -a $out/binning_ab.txt
 done

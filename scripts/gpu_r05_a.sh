@@ -12,7 +12,7 @@ for lay in uniform clustered:0.5:0.4; do
 done
 for lay in needles:0.3:10 clustered:0.5:0.4+needles:0.3:10 needles:1.0:10; do
   f=$out/bench_${lay//[:.+]/_}
-  timeout 300 python bench.py --layout $lay --steps 40 --warmup 10 --no-cpu-baseline --no-graph > $f.json 2> $f.err
+  timeout 300 python bench.py --full --layout $lay --steps 40 --warmup 10 --no-cpu-baseline --no-graph > $f.json 2> $f.err
   python3 -c "
 import json,sys; d=json.load(open('$f.json')); print('$lay', round(d['value'],1), 'Mpix/s', round(d['ms_per_step'],4), 'ms', d['stage_ms'], 'I_raster', d['config']['I_raster'], 'longest', d['config'].get('longest_tile_list'))" || tail -3 $f.err
 done

@@ -13,5 +13,5 @@ import json; d=json.load(open('$out/refine_${pool}_${lay//[:.]/_}.json')); print
     grep "diag step 320[01]" $out/refine_${pool}_${lay//[:.]/_}.err | cut -c1-200
   done
 done
-for i in 1 2; do timeout 300 python bench.py --steps 50 --warmup 10 --no-cpu-baseline --no-graph --no-clustered > $out/b$i.json 2> $out/b$i.err; python3 -c "
+for i in 1 2; do timeout 300 python bench.py --full --steps 50 --warmup 10 --no-cpu-baseline --no-graph --no-clustered > $out/b$i.json 2> $out/b$i.err; python3 -c "
 import json; d=json.loads(open('$out/b$i.json').read().strip().splitlines()[-1]); print(round(d['value'],1), round(d['ms_per_step'],4), d['stage_ms'], d.get('host_step_ms'))"; done

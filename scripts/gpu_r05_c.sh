@@ -9,7 +9,7 @@ for rep in 1 2; do
 for exact in 1 0; do
 for lay in uniform needles:0.3:10; do
   f=$out/bench_${lay//[:.+]/_}_exact${exact}_$rep
-  FG_EXACT_TILES=$exact timeout 300 python bench.py --layout $lay --steps 40 --warmup 10 --no-cpu-baseline --no-graph --no-clustered > $f.json 2> $f.err
+  FG_EXACT_TILES=$exact timeout 300 python bench.py --full --layout $lay --steps 40 --warmup 10 --no-cpu-baseline --no-graph --no-clustered > $f.json 2> $f.err
   python3 -c "
 import json,sys; d=json.load(open('$f.json')); print('exact=$exact', '$lay', 'median', round(d['host_step_ms']['median'],4), 'mean', round(d['ms_per_step'],4), 'ms', d['stage_ms'], 'I_raster', d['config']['I_raster'])" || tail -3 $f.err
 done; done; done

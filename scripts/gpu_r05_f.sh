@@ -30,8 +30,8 @@ for n in ("uniform", "0.5_0.4", "0.8_0.2"):
 PY
 for lay in clustered:0.5:0.4 clustered:0.8:0.2; do
   tag=${lay//[:.+]/_}
-  timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_$tag -o stats -- python3 bench.py --layout $lay --steps 40 --warmup 10 --no-cpu-baseline --no-graph --no-clustered > $out/prof_$tag.json 2> $out/prof_$tag.err
+  timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_$tag -o stats -- python3 bench.py --full --layout $lay --steps 40 --warmup 10 --no-cpu-baseline --no-graph --no-clustered > $out/prof_$tag.json 2> $out/prof_$tag.err
   find $out/prof_$tag -name "*kernel_stats*" -exec cp {} $out/kernel_stats_$tag.csv \;
   rm -rf $out/prof_$tag
 done
-timeout 900 python bench.py > $out/bench.json 2> $out/bench.err; tail -1 $out/bench.json | cut -c1-1500
+timeout 900 python bench.py --full > $out/bench.json 2> $out/bench.err; tail -1 $out/bench.json | cut -c1-1500

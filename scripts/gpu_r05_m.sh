@@ -8,7 +8,7 @@ cd /tmp
 prof() {  # tag layout env...
   local tag=$1 lay=$2; shift 2
   for kv in "$@"; do export "$kv"; done
-  rocprofv3 --kernel-trace -d $R/$out/prof_$tag -o p -- python3 $R/bench.py --layout $lay --steps 32 --warmup 8 --no-cpu-baseline --no-graph --no-clustered > $R/$out/prof_$tag.json 2> $R/$out/prof_$tag.err
+  rocprofv3 --kernel-trace -d $R/$out/prof_$tag -o p -- python3 $R/bench.py --full --layout $lay --steps 32 --warmup 8 --no-cpu-baseline --no-graph --no-clustered > $R/$out/prof_$tag.json 2> $R/$out/prof_$tag.err
   for kv in "$@"; do unset "${kv%%=*}"; done
   echo "== $tag $lay $*"
   python3 $R/scripts/rocprof_top.py $R/$out/prof_$tag/p_results.db 4 raster

@@ -8,7 +8,7 @@ tail -4 $out/pytest_wide.log
 run() {  # name, layout, env...
   local tag=$1 lay=$2; shift 2
   local f=$out/b_${tag}_${lay//[:.+]/_}
-  env "$@" timeout 200 python bench.py --layout $lay --steps 32 --warmup 8 --settle-s 0.5 --no-cpu-baseline --no-graph --no-clustered > $f.json 2> $f.err
+  env "$@" timeout 200 python bench.py --full --layout $lay --steps 32 --warmup 8 --settle-s 0.5 --no-cpu-baseline --no-graph --no-clustered > $f.json 2> $f.err
   python3 -c "
 import json,sys; d=json.loads(open('$f.json').read().strip().splitlines()[-1]); s=d['stage_ms']; print('$tag $lay', 'median', round(d['host_step_ms']['median'],4), 'fwd', s.get('fg_raster_fwd'), 'bwd', s.get('fg_raster_bwd'), 'fill', s.get('fg_bin_emit_sort_capacity'), 'heavy_steps', d['config'].get('heavy_tile_steps'))" || tail -2 $f.err
 }
@@ -24,7 +24,7 @@ cd /tmp
 for lay in clustered:0.8:0.2 clustered:0.5:0.4; do
   for heavy in 2560 1536; do
     tag=${lay//[:.+]/_}_$heavy
-    FG_HEAVY_TILE_LEN=$heavy rocprofv3 --kernel-trace -d $R/$out/prof_$tag -o p -- python3 $R/bench.py --layout $lay --steps 32 --warmup 8 --no-cpu-baseline --no-graph --no-clustered > $R/$out/prof_$tag.json 2> $R/$out/prof_$tag.err
+    FG_HEAVY_TILE_LEN=$heavy rocprofv3 --kernel-trace -d $R/$out/prof_$tag -o p -- python3 $R/bench.py --full --layout $lay --steps 32 --warmup 8 --no-cpu-baseline --no-graph --no-clustered > $R/$out/prof_$tag.json 2> $R/$out/prof_$tag.err
     echo "== $tag"; python3 $R/scripts/rocprof_top.py $R/$out/prof_$tag/p_results.db 3 raster; rm -rf $R/$out/prof_$tag
   done
 done

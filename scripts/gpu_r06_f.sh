@@ -9,7 +9,7 @@ timeout 1500 python -m pytest tests/test_gpu_parity.py -m gpu -x -q -k "binning 
 cd /tmp
 for lay in uniform needles:0.3:10 trained:$R/$T; do
   tag=$(echo $lay | sed 's/[:.+\/]/_/g' | cut -c1-24)
-  timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$out/prof_$tag -o stats -- python3 $R/bench.py --layout $lay --steps 40 --warmup 10 --no-cpu-baseline --no-graph --no-clustered > $R/$out/prof_$tag.json 2> $R/$out/prof_$tag.err
+  timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$out/prof_$tag -o stats -- python3 $R/bench.py --full --layout $lay --steps 40 --warmup 10 --no-cpu-baseline --no-graph --no-clustered > $R/$out/prof_$tag.json 2> $R/$out/prof_$tag.err
   find $R/$out/prof_$tag -name "*kernel_stats*" -exec cp {} $R/$out/kernel_stats_$tag.csv \;
   rm -rf $R/$out/prof_$tag
   echo "== $lay"

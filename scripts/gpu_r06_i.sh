@@ -14,7 +14,7 @@ for i,r in enumerate(b["rows"]):
 PY
 for lay in clustered:0.5:0.4 clustered:0.8:0.2 trained:data/trained_scene_r06.npz uniform; do
   for w in 1 0; do
-    FG_TILE_WALKS=$w timeout 300 python bench.py --layout $lay --steps 48 --warmup 10 --no-cpu-baseline --no-graph --no-clustered > $out/b.json 2> $out/b.err
+    FG_TILE_WALKS=$w timeout 300 python bench.py --full --layout $lay --steps 48 --warmup 10 --no-cpu-baseline --no-graph --no-clustered > $out/b.json 2> $out/b.err
     python3 -c "
 import json; d=json.loads([l for l in open('$out/b.json').read().strip().splitlines() if l.startswith('{')][-1]); print('$lay walks=$w', round(d['ms_per_step'],4), 'median', round(d['host_step_ms']['median'],4), {k:v for k,v in d['stage_ms'].items() if 'raster' in k})"
   done

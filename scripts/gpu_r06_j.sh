@@ -13,7 +13,7 @@ PY
 done
 for lib in libfgraster.so libfgraster_cap1536.so; do
 for lay in clustered:0.5:0.4 clustered:0.8:0.2 needles:0.3:10; do
-    FG_RASTER_LIB=$PWD/freegaussian_amd/$lib timeout 300 python bench.py --layout $lay --steps 48 --warmup 10 --no-cpu-baseline --no-graph --no-clustered > $out/b.json 2> $out/b.err
+    FG_RASTER_LIB=$PWD/freegaussian_amd/$lib timeout 300 python bench.py --full --layout $lay --steps 48 --warmup 10 --no-cpu-baseline --no-graph --no-clustered > $out/b.json 2> $out/b.err
     python3 -c "
 import json; d=json.loads([l for l in open('$out/b.json').read().strip().splitlines() if l.startswith('{')][-1]); print('$lib $lay', round(d['ms_per_step'],4), 'median', round(d['host_step_ms']['median'],4), {k:v for k,v in d['stage_ms'].items() if 'raster' in k})"
 done

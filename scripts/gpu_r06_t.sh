@@ -9,7 +9,7 @@ timeout 1500 python -m pytest tests/test_gpu_parity.py -m gpu -x -q -k "binning 
 cd /tmp
 for lay in clustered:0.5:0.4 clustered:0.8:0.2 trained:$R/data/trained_scene_r06.npz; do
   tag2=$(echo $lay | sed 's/[:.+\/]/_/g' | cut -c1-24)
-  timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$out/prof_$tag2 -o stats -- python3 $R/bench.py --layout $lay --steps 40 --warmup 10 --no-cpu-baseline --no-graph --no-clustered > $R/$out/prof_$tag2.json 2> $R/$out/prof_$tag2.err
+  timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$out/prof_$tag2 -o stats -- python3 $R/bench.py --full --layout $lay --steps 40 --warmup 10 --no-cpu-baseline --no-graph --no-clustered > $R/$out/prof_$tag2.json 2> $R/$out/prof_$tag2.err
   find $R/$out/prof_$tag2 -name "*kernel_stats*" -exec cp {} $R/$out/kernel_stats_$tag2.csv \;
   rm -rf $R/$out/prof_$tag2
   echo "== $lay"; python3 - <<PY

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Classic vs mixed forward launch at other sizes.  Usage: gpurun -- 'bash scripts/gpu_sizes.sh'
 run() {
-  env $1 timeout 300 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-graph --n-gauss $2 --width $3 --height $4 2>/dev/null | python3 -c "
+  env $1 timeout 300 python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-graph --n-gauss $2 --width $3 --height $4 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); s=d['stage_ms']
 print('$1'.ljust(46), 'N=$2 $3x$4', 'fwd %.4f bwd %.4f step %.4f I=%d' % (s['fg_raster_fwd'], s['fg_raster_bwd'], d['ms_per_step'], d['config']['I']))"

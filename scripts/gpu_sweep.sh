@@ -4,7 +4,7 @@ tag=${1:-sweep}
 out=gpurun_out/$tag
 mkdir -p $out
 for f in 1 2 4; do for b in 1 2 4; do
-  FG_RASTER_PPT_FWD=$f FG_RASTER_PPT_BWD=$b timeout 200 python bench.py --steps 10 --warmup 3 --no-cpu-baseline > $out/b_${f}_${b}.json 2>/dev/null
+  FG_RASTER_PPT_FWD=$f FG_RASTER_PPT_BWD=$b timeout 200 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline > $out/b_${f}_${b}.json 2>/dev/null
 done; done
 python3 - <<PY
 import json,glob

@@ -215,7 +215,7 @@ def test_bench_trains_its_own_scene_when_the_checkpoint_file_is_absent():
     import subprocess
 
     env = dict(os.environ, FG_BENCH_TRAIN_HERE="1", FG_BENCH_TRAIN="400,20000,480,270,6000")
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--layout", "trained:auto", "--steps", "12", "--warmup", "4",
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--layout", "trained:auto", "--steps", "12", "--warmup", "4",
                           "--settle-s", "0.2", "--no-cpu-baseline", "--no-graph", "--no-clustered"], capture_output=True, text=True, env=env, timeout=600)  # fmt: skip
     lines = [ln for ln in res.stdout.strip().splitlines() if ln.startswith("{")]
     assert res.returncode == 0 and lines, res.stderr[-2000:]

@@ -2449,7 +2449,7 @@ def test_world_size_8_exchange_and_bench_launcher_over_gloo_on_one_gpu():
         assert out.returncode == 0 and "exchange ok" in out.stdout and "world=8" in out.stdout, out.stdout[-2000:] + out.stderr[-2000:]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(FG_BENCH_BACKEND="gloo", OMP_NUM_THREADS="4")
-    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "1",
+    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "8", "--steps", "3", "--warmup", "1",
                           "--n-gauss", "50000", "--width", "640", "--height", "360"], env=env, capture_output=True,
                          text=True, timeout=900)  # fmt: skip
     assert res.returncode == 0, res.stderr[-3000:]
