@@ -114,6 +114,8 @@ class FreeGaussianModelConfig:
     fused_front_end: bool = True
 
 
+_EVAL_BACKGROUND = {"random": torch.tensor([0.1490, 0.1647, 0.2157]), "white": torch.ones(3), "black": torch.zeros(3)}
+
 _POSE_RING = None
 
 
@@ -173,7 +175,9 @@ class FreeGaussianModel(nn.Module):
             gx, gy, gw = self.config.grid_shape
             self.bil_grids = BilateralGrid(num=int(num_train_data), grid_X=gx, grid_Y=gy, grid_W=gw)
         self.step = 0
-        self.background_color = torch.zeros(3)
+        # (:221-226) Viser's default grey for "random", else the named colour: what an eval render composites over with
+        # background "random" (:653), and the colour of the empty-crop output in every mode (:782)
+        self.background_color = _EVAL_BACKGROUND[self.config.background_color].clone()
         self.xys: Optional[torch.Tensor] = None
         self.radii: Optional[torch.Tensor] = None
         self.xys_grad_norm: Optional[torch.Tensor] = None
@@ -321,6 +325,9 @@ class FreeGaussianModel(nn.Module):
             assert bool((cam0.get_intrinsics_matrices() == camera.get_intrinsics_matrices()).all()), \
                 "Intrinsics matrices should be the same"
         s = self._get_downscale_factor()
+        # Without a cameras0 of its own the reference aliases it to the camera (:769-770) and rescales that one object
+        # twice (:807-808): a d^2 render at d > 1.  Training cameras always carry their own (the data parser's), so the
+        # alias only matters to a viewer render at training time; here the camera is rescaled once.
         # The reference rescales by 1/s and later by s (:807-808, :813-814).  With floor rounding that
         # does not restore a size that s does not divide (1014 -> 253 -> 1012): its camera objects
         # shrink once and, one schedule step later, render 506 rows against a 507-row target.  Here the

@@ -571,6 +571,13 @@ def rasterization(
     assert viewmats.shape[0] == 1 and Ks.shape[0] == 1, "one camera at a time"
     viewmat, K = viewmats[0], Ks[0]
     N = means.shape[0]
+    if sh_degree is None:
+        # gsplat 1.x (rendering.py): assert (colors.dim() == 2 and colors.shape[0] == N) or
+        # (colors.dim() == 3 and colors.shape[:2] == (C, N)) -- post-activation colours [N,D] or [C,N,D], C = 1 here.
+        # (The reference's sigmoid path hands it [N,1,3]: an AssertionError there for any N > 1.)
+        assert (colors.dim() == 2 and colors.shape[0] == N) or (colors.dim() == 3 and colors.shape[:2] == (1, N)), colors.shape
+        if colors.dim() == 3:
+            colors = colors[0]
     proj = project(means, quats, scales, viewmat, K, width, height, eps2d, near_plane, far_plane, radius_clip)
     opac = opacities
     if rasterize_mode == "antialiased":

@@ -19,6 +19,18 @@ What is captured -- data only, no reference source text 
   g_densify.npz refinement_after / split_gaussians / dup_gaussians / cull_gaussians / the
                 optimizer surgery and after_train_iter, executed as methods of a stub ``self``
                                                             (freegaussian_model.py:313-392, :404-571)
+  g_outputs.npz stage-1 get_outputs (H1-H4, O1): camera rescale, deform, SH-degree
+                schedule, background composite + clamp, crop, ED depth rule, bilateral grid, in float64
+                                                            (freegaussian_model.py:753-898)
+  g_control.npz stage-2 get_outputs ((f)-1): control-point averages, the scatter into the full set
+                                                            (freegaussian_control_model.py:52-209)
+  g_loss.npz    get_loss_dict / get_metrics_dict / composite_with_background / get_gt_img
+                                                            (freegaussian_model.py:900-990)
+  g_knn.npz     the key-frame mask back-projection ((f)-4)  (preprocess/knn_gaussian.py:114-132)
+
+The raster itself (K0-K8) is NOT pinned to a reference run: gsplat is not part of the reference and
+cannot run here, so the four model-surface fixtures use oracle/raster_oracle.py, the gsplat-1.x
+restatement, in its place, and the raster stays pinned only to that restatement.
 
 The reference modules import nerfstudio / mmflow, which are not installed; utils.py is loaded
 with a stub for its single non-torch import and the two other pieces are executed from their
@@ -469,11 +481,688 @@ def gen_flow_query(U):
     print("g_flow_query.npz", {k: tuple(v.shape) for k, v in d.items() if k in ("plain", "grid_16_8", "grid_8_2")})
 
 
+# ------------------------------------------------------------------------------------------------
+# The model surface: get_outputs (stages 1 and 2), the losses, the key-frame mask back-projection.
+# Everything below the "tables" line is shared with tests/test_reference_goldens.py, which imports it.
+
+IMG_W, IMG_H = 48, 32
+GAUSS = ("means", "scales", "quats", "features_dc", "features_rest", "opacities")
+HEADS = ("branch_w", "branch_v", "gaussian_rotation", "gaussian_scaling", "d_xyz", "d_scale", "d_rot")
+# the output heads of the seeded MLPs are scaled down: deltas of a few percent of the scene, scale deltas well below
+# the splat sizes (exp(scales) ~ 0.05) so that no covariance degenerates
+HEAD_GAIN = {"branch_w": 0.05, "branch_v": 0.05, "gaussian_rotation": 0.05, "gaussian_scaling": 0.002, "d_xyz": 0.05,
+             "d_rot": 0.05, "d_scale": 0.002}  # fmt: skip
+SKETCH = 256
+MIN_TIME_RESPONSE = 1e-3  # the seeded deform net must move a point this much between two times (well above fp32 rounding)
+
+
+def mlp_weights(module):
+    """Deterministic He-uniform weights for the MLPs of the model-surface fixtures, applied alike to the reference's
+    and the build's modules (same parameter names): entry i of the k-th parameter (sorted by name) is
+    bound * (2 u - 1), u = frac(43758.5453 sin(12.9898 i + 78.233 (k + 1))), bound = sqrt(6 / fan_in) (0.05 for
+    biases), the output heads scaled by HEAD_GAIN.  Unlike fill_params' smooth rows, these keep the signal -- and the
+    response to time -- through the eight-layer trunk."""
+    with torch.no_grad():
+        for k, (name, p) in enumerate(sorted(module.named_parameters())):
+            i = torch.arange(p.numel(), dtype=torch.float64)
+            x = torch.sin(i * 12.9898 + 78.233 * (k + 1)) * 43758.5453
+            u = x - torch.floor(x)
+            bound = (6.0 / p.shape[-1]) ** 0.5 if p.dim() > 1 else 0.05
+            vals = (2 * u - 1) * bound * HEAD_GAIN.get(name.split(".")[0], 1.0)
+            p.copy_(vals.reshape(p.shape).to(torch.float32))
+
+
+def grad_sketch(grads):
+    """A count sketch [SKETCH] of a flat gradient (deterministic bucket and sign per entry): rel_l2 of two sketches
+    follows rel_l2 of the full vectors, at a size a fixture can hold."""
+    g = torch.cat([t.detach().reshape(-1).double().cpu() for t in grads])
+    j = torch.arange(g.numel(), dtype=torch.int64)
+    bucket = (j * 2654435761) % SKETCH
+    sign = torch.where(torch.sin(j.double() * 0.913 + 0.5) >= 0, 1.0, -1.0).double()
+    return torch.zeros(SKETCH, dtype=torch.float64).index_add_(0, bucket, g * sign)
+
+
+def mlp_grads(module):
+    """(head gradients by name, sketch of every gradient) of an MLP after backward."""
+    named = [(n, p.grad if p.grad is not None else torch.zeros_like(p)) for n, p in module.named_parameters()]
+    return {n: g for n, g in named if n.split(".")[0] in HEADS}, grad_sketch([g for _, g in named])
+
+
+def cotangent(shape, k):
+    """A fixed, RNG-free cotangent of the given shape (the test's loss is sum(output * cotangent))."""
+    n = int(np.prod(shape))
+    return torch.sin(torch.arange(n, dtype=torch.float64) * (0.61 + 0.013 * k) + 0.3 * k).reshape(shape)
+
+
+def cotangent_loss(out):
+    """The seeded scalar whose gradient the fixtures store: rgb, accumulation, and the depth weighted by the
+    accumulation (no gradient through it), so pixels of vanishing alpha do not dominate."""
+    rgb, acc = out["rgb"], out["accumulation"]
+    loss = (rgb * cotangent(rgb.shape, 0).to(rgb)).sum() + (acc * cotangent(acc.shape, 1).to(acc)).sum()
+    if out.get("depth") is not None:
+        d = out["depth"]
+        loss = loss + 0.1 * (d * acc.detach() * cotangent(d.shape, 2).to(d)).sum()
+    return loss
+
+
+def scene_camera(times=0.4, W=IMG_W, H=IMG_H):
+    """c2w [1,3,4] (OpenGL axes) of a camera 3 units from the origin looking at it, slightly turned; fx fy cx cy."""
+    a, b = 0.12, -0.07
+    Ry = torch.tensor([[np.cos(a), 0, np.sin(a)], [0, 1, 0], [-np.sin(a), 0, np.cos(a)]])
+    Rx = torch.tensor([[1, 0, 0], [0, np.cos(b), -np.sin(b)], [0, np.sin(b), np.cos(b)]])
+    R = (Ry @ Rx).float()
+    c2w = torch.cat([R, (R @ torch.tensor([0.05, -0.03, 3.0]))[:, None]], -1)[None]
+    f = W * 0.95
+    return c2w, (f, f * 1.02, W / 2 - 0.5, H / 2 + 0.25), torch.tensor([[times]])
+
+
+def scene_params(n, k_rest, seed, spread=(0.8, 0.6, 0.5)):
+    """Seeded Gaussians in front of scene_camera (fp32 values: the build reads them exactly)."""
+    g = torch.Generator().manual_seed(seed)
+    means = (torch.rand(n, 3, generator=g) * 2 - 1) * torch.tensor(spread)
+    return {
+        "means": means,
+        "scales": torch.randn(n, 3, generator=g) * 0.3 - 3.0,
+        "quats": torch.randn(n, 4, generator=g),
+        "features_dc": torch.randn(n, 3, generator=g) * 1.5,  # colours past 1: the clamp after the composite acts
+        "features_rest": torch.randn(n, k_rest, 3, generator=g) * 0.15,
+        "opacities": torch.randn(n, 1, generator=g) * 1.5 + 0.5,
+    }
+
+
+# (tag, training, step, config overrides, extra)  -- stage 1 (g_outputs.npz)
+OUTPUT_BASE = dict(warm_up=3000, resolution_schedule=3000, num_downscales=0, sh_degree=1, sh_degree_interval=1000,
+                   background_color="white", rasterize_mode="classic", output_depth_during_training=False,
+                   use_bilateral_grid=False, grid_shape=(4, 4, 2))  # fmt: skip
+OUTPUT_CASES = [
+    ("warmup", True, 1500, {"sh_degree": 3}, None),  # step < warm_up: no deform; SH degree 1 of 3
+    # deform on, d = 4 and d = 2 (black: on a white background the clamp at 1 is a knife edge for many pixels)
+    ("down4", True, 3500, {"num_downscales": 2, "resolution_schedule": 4000, "background_color": "black"}, None),
+    ("down2", True, 4500, {"num_downscales": 2, "resolution_schedule": 4000, "background_color": "black"}, None),
+    ("eval_ed", False, 30000, {}, None),  # RGB+ED, empty corners (alpha == 0), background expanded to HxW
+    ("crop", False, 30000, {}, "crop"),  # crop box holding some Gaussians
+    ("crop_empty", False, 30000, {}, "crop_empty"),  # crop box holding none: get_empty_outputs
+    ("sh0", True, 5000, {"sh_degree": 0}, None),  # the sigmoid colour path
+    ("antialiased", True, 5000, {"rasterize_mode": "antialiased"}, None),
+    ("eval_random", False, 30000, {"background_color": "random"}, None),  # the eval colour of "random"
+    ("bilagrid", True, 5000, {"use_bilateral_grid": True, "background_color": "black"}, "bilagrid"),
+]
+OUTPUT_N = 200
+# cases whose first draw put a covered pixel within CLAMP_EDGE of the clamp (see _near_clamp): drawn again
+OUTPUT_RESEED = {"antialiased": 1}
+BIL_NUM, BIL_CAM = 3, 1
+CROP_BOXES = {"crop": ([0.2, 0.0, 0.0], [0.9, 1.0, 1.2]), "crop_empty": ([5.0, 5.0, 5.0], [0.5, 0.5, 0.5])}
+
+# stage 2 (g_control.npz): (tag, training, cameras0, mask layout, crop)
+CONTROL_CASES = [
+    ("eval_cam0", False, True, "base", None),
+    ("eval_nocam0", False, False, "base", None),  # the controller's values
+    ("train", True, True, "base", None),
+    ("overlap", False, True, "overlap", None),  # many Gaussians in two attributes
+    ("crop", False, True, "base", ([0.3, 0.0, 0.0], [1.0, 1.4, 1.2])),  # the box cuts the masks
+]
+CONTROL_N, CONTROL_M = 160, 3
+
+
+def control_mask(layout, n=CONTROL_N):
+    m = torch.zeros(n, CONTROL_M, dtype=torch.bool)
+    if layout == "base":
+        m[:30, 0] = True
+        m[20:60, 1] = True
+        m[90:110, 2] = True
+    else:
+        m[:70, 0] = True
+        m[15:90, 1] = True
+        m[50:120, 2] = True
+    return m
+
+
+# (tag, step, config overrides, batch layout)  -- g_loss.npz
+LOSS_BASE = dict(num_downscales=0, resolution_schedule=3000, ssim_lambda=0.2, use_scale_regularization=False,
+                 max_gauss_ratio=10.0, use_bilateral_grid=False, color_corrected_metrics=False, grid_shape=(4, 4, 2))  # fmt: skip
+LOSS_CASES = [
+    ("rgba", 5000, {}, "rgba"),
+    ("uint8", 5000, {}, "uint8"),
+    ("mask_d2", 100, {"num_downscales": 1}, "mask"),  # d = 2: image and mask downscaled
+    ("scale_reg10", 20, {"use_scale_regularization": True, "max_gauss_ratio": 3.0}, "rgb"),
+    ("scale_reg11", 21, {"use_scale_regularization": True, "max_gauss_ratio": 3.0}, "rgb"),
+    ("tv", 5000, {"use_bilateral_grid": True}, "rgb"),
+]
+LOSS_N = 60
+
+KNN_N, KNN_M, KNN_FRAMES = 400, 3, 3
+KNN_BORDER = [(-0.5, 10.3), (12.3, -0.6), (-0.7, -0.6), (-2.2, 12.7), (IMG_W + 0.4, 5.3), (IMG_W - 0.5, IMG_H - 0.5),
+              (-30.0, 15.2), (20.3, IMG_H + 40.0)]  # (u, v) pixel targets at depth 2.6, per key frame  # fmt: skip
+KNN_EDGE_PX, KNN_EDGE_RATIO = 1e-4, 1e-5  # an fp32 kernel may flip a Gaussian this close to a decision
+# ---------------------------------------------------------------------------------------------- tables
+
+
+def _nerfstudio_standins():
+    """Stand-ins for the nerfstudio / gsplat / pytorch_msssim / torchmetrics names the sliced methods use.
+    Restatements of those libraries (not of the reference); each is named in the fixture docstrings."""
+
+    class Cameras:
+        """nerfstudio ``Cameras`` subset: ``metadata``, ``camera_to_worlds`` [1,3,4], ``width`` / ``height`` int64
+        [1,1], ``fx fy cx cy`` [1,1], ``times`` [1,1], ``shape``, ``get_intrinsics_matrices()`` and
+        ``rescale_output_resolution(s)``, whose rule is nerfstudio's (default ``scale_rounding_mode="floor"``):
+        fx, fy, cx, cy are multiplied by s; width and height are multiplied by s and truncated to int64."""
+
+        def __init__(self, c2w, intr, W, H, times, metadata=None):
+            dt = c2w.dtype
+            self.camera_to_worlds = c2w
+            self.fx, self.fy, self.cx, self.cy = (torch.tensor([[float(v)]], dtype=dt) for v in intr)
+            self.width, self.height = torch.tensor([[W]]), torch.tensor([[H]])
+            self.times = times
+            self.metadata = {} if metadata is None else metadata
+
+        @property
+        def shape(self):
+            return self.camera_to_worlds.shape[:1]
+
+        def get_intrinsics_matrices(self):
+            K = torch.zeros(1, 3, 3, dtype=self.fx.dtype)
+            K[:, 0, 0], K[:, 1, 1], K[:, 0, 2], K[:, 1, 2] = self.fx[:, 0], self.fy[:, 0], self.cx[:, 0], self.cy[:, 0]
+            K[:, 2, 2] = 1.0
+            return K
+
+        def rescale_output_resolution(self, s):
+            self.fx, self.fy, self.cx, self.cy = self.fx * s, self.fy * s, self.cx * s, self.cy * s
+            self.height = (self.height * s).to(torch.int64)
+            self.width = (self.width * s).to(torch.int64)
+
+    class OrientedBox:
+        """nerfstudio ``OrientedBox.within``: points into the box frame (R, T), strictly inside +-S/2 on every axis."""
+
+        def __init__(self, R, T, S):
+            self.R, self.T, self.S = R, T, S
+
+        def within(self, pts):
+            local = (pts - self.T.to(pts)) @ self.R.to(pts)
+            return ((local > -self.S.to(pts) / 2) & (local < self.S.to(pts) / 2)).all(-1)
+
+    class CameraOptimizerOff:
+        """mode "off": the pose is the camera's own; no metrics, no loss."""
+
+        def apply_to_camera(self, camera):
+            return camera.camera_to_worlds
+
+        def get_metrics_dict(self, d):
+            return None
+
+        def get_loss_dict(self, d):
+            return None
+
+    def ssim64(X, Y):
+        """pytorch_msssim ``SSIM(data_range=1.0, size_average=True, channel=3)`` after its published algorithm, in fp64:
+        11-tap Gaussian window, sigma 1.5, separable 'valid' convolution, K1 = 0.01, K2 = 0.03, mean over the map."""
+        X, Y = X.double(), Y.double()
+        C = X.shape[1]
+        x = torch.arange(11, dtype=torch.float64) - 5
+        w = torch.exp(-(x * x) / (2 * 1.5**2))
+        w = w / w.sum()
+
+        def filt(t):
+            t = torch.nn.functional.conv2d(t, w.view(1, 1, 11, 1).expand(C, 1, 11, 1), groups=C)
+            return torch.nn.functional.conv2d(t, w.view(1, 1, 1, 11).expand(C, 1, 1, 11), groups=C)
+
+        mu1, mu2 = filt(X), filt(Y)
+        s11, s22, s12 = filt(X * X) - mu1 * mu1, filt(Y * Y) - mu2 * mu2, filt(X * Y) - mu1 * mu2
+        c1, c2 = 0.01**2, 0.03**2
+        cs = (2 * s12 + c2) / (s11 + s22 + c2)
+        smap = ((2 * mu1 * mu2 + c1) / (mu1 * mu1 + mu2 * mu2 + c1)) * cs
+        return smap.flatten(2).mean(-1).mean()
+
+    def psnr64(pred, gt):
+        """torchmetrics ``PeakSignalNoiseRatio(data_range=1.0)`` on one batch: 10 log10(1 / mse)."""
+        return 10 * torch.log10(1.0 / ((pred.double() - gt.double()) ** 2).mean())
+
+    def get_color(name):
+        """nerfstudio.utils.colors.get_color for the two names the configs use."""
+        return {"white": torch.tensor([1.0, 1.0, 1.0]), "black": torch.tensor([0.0, 0.0, 0.0])}[name]
+
+    return Cameras, OrientedBox, CameraOptimizerOff, ssim64, psnr64, get_color
+
+
+MODEL_METHODS = ["_get_downscale_factor", "_downscale_if_required", "get_empty_outputs", "_get_background_color",
+                 "get_outputs", "get_gt_img", "composite_with_background", "get_metrics_dict", "get_loss_dict"]  # fmt: skip
+
+
+def _populate_background(path):
+    """The statement of ``populate_modules`` that sets ``self.background_color`` (executed, never saved)."""
+    src = open(path).read()
+    for node in ast.walk(ast.parse(src)):
+        if isinstance(node, ast.FunctionDef) and node.name == "populate_modules":
+            for st in node.body:
+                if isinstance(st, ast.If) and "background_color" in ast.unparse(st.test):
+                    return ast.unparse(st)
+    raise AssertionError("populate_modules background statement not found")
+
+
+def reference_model_classes(U):
+    """Stub ``self`` classes whose methods are the reference's own (stage 1 and stage 2), and the stand-ins."""
+    from typing import Dict, List, Optional, Union
+
+    sys.path.insert(0, os.path.join(OUT, "..", ".."))
+    from freegaussian_amd import bilagrid
+    from oracle.raster_oracle import rasterization
+
+    Cameras, OrientedBox, CamOpt, ssim64, psnr64, get_color = _nerfstudio_standins()
+    mpath = os.path.join(REF, "freegaussian", "freegaussian_model.py")
+    src = slice_methods(mpath, "FreeGaussianModel", MODEL_METHODS)
+    def rasterization_tap(*a, **k):
+        _LAST_RASTER["out"] = rasterization(*a, **k)
+        return _LAST_RASTER["out"]
+
+    ns = {"torch": torch, "Cameras": Cameras, "rasterization": rasterization_tap, "get_viewmat": U.get_viewmat,
+          "resize_image": U.resize_image, "from_homogenous": U.from_homogenous, "to_homogenous": U.to_homogenous,
+          "color_correct": bilagrid.color_correct, "total_variation_loss": bilagrid.total_variation_loss,
+          "get_color": get_color, "Dict": Dict, "List": List, "Union": Union, "Optional": Optional}  # fmt: skip
+    exec(compile(src, "<reference model slice>", "exec"), ns)
+    cpath = os.path.join(REF, "freegaussian", "freegaussian_control_model.py")
+    cns = dict(ns)
+    exec(compile(slice_methods(cpath, "FreeGaussianControlModel", ["get_outputs"]), "<reference control slice>", "exec"), cns)
+    bg_stmt = compile(_populate_background(mpath), "<reference background statement>", "exec")
+    mlp_ns = {"nn": torch.nn, "torch": torch, "F": torch.nn.functional, "get_embedder": U.get_embedder, "exp_se3": U.exp_se3}
+    exec(compile(slice_defs(mpath, ["FreeGaussianDeformableModel", "FreeGaussianControllableModel"]), "<reference MLP slice>",
+                 "exec"), mlp_ns)  # fmt: skip
+
+    class Ref(torch.nn.Module):
+        device = torch.device("cpu")
+
+        def __init__(self, cfg, params, step, training):
+            super().__init__()
+            self.config = types.SimpleNamespace(**cfg)
+            self.gauss_params = torch.nn.ParameterDict({k: torch.nn.Parameter(v.double().clone()) for k, v in params.items()})
+            self.deform = mlp_ns["FreeGaussianDeformableModel"](is_blender=True)
+            self.control = mlp_ns["FreeGaussianControllableModel"]()
+            mlp_weights(self.deform)
+            mlp_weights(self.control)
+            self.deform.double()
+            self.control.double()
+            self.camera_optimizer = CamOpt()
+            self.ssim, self.psnr = ssim64, psnr64
+            self.crop_box = None
+            self.step = step
+            if cfg.get("use_bilateral_grid"):
+                gx, gy, gw = cfg["grid_shape"]
+                self.bil_grids = bilagrid.BilateralGrid(num=BIL_NUM, grid_X=gx, grid_Y=gy, grid_W=gw).double()
+                with torch.no_grad():
+                    g = torch.Generator().manual_seed(5)
+                    self.bil_grids.grids.add_((torch.randn(self.bil_grids.grids.shape, generator=g) * 0.05).float().double())
+            exec(bg_stmt, ns, {"self": self})  # populate_modules: self.background_color
+            self.train(training)
+
+        num_points = property(lambda self: self.means.shape[0])
+
+        def _apply_bilateral_grid(self, rgb, cam_idx, H, W):
+            """nerfstudio's SplatfactoModel method (the reference inherits it): the build's statement of it."""
+            return bilagrid.apply_to_render(self.bil_grids, rgb, cam_idx, H, W)
+
+    for k in GAUSS:
+        setattr(Ref, k, property(lambda self, k=k: self.gauss_params[k]))
+    for name in MODEL_METHODS:
+        setattr(Ref, name, ns[name])
+
+    class RefControl(Ref):
+        pass
+
+    RefControl.get_outputs = cns["get_outputs"]
+    return Ref, RefControl, Cameras, OrientedBox
+
+
+def _deformed(U, deform, pts, t):
+    """The reference's deformed positions of pts at time t (freegaussian_model.py:833-843)."""
+    with torch.no_grad():
+        T, _, _ = deform(pts, torch.full((pts.shape[0], 1), float(t), dtype=pts.dtype))
+        return U.from_homogenous(torch.bmm(T, U.to_homogenous(pts).unsqueeze(-1)).squeeze(-1))
+
+
+_LAST_RASTER = {}
+CLAMP_EDGE = 1e-5  # a composite this close to the clamp at 1 may land on either side in fp32
+
+
+def _near_clamp(m):
+    """Covered pixels (alpha > 1e-3) whose composite (before the clamp, :875-876) of the last raster call lies within
+    CLAMP_EDGE of 1 without being exactly 1: the clamp's gradient is 1 on one side and 0 on the other, so an fp32 run
+    may legitimately take the other branch there, and the splats under the pixel then get a different gradient.  The
+    cases are chosen to have none.  (Uncovered pixels over a white background are exactly 1 in any precision.)"""
+    render, alpha, _ = _LAST_RASTER["out"]
+    v = render[..., :3] + (1 - alpha) * m._get_background_color()
+    near = ((v - 1).abs() < CLAMP_EDGE) & (v != 1) & (alpha > 1e-3)
+    return int(near.sum())
+
+
+RELU_EDGE = 2e-6  # relative to a layer's mean |pre-activation|: within fp32 GEMM rounding of the ReLU's kink
+
+
+def _near_relu(pre):
+    """Control-MLP pre-activations within RELU_EDGE of 0: the ReLU's derivative is 1 on one side and 0 on the other, an
+    fp32 GEMM summing in another order may take the other side, and the input gradient of that control point (its
+    share of the means gradient) then differs.  The cases are chosen to have none."""
+    return sum(int((z.abs() < RELU_EDGE * z.abs().mean()).sum()) for z in pre)
+
+
+class _NoCuda:
+    """``Tensor.cuda`` returns its input while the generator runs (the reference moves K to the GPU)."""
+
+    def __enter__(self):
+        self.saved = torch.Tensor.cuda
+        torch.Tensor.cuda = lambda self, *a, **k: self
+
+    def __exit__(self, *exc):
+        torch.Tensor.cuda = self.saved
+
+
+class _Fp64Float:
+    """``Tensor.float`` returns float64 while stage 2 runs: the reference takes ``mask.float() @ averages``
+    (freegaussian_control_model.py:140), which would otherwise mix float32 into the float64 case."""
+
+    def __enter__(self):
+        self.saved = torch.Tensor.float
+        torch.Tensor.float = lambda self, *a, **k: self.double()
+
+    def __exit__(self, *exc):
+        torch.Tensor.float = self.saved
+
+
+def _save(name, d):
+    np.savez_compressed(os.path.join(OUT, name), **{k: (t.detach().numpy() if torch.is_tensor(t) else np.asarray(t)) for k, t in d.items()})
+    print(name, len(d), os.path.getsize(os.path.join(OUT, name)), "bytes")
+
+
+def _outputs_and_grads(d, tag, m, out, extra_groups=()):
+    """Forward outputs (fp32 storage of the fp64 run) and the cotangent loss's gradients of one case."""
+    for k in ("rgb", "depth", "accumulation"):
+        if out.get(k) is not None:
+            d[f"{tag}.{k}"] = out[k].detach().to(torch.float32)
+    bg = out["background"].detach()
+    d[f"{tag}.background_shape"] = torch.tensor(bg.shape)
+    d[f"{tag}.background"] = bg.reshape(-1, 3).unique(dim=0).double()  # an expanded background: one colour
+    if not any(p.requires_grad for p in [out["rgb"]]):
+        return
+    cotangent_loss(out).backward()
+    for k in GAUSS:
+        gr = m.gauss_params[k].grad
+        d[f"{tag}.grad.{k}"] = (gr if gr is not None else torch.zeros_like(m.gauss_params[k])).to(torch.float32)
+    for label, mod in extra_groups:
+        heads, sk = mlp_grads(mod)
+        for n, v in heads.items():
+            d[f"{tag}.grad.{label}.{n}"] = v.to(torch.float32)
+        d[f"{tag}.grad.{label}.sketch"] = sk
+    if hasattr(m, "bil_grids"):
+        d[f"{tag}.grad.bil_grids"] = m.bil_grids.grids.grad.to(torch.float32)
+
+
+def gen_outputs(U):
+    """g_outputs.npz: stage-1 ``get_outputs`` (freegaussian_model.py:753-898) run in float64 -- parameters, MLP weights,
+    cameras, raster -- as a method of a stub ``self`` whose other methods (``_get_downscale_factor``,
+    ``_get_background_color``, ``get_empty_outputs``, ``_downscale_if_required``) are the reference's own, and whose
+    ``background_color`` is set by the reference's own statement of ``populate_modules``.  Injected stand-ins:
+    ``rasterization`` = oracle/raster_oracle.py (the gsplat-1.x restatement), ``Cameras`` / ``OrientedBox`` /
+    ``get_color`` / the camera optimizer in mode "off" (nerfstudio subsets, see ``_nerfstudio_standins``),
+    ``BilateralGrid`` / ``slice`` / ``total_variation_loss`` = freegaussian_amd/bilagrid.py and
+    ``_apply_bilateral_grid`` = its ``apply_to_render`` (nerfstudio's are absent: for the slice itself this checks
+    the build against itself; the fixture pins WHERE the reference applies it), ``Tensor.cuda`` = identity."""
+    Ref, _, Cameras, OrientedBox = reference_model_classes(U)
+    d = {}
+    with _NoCuda():
+        for ci, (tag, training, step, over, extra) in enumerate(OUTPUT_CASES):
+            cfg = {**OUTPUT_BASE, **over}
+            k_rest = num_sh_bases_(cfg["sh_degree"]) - 1
+            p = scene_params(OUTPUT_N, k_rest, seed=300 + ci + 1000 * OUTPUT_RESEED.get(tag, 0))
+            if cfg["num_downscales"]:
+                # fainter splats: at 1/4 resolution every pixel stacks dozens of them, and the fp32 backward, which
+                # rebuilds the transmittance by division (as gsplat's does), would lose digits where it nears zero
+                p["opacities"] -= 2.5
+            m = Ref(cfg, p, step, training)
+            c2w, intr, times = scene_camera()
+            cam = Cameras(c2w.double(), intr, IMG_W, IMG_H, times.double())
+            if extra in CROP_BOXES:
+                T, S = CROP_BOXES[extra]
+                m.crop_box = OrientedBox(torch.eye(3), torch.tensor(T), torch.tensor(S))
+            if extra == "bilagrid":
+                cam.metadata["cam_idx"] = BIL_CAM
+                d[f"{tag}.in.bil_grids"] = m.bil_grids.grids.detach().to(torch.float32)
+            if training:
+                # a training camera carries its own cameras0 (the dataparser's, freegaussian_dataparser.py:501): without
+                # one the reference aliases cameras0 to the camera and rescales that object twice (d^2, not d)
+                cam.metadata["cameras0"] = Cameras(c2w.double(), intr, IMG_W, IMG_H, torch.tensor([[0.0]], dtype=torch.float64))
+            if step >= cfg["warm_up"]:  # the deform net's response to the camera's time is material
+                moved = _deformed(U, m.deform, m.means.detach(), float(times)) - _deformed(U, m.deform, m.means.detach(), 0.0)
+                assert float(moved.abs().max()) > MIN_TIME_RESPONSE, tag
+            for k, v in p.items():
+                d[f"{tag}.in.{k}"] = v
+            d[f"{tag}.meta"] = torch.tensor([step, int(training), IMG_W, IMG_H])
+            try:
+                out = m.get_outputs(cam)
+            except (AssertionError, ValueError) as e:  # gsplat's shape check on post-activation colours
+                d[f"{tag}.raises"] = torch.tensor(1)
+                print(" ", tag, "raises:", e)
+                continue
+            if extra != "crop_empty":
+                assert _near_clamp(m) == 0, tag
+                d[f"{tag}.radii"] = m.radii.to(torch.int32)
+                d[f"{tag}.means2d"] = m.xys.detach()[0].to(torch.float32)
+                _outputs_and_grads(d, tag, m, out, [("deform", m.deform)])
+                if training:
+                    d[f"{tag}.absgrad"] = m.xys.absgrad[0].to(torch.float32)
+            else:
+                _outputs_and_grads(d, tag, m, out)
+            print(" ", tag, {k: tuple(v.shape) for k, v in out.items() if torch.is_tensor(v)})
+        # the documented deviation: a training camera WITHOUT a cameras0 of its own at d = 2 -- the reference aliases
+        # cameras0 to it and rescales that one object twice (only the rendered size is recorded)
+        m = Ref({**OUTPUT_BASE, "num_downscales": 1}, scene_params(OUTPUT_N, 3, seed=390), 100, True)
+        c2w, intr, times = scene_camera()
+        with torch.no_grad():
+            out = m.get_outputs(Cameras(c2w.double(), intr, IMG_W, IMG_H, times.double()))
+        d["alias.rgb_shape"] = torch.tensor(out["rgb"].shape)
+    d["camera.c2w"], d["camera.intr"], d["camera.times"] = scene_camera()
+    _save("g_outputs.npz", d)
+
+
+def num_sh_bases_(degree):
+    return (degree + 1) ** 2
+
+
+def gen_control(U):
+    """g_control.npz: stage-2 ``get_outputs`` (freegaussian_control_model.py:52-209) in float64 on the stub of
+    gen_outputs, with ``gaussian_mask``, ``init_camera`` and -- for the eval render without ``cameras0`` -- a
+    ``controller`` whose ``get_atrb_vals()`` returns seeded values (stored)."""
+    _, RefControl, Cameras, OrientedBox = reference_model_classes(U)
+    cfg = {**OUTPUT_BASE, "background_color": "black"}
+    d = {}
+    with _NoCuda():
+        for ci, (tag, training, cam0, layout, crop) in enumerate(CONTROL_CASES):
+            # the first draw with no control point on a ReLU kink and no pixel on the clamp (see _near_relu, _near_clamp)
+            for attempt in range(8):
+                p = scene_params(CONTROL_N, 3, seed=400 + ci + 1000 * attempt)
+                m = RefControl(cfg, p, 30000, training)
+                mask = control_mask(layout)
+                m.gaussian_mask = mask
+                c2w, intr, times = scene_camera(times=0.7)
+                m.init_camera = Cameras(c2w.double(), intr, IMG_W, IMG_H, torch.tensor([[0.0]], dtype=torch.float64))
+                vals = (torch.randn(CONTROL_M, 3, generator=torch.Generator().manual_seed(41 + ci)) * 0.05).double()
+                m.controller = types.SimpleNamespace(get_atrb_vals=lambda v=vals: v.clone())
+                cam = Cameras(c2w.double(), intr, IMG_W, IMG_H, times.double())
+                if cam0:
+                    cam.metadata["cameras0"] = m.init_camera
+                if crop is not None:
+                    m.crop_box = OrientedBox(torch.eye(3), torch.tensor(crop[0]), torch.tensor(crop[1]))
+                if cam0:  # every attribute's average displacement is material (the thing this fixture pins)
+                    pts = m.means.detach()
+                    if crop is not None:
+                        keep = m.crop_box.within(pts)
+                        pts, cm_ = pts[keep], mask[keep]
+                    else:
+                        cm_ = mask
+                    sel = cm_.any(-1)
+                    delta = _deformed(U, m.deform, pts[sel], float(times)) - _deformed(U, m.deform, pts[sel], 0.0)
+                    avg = torch.stack([delta[cm_[sel][:, i]].mean(0) for i in range(CONTROL_M)])
+                    assert float(avg.norm(dim=-1).min()) > MIN_TIME_RESPONSE, (tag, avg)
+                    d[f"{tag}.d_avg"] = avg
+                pre = []
+                hooks = [lin.register_forward_hook(lambda mod, i, o: pre.append(o.detach())) for lin in m.control.linear]
+                with _Fp64Float():
+                    out = m.get_outputs(cam)
+                for h in hooks:
+                    h.remove()
+                if _near_relu(pre) == 0 and _near_clamp(m) == 0:
+                    break
+            for k, v in p.items():
+                d[f"{tag}.in.{k}"] = v
+            d[f"{tag}.mask"], d[f"{tag}.atrb_vals"] = mask, vals.to(torch.float32)
+            d[f"{tag}.meta"] = torch.tensor([int(training), int(cam0), attempt])
+            assert _near_relu(pre) == 0 and _near_clamp(m) == 0, tag
+            d[f"{tag}.radii"] = m.radii.to(torch.int32)
+            _outputs_and_grads(d, tag, m, out, [("control", m.control)])
+            print(" ", tag, int(mask.any(-1).sum()), "control points, draw", attempt)
+    _save("g_control.npz", d)
+
+
+def gen_loss(U):
+    """g_loss.npz: ``get_loss_dict`` / ``get_metrics_dict`` / ``composite_with_background`` / ``get_gt_img``
+    (freegaussian_model.py:900-990) in float64 on the stub of gen_outputs.  Injected stand-ins: ``self.ssim`` = an fp64
+    SSIM written from pytorch_msssim's published algorithm, ``self.psnr`` = torchmetrics' PSNR with data_range 1,
+    ``total_variation_loss`` / ``BilateralGrid`` = freegaussian_amd/bilagrid.py, the camera optimizer in mode "off".
+    (The reference's resize_image works in float32: downscaled ground truths are float32 data, as there.)"""
+    Ref, _, _, _ = reference_model_classes(U)
+    d = {}
+    for ci, (tag, step, over, layout) in enumerate(LOSS_CASES):
+        cfg = {**OUTPUT_BASE, **LOSS_BASE, **over}
+        g = torch.Generator().manual_seed(500 + ci)
+        p = scene_params(LOSS_N, 3, seed=500 + ci)
+        p["scales"] = torch.randn(LOSS_N, 3, generator=g) * 0.8 - 3.0
+        m = Ref(cfg, p, step, True)
+        dfac = m._get_downscale_factor()
+        H, W = IMG_H, IMG_W
+        pred = (torch.rand(H, W, 3, generator=g) * 0.9 + 0.05).double().requires_grad_(True)
+        bg = torch.rand(3, generator=g)
+        if layout == "rgba":
+            image = torch.rand(H * dfac, W * dfac, 4, generator=g)
+        elif layout == "uint8":
+            image = (torch.rand(H * dfac, W * dfac, 3, generator=g) * 256).clamp_max(255).to(torch.uint8)
+        else:
+            image = torch.rand(H * dfac, W * dfac, 3, generator=g)
+        batch = {"image": image.double() if image.dtype != torch.uint8 else image}
+        if layout == "mask":
+            batch["mask"] = torch.rand(H * dfac, W * dfac, 1, generator=g) > 0.3
+            d[f"{tag}.in.mask"] = batch["mask"]
+        outputs = {"rgb": pred, "background": bg.double()}
+        loss = m.get_loss_dict(outputs, batch)
+        metrics = m.get_metrics_dict({"rgb": pred.detach(), "background": bg.double()}, batch)
+        loss["main_loss"].backward()
+        d[f"{tag}.in.pred"], d[f"{tag}.in.background"], d[f"{tag}.in.image"] = pred.detach().to(torch.float32), bg, image  # exact in fp32
+        d[f"{tag}.in.scales"] = p["scales"]
+        if hasattr(m, "bil_grids"):
+            d[f"{tag}.in.bil_grids"] = m.bil_grids.grids.detach().float()
+        d[f"{tag}.meta"] = torch.tensor([step, dfac])
+        for k, v in loss.items():
+            d[f"{tag}.loss.{k}"] = v.detach().double()
+        d[f"{tag}.psnr"], d[f"{tag}.gaussian_count"] = metrics["psnr"].detach(), torch.tensor(metrics["gaussian_count"])
+        d[f"{tag}.composited"] = m.composite_with_background(m.get_gt_img(batch["image"]), outputs["background"]).detach()
+        d[f"{tag}.grad_pred"] = pred.grad
+        print(" ", tag, {k: float(v.detach()) for k, v in loss.items()})
+    _save("g_loss.npz", d)
+
+
+def knn_frame_cameras():
+    """The key-frame cameras of g_knn.npz: scene_camera turned a little further each frame."""
+    out = []
+    for f in range(KNN_FRAMES):
+        c2w, intr, _ = scene_camera()
+        a = 0.08 * (f - 1)
+        R = torch.tensor([[np.cos(a), 0, np.sin(a)], [0, 1, 0], [-np.sin(a), 0, np.cos(a)]]).float()
+        c2w = torch.cat([R @ c2w[0, :, :3], (R @ c2w[0, :, 3:])], -1)[None]
+        out.append((c2w, intr))
+    return out
+
+
+def gen_knn(U):
+    """g_knn.npz: the key-frame body of preprocess/knn_gaussian.py (the statements after the render, :114-132),
+    sliced from its enclosing loop and run on each key frame's float64 packed "ED" render (oracle/raster_oracle.py in
+    place of gsplat) with seeded ``atrb_masks`` / ``mask_valids``.  Gaussians an fp32 kernel may legitimately flip --
+    ``means2d`` within KNN_EDGE_PX of an integer, or the depth ratio within KNN_EDGE_RATIO of a band edge -- are
+    listed per frame in ``edge``.  KNN_BORDER places a few centres per frame across the image border and off screen."""
+    sys.path.insert(0, os.path.join(OUT, "..", ".."))
+    from oracle.raster_oracle import rasterization
+
+    src = open(os.path.join(REF, "preprocess", "knn_gaussian.py")).read()
+    body = None
+    for node in ast.walk(ast.parse(src)):
+        if isinstance(node, ast.For) and any(isinstance(s, ast.Assign) and "rasterization" in ast.unparse(s.value) for s in node.body):
+            k = [i for i, s in enumerate(node.body) if isinstance(s, ast.Assign) and "rasterization" in ast.unparse(s.value)][0]
+            body = "\n".join(ast.unparse(s) for s in node.body[k + 1 :])
+    assert body is not None and "gaussian_masks" in body
+    code = compile(body, "<reference knn body>", "exec")
+    p = scene_params(KNN_N, 3, seed=600)
+    g = torch.Generator().manual_seed(601)
+    # some splats share a line of sight with others: depth bands with something in front
+    p["means"][: KNN_N // 4] = p["means"][KNN_N // 4 : KNN_N // 2] + torch.tensor([0.0, 0.0, 0.4])
+    # per frame, a few centres placed across the image border and off screen: the in-image filter, the .long()
+    # truncation of centres in (-1, 0) to pixel 0, and Gaussians culled by the raster (radii == 0)
+    for f, (c2w, intr) in enumerate(knn_frame_cameras()):
+        fx, fy, cx, cy = intr
+        c2v = torch.linalg.inv(U.get_viewmat(c2w.double())[0])
+        for j, (u, v) in enumerate(KNN_BORDER):
+            z = 2.6
+            pc = torch.tensor([(u - cx) * z / fx, (v - cy) * z / fy, z, 1.0], dtype=torch.float64)
+            i = KNN_N - len(KNN_BORDER) * (f + 1) + j
+            p["means"][i] = (c2v @ pc)[:3].float()
+            p["opacities"][i] = 3.0
+    means, quats = p["means"].double(), p["quats"].double()
+    scales, opac = torch.exp(p["scales"].double()), torch.sigmoid(p["opacities"].double()).squeeze(-1)
+    colors = torch.cat([p["features_dc"][:, None], p["features_rest"]], 1).double()
+    gaussian_masks = torch.zeros(KNN_N, KNN_M, dtype=torch.bool)
+    d = {f"in.{k}": v for k, v in p.items()}
+    for f, (c2w, intr) in enumerate(knn_frame_cameras()):
+        cam = types.SimpleNamespace(camera_to_worlds=c2w.double())
+        viewmat = U.get_viewmat(cam.camera_to_worlds)
+        K = torch.tensor([[[intr[0], 0, intr[2]], [0, intr[1], intr[3]], [0, 0, 1.0]]], dtype=torch.float64)
+        W, H = IMG_W, IMG_H
+        with torch.no_grad():
+            render, alpha, info = rasterization(means, quats, scales, opac, colors, viewmat, K, W, H, tile_size=16, packed=True,
+                                                near_plane=0.01, far_plane=1e10, render_mode="ED", sh_degree=1, absgrad=True)  # fmt: skip
+        atrb = torch.rand(H, W, KNN_M + 1, generator=g) > 0.55
+        valids = torch.ones(KNN_M + 1, dtype=torch.bool)
+        if f == 1:
+            valids[1] = False
+        data = {"atrb_masks": atrb, "mask_valids": valids}
+        before = gaussian_masks.clone()
+        exec(code, {"torch": torch}, {"info": info, "render": render, "W": W, "H": H, "i": f, "num_train_cameras": KNN_FRAMES,
+                                     "data": data, "M": KNN_M, "gaussian_masks": gaussian_masks})  # fmt: skip
+        # the edge list: the same filter's decisions, within rounding of an fp32 kernel's
+        xy = info["means2d"]
+        near_int = ((xy - xy.round()).abs() < KNN_EDGE_PX).any(-1)
+        xyl = xy.long()
+        im = ((xyl >= 0) & (xyl < torch.tensor([W, H]))).all(-1)
+        depth = render.squeeze()
+        px = depth[xyl[:, 1].clamp(0, H - 1), xyl[:, 0].clamp(0, W - 1)]
+        ratio = (px - info["depths"]) / px
+        near_band = ((ratio + 0.1).abs() < KNN_EDGE_RATIO) | ((ratio - 1.0).abs() < KNN_EDGE_RATIO)
+        edge = info["gaussian_ids"][(near_int | (im & near_band))]
+        d[f"f{f}.c2w"], d[f"f{f}.intr"] = c2w, torch.tensor(intr)
+        d[f"f{f}.atrb_masks"], d[f"f{f}.mask_valids"] = atrb, valids
+        d[f"f{f}.gaussian_ids"], d[f"f{f}.means2d"], d[f"f{f}.depths"] = info["gaussian_ids"], xy, info["depths"]
+        d[f"f{f}.depth_map"] = depth
+        d[f"f{f}.edge"] = edge
+        d[f"f{f}.gaussian_masks"] = gaussian_masks.clone()
+        vis = torch.zeros(KNN_N, dtype=torch.bool)
+        vis[info["gaussian_ids"]] = True
+        outside = info["gaussian_ids"][~im]
+        truncated = info["gaussian_ids"][im & ((xy < 0) & (xy > -1)).any(-1)]
+        assert outside.numel() > 0 and truncated.numel() > 0 and int((~vis).sum()) > 0, f
+        print("   visible outside", outside.numel(), "truncated into pixel 0", truncated.numel(), "culled", int((~vis).sum()))
+        print(" ", f, "visible", info["gaussian_ids"].numel(), "new labels", int((gaussian_masks & ~before).sum()), "edge", edge.numel())
+    d["gaussian_masks"] = gaussian_masks
+    _save("g_knn.npz", d)
+
+
 if __name__ == "__main__":
     U = load_utils()
-    gen_utils(U)
-    gen_mlp(U)
-    gen_flow()
-    gen_flow_bp()
-    gen_densify()
-    gen_flow_query(U)
+    which = set(sys.argv[1:])
+    gens = [("utils", lambda: gen_utils(U)), ("mlp", lambda: gen_mlp(U)), ("flow", gen_flow), ("flow_bp", gen_flow_bp),
+            ("densify", gen_densify), ("flow_query", lambda: gen_flow_query(U)), ("outputs", lambda: gen_outputs(U)),
+            ("control", lambda: gen_control(U)), ("loss", lambda: gen_loss(U)), ("knn", lambda: gen_knn(U))]  # fmt: skip
+    for name, fn in gens:
+        if not which or name in which:
+            fn()

@@ -1310,7 +1310,8 @@ def _model_and_camera(n=4000, W=160, H=96, step=4000, training=True, log_scale=-
 
 
 def _oracle_outputs(ref, cam, render_mode):
-    """The same host math on CPU tensors, with the CPU oracle in place of the HIP raster."""
+    """The same host math on CPU tensors, with the CPU oracle in place of the HIP raster.  A secondary check: the
+    primary one is tests/test_reference_goldens.py, against fixtures made by running the reference's own methods."""
     from freegaussian_amd.utils import from_homogenous, get_viewmat, to_homogenous
 
     viewmat = get_viewmat(cam.camera_to_worlds)

@@ -301,7 +301,8 @@ def test_loss_dict_mirrors_the_reference_expressions():
     """get_loss_dict / composite_with_background / get_metrics_dict (freegaussian_model.py:911-990): RGBA ground
     truth over the step's background, the mask blacking out both images, main loss from L1 and SSIM with
     ssim_lambda, the scale-ratio regulariser 0.1 mean(max(ratio, max_gauss_ratio) - max_gauss_ratio) on every
-    10th step only -- spelled out again here from the reference's lines."""
+    10th step only -- spelled out again here from the reference's lines.  A secondary check: the primary one is
+    tests/test_reference_goldens.py, against fixtures made by running the reference's own methods."""
     from freegaussian_amd.harness import ssim
 
     g = torch.Generator().manual_seed(5)
