@@ -68,6 +68,8 @@ static_assert(SB_LONG_SPLIT <= SB_LONG_MIN && SB_LONG_SPLIT >= 2 * 1536, "long s
 constexpr int LG_T = 1536;                           // target bucket size: half of the small LDS sort's capacity (sb_long_sort_kernel)
 constexpr int LG_KMAX = 1008;                        // buckets per segment at most (splitters + counters in LDS)
 constexpr int LG_SA = 32;                            // samples per bucket (fewer when LG_SA * k exceeds one LDS sort): a bucket twice its target is a 1e-6 event
+// ... for k <= 96 (segments up to ~147 000 elements).  The sample holds 3072 elements at most: at the cap, k = LG_KMAX, a bucket
+// has ~3 samples, buckets beyond their slabs are common and one beyond 7936 elements is near certain from ~2.5M elements on
 constexpr int LG_BLOCK = 512, LG_PER = 8, LG_CHUNK = LG_BLOCK * LG_PER;  // count / scatter passes over a long segment
 constexpr int LG_GRID = 1024, LG_SORT_GRID = 1024;   // persistent workgroups of those passes / of the bucket sort
 constexpr int SB_LONG_OVER_GRID = 64;                // workgroups of sb_long_overflow_kernel
@@ -1517,7 +1519,8 @@ sb_sort_small_kernel(int tile_w, int tile_h, const int32_t* __restrict__ tile_of
 
 // The buckets of the long segments (slot = work item) and the skewed segments the small launch left: LG_SORT_GRID
 // persistent workgroups, the small launch's LDS sort with the splitter path for skew.  A bucket whose cursor ran beyond its
-// slab (the sample was unlucky by a factor of two: with 32 samples per bucket a 1e-6 event per bucket) goes on over_list's
+// slab (the sample was unlucky by a factor of two: with 32 samples per bucket -- k <= 96, segments up to ~147 000 elements --
+// a 1e-6 event per bucket; at the 1008-bucket cap, ~3 samples per bucket, a few per cent of the buckets) goes on over_list's
 // second list for sb_long_overflow_kernel.
 // (eight wavefronts per SIMD = four workgroups per CU, as the small launch: 9 spilled registers on the skew path)
 __global__ void __launch_bounds__(64 * SB_SMALL_WAVES) __attribute__((amdgpu_waves_per_eu(8, 8)))
@@ -1584,8 +1587,10 @@ sb_long_sort_kernel(int tile_w, int tile_h, long long capacity, const int32_t* _
   }
 }
 
-// The buckets that outgrew their slabs (over_list's second list; normally none: 5 us of an empty grid -- a bucket of twice its
-// target size is a 1e-4 ... 1e-6 event, seen about once in a hundred calls on a scene with a hundred buckets), one workgroup each.
+// The buckets that outgrew their slabs (over_list's second list; on segments up to ~147 000 elements -- 32 samples per bucket
+// -- normally none: 5 us of an empty grid -- a bucket of twice its target size is a 1e-4 ... 1e-6 event, seen about once in a
+// hundred calls on a scene with a hundred buckets; on segments at the 1008-bucket cap, from 1 548 288 elements, a few per cent
+// of the buckets, and from ~2.5M elements a bucket beyond 7936 -- the whole segment below -- is the rule), one workgroup each.
 // The scatter pass dropped what did not fit the slab but left `entries` intact: the bucket's elements are gathered from its
 // segment again -- those between the bucket's two splitters -- into the workgroup's own stretch of a small arena (64 x 7936
 // elements of the workspace), then sorted and emitted like any bucket, by the large launch's LDS sort (7936 elements).  A bucket beyond even that -- the sample missed it by a factor of five -- sends its
@@ -1629,7 +1634,12 @@ sb_long_overflow_kernel(int tile_w, int tile_h, long long capacity, const int32_
       if (threadIdx.x == 0) s_mine = atomicCAS(lt.cnt + bi.x, 0u, 0xFFFFFFFFu) == 0u ? 1 : 0;
       __syncthreads();
       if (s_mine) {
-        const uint64_t* fin = sort_segment_global<SB_LARGE_WAVES>(entries + off, scratch + (size_t)bi.x * SB_LONG_SLAB, n_seg, wave_cnt,
+        // The temp is the segment's OWN element range of `scratch` ([off, off + n_seg), as the large launch's global
+        // path): disjoint between segments and inside `scratch` (capacity >= off + n_seg).  Not its buckets' slabs: those
+        // hold k x SB_LONG_SLAB elements, fewer than n_seg from 1008 x 3072 elements on (LG_KMAX), and two segments
+        // sorted whole by two workgroups would then share memory.  No one reads a slab during this launch (outgrown
+        // buckets gather into lt.arena).
+        const uint64_t* fin = sort_segment_global<SB_LARGE_WAVES>(entries + off, scratch + off, n_seg, wave_cnt,
                                                                    sh.scan_tmp, sh.red);
         emit_tiles<SB_LARGE_WAVES>(fin, n_seg, tile_base, flatten_ids, sh.tcnt);
       }

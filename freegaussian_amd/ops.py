@@ -993,9 +993,8 @@ def _note_counts(rctx, lkey, key, count_slot, need_reported: bool = False, N: in
     longest tile list) and update what the next calls of the shape go by: the list capacity, the long-segment flag of the
     binning, the heavy-tile policy of the raster.  -> the list length."""
     n_isects = _poll_count(count_slot)
-    if masked is not None:  # (the rectangles' area: stored by the same workgroup launch as the longest segment, word 1)
-        _poll_count(count_slot, 1)
-        rctx.note_mask_ratio(lkey, bool(masked), n_isects, int(_count_ring_np[_RING_WORDS * count_slot + 14]))
+    if masked is not None:  # (the rectangles' area: a store of its own, which may land after words 0-3: waited for)
+        rctx.note_mask_ratio(lkey, bool(masked), n_isects, _poll_count(count_slot, 14))
     _note_ckpt_need(rctx, lkey, count_slot, need_reported, N, walks)  # (first: the previous call's walk report decides below)
     rctx.longest_segment_seen = _poll_count(count_slot, 1)
     for word, limit, shapes, cooldown in ((1, rctx.long_segment, rctx.long_shapes, rctx.long_cooldown),

@@ -45,6 +45,7 @@ typedef void* fg_stream_t;
 #define FG_SPLAT_FLOATS 16   /* one 64-byte record per Gaussian, see fg_pack_splats */
 #define FG_SH_JAC_FLOATS 10  /* per-Gaussian note of the SH colour for the backward, see fg_preprocess_fwd */
 #define FG_ABI_VERSION 9
+#define FG_COUNT_OUT_WORDS 16 /* int64 words of a count_out block (fg_stbin_count, fg_step_io): ABI 9 */
 
 int fg_abi_version(void);
 const char* fg_error_string(int code);
@@ -151,10 +152,10 @@ int fg_bin_prepare_keys(int N, uint32_t* depth_keys, const int32_t* tile_rects, 
  * elements than (Gaussian, tile) pairs on the 1M / 1080p scene (csrc/stbin.hip).
  * tile_rects / depth_keys: the optional outputs of fg_preprocess_fwd.  fg_stbin_count writes
  * tile_offsets[T + 1] (exact, independent of any capacity) and, if count_out is not NULL, FIVE words of a block of
- * SIXTEEN int64 (ABI 9; a block of four before) with system scope (pinned host memory): count_out[0] the list length,
- * count_out[2] the longest tile list (a host turns fg_raster_config::heavy_tiles on from it), count_out[1] the longest
- * supertile segment, count_out[3] the number of segments of more than 3072 elements, and count_out[14] the summed AREA of
- * the footprint rectangles in tiles -- what the list length would be without tile_masks: a host keeps the masks for an
+ * FG_COUNT_OUT_WORDS = SIXTEEN int64 (ABI 9; a block of four before) with system scope (pinned host memory):
+ * count_out[0] the list length, count_out[2] the longest tile list (a host turns fg_raster_config::heavy_tiles on
+ * from it), count_out[1] the longest supertile segment, count_out[3] the number of segments of more than 3072
+ * elements, and count_out[14] the summed AREA of the footprint rectangles in tiles -- what the list length would be without tile_masks: a host keeps the masks for an
  * image size only while list length / area says they drop enough (ops.RasterContext.masks_on: below 0.8).  (Words 4..13
  * and 15 belong to fg_stbin_fill_jobs' ckpt_need_out and fg_raster_jobs_fwd's walk_out when the host hands them the same
  * block, as ops.py does.)
@@ -193,7 +194,10 @@ size_t fg_stbin_fill_workspace_bytes(int64_t capacity);
 /* (ABI 9, with FG_STBIN_LONG_SEGMENTS; a TEST hook: a bucket of the sample sort counts as having outgrown its slab from 1600
  * elements instead of 3072 -- it is gathered again from its segment and sorted by a larger LDS sort -- and, in even
  * supertiles, a segment with a bucket beyond 1728 elements instead of 7936 goes through global memory whole, so that both
- * paths behind an outgrown slab -- a 1e-6 event per bucket otherwise -- run in tests; same lists) */
+ * paths behind an outgrown slab run in tests on segments of any size; same lists.  Without the hook they are rare only on
+ * segments of up to ~147 000 elements -- 96 buckets, 32 samples each: a 1e-6 event per bucket --; the sample has 3072
+ * elements at most, so longer segments have fewer samples per bucket, down to ~3 at the 1008-bucket cap (1 548 288
+ * elements), where outgrown slabs are common and from ~2.5M elements a segment sorted whole is the normal route) */
 #define FG_STBIN_TEST_SMALL_SLABS 4
 int fg_stbin_fill(int N, const uint32_t* depth_keys, const int32_t* tile_rects, const uint64_t* tile_masks, int tile_w,
                   int tile_h, int64_t capacity, const int32_t* tile_offsets, const void* count_workspace,
@@ -594,7 +598,8 @@ int fg_payload_expand(int N, int payload_floats, int n_views, const float* compa
  * and its autograd backward.
  *   fg_step_desc    what is rendered (sizes, SH degree, channels, composite epilogue, list capacity, flags)
  *   fg_step_io      device pointers: the inputs (plain or raw parameter forms, as the two preprocess entry points take
- *                   them), count_out (pinned host memory, the four words of fg_stbin_count), and for the backward the
+ *                   them), count_out (pinned host memory: a block of FG_COUNT_OUT_WORDS int64, the five words of
+ *                   fg_stbin_count among them, see there; a smaller block is written past), and for the backward the
  *                   upstream gradients and the output gradients
  *   fg_step_layout  from fg_step_layout_query: offsets / sizes of every buffer inside the two caller-allocated
  *                   workspaces -- `keep` (read by the backward and by the caller: FG_STEP_RADII .. FG_STEP_CLAMP_MASK;
@@ -626,7 +631,7 @@ typedef struct fg_step_desc {
 typedef struct fg_step_io {
   const float *means, *quats, *d_quats, *scales, *d_scales, *opacities, *colors, *features_rest, *extra, *viewmat, *K,
       *background;        /* raw = 1: scales = log-scales, opacities = logits, colors = features_dc */
-  int64_t* count_out;     /* nullable */
+  int64_t* count_out;     /* nullable; FG_COUNT_OUT_WORDS int64 */
   /* backward only */
   const float *v_render, *v_alphas, *v_depths, *v_conics;  /* upstream gradients; all but v_render nullable */
   float *v_means, *v_quats, *v_d_quats, *v_scales, *v_d_scales, *v_opacities, *v_colors, *v_features_rest, *v_extra;

@@ -339,6 +339,56 @@ def test_heavy_tiles_follow_the_walks_the_forward_reports_host_logic(monkeypatch
     assert not call(101, 2000) and call(102, 12_000)
 
 
+def test_count_out_block_size_in_the_header_is_the_ring_slot_host_logic():
+    """include/fgraster.h FG_COUNT_OUT_WORDS (the count_out block fg_stbin_count and fg_step_fwd write into, ABI 9) is the
+    size of a slot of ops' pinned ring: a C caller who sizes the block by the header gets every word the GPU stores."""
+    from freegaussian_amd import ops
+
+    text = open(os.path.join(ROOT, "include", "fgraster.h")).read()
+    m = re.search(r"^#define FG_COUNT_OUT_WORDS (\d+)", text, flags=re.M)
+    assert m, "FG_COUNT_OUT_WORDS missing from fgraster.h"
+    assert int(m.group(1)) == ops._RING_WORDS == 16
+
+
+def test_mask_ratio_waits_for_the_area_word_host_logic(monkeypatch):
+    """ops._note_counts: fg_stbin_count's area (word 14 of the call's ring slot) is a store of its own that may land after
+    words 0-3.  A masked call must wait for it and record list length / area for the shape -- read early it is still -1,
+    which would book the call as an unmasked one.  Pure host logic: a numpy ring, a thread stores the area late."""
+    import threading
+    import time
+
+    import numpy as np
+
+    from freegaussian_amd import ops
+
+    ring = np.zeros(ops._RING_WORDS * ops._COUNT_RING, dtype=np.int64)
+    monkeypatch.setattr(ops, "_count_ring_np", ring)
+    ctx = ops.RasterContext(env={})
+    lkey, key = ("dev", 120, 68), ("dev", 120, 68, "fg_stbin")
+    slot = 3
+    base = ops._RING_WORDS * slot
+    ring[base : base + 16] = -1
+    ring[base : base + 4] = (3_000_000, 1000, 2000, 0)  # list length, longest segment, longest tile list, segments > 3072
+    ring[base + 13] = 0
+
+    def late_area():
+        time.sleep(0.004)
+        ring[base + 14] = 4_000_000
+
+    writer = threading.Thread(target=late_area)
+
+    class _Stream:  # (what _poll_count drains after 20 ms without the word: here the writer)
+        def synchronize(self):
+            writer.join()
+
+    monkeypatch.setattr(ops, "_count_ring_stream", [_Stream()] * ops._COUNT_RING)
+    ops._count_ring_gen[slot] += 1
+    writer.start()
+    assert ops._note_counts(ctx, lkey, key, slot, N=1_000_000, masked=True) == 3_000_000
+    writer.join()
+    assert ctx.mask_keep[lkey] == [[0.75], 0]  # the ratio, not a call without masks
+
+
 def test_workspace_pool_hands_out_only_buffers_nobody_refers_to_host_logic():
     """ops.RasterContext.workspace: the one-call path's `keep` / `tmp` buffers from a pool of the context's own.  A buffer is
     handed out again only when every view of its storage is gone (outputs, info tensors and saved tensors are views of

@@ -560,6 +560,90 @@ def test_supertile_binning_equals_depth_first_binning(case, monkeypatch):
     assert torch.equal(o.cpu().long(), torch.searchsorted(tile[order].contiguous(), torch.arange(tw * th + 1)))
 
 
+# Segments at the sample sort's bucket cap (csrc/stbin.hip: LG_KMAX = 1008 buckets of LG_T = 1536 elements, slabs of 3072):
+# from 1 548 288 elements the buckets grow past their target, from 3 096 576 a segment outgrows its buckets' slabs, and with
+# ~3 samples per bucket some bucket beyond 7936 elements -- the whole segment through global memory in
+# sb_long_overflow_kernel -- is the normal route from ~2.5M elements on.  (sx, sy, elements) per long segment; supertile
+# index = sy x 20 + sx on the 640 x 400 image, so the parity of sx is the supertile's (FG_STBIN_TEST_SMALL_SLABS treats even
+# and odd supertiles differently).
+_CAP_SHAPES = {
+    "k_saturation": [(2, 2, 1_548_288), (5, 3, 1_548_289)],  # k = 1008 exactly / the first segment beyond it
+    "slab_region_edge": [(4, 2, 3_096_576), (7, 4, 3_096_577)],  # its buckets' slabs exactly / one element beyond them
+    "adjacent_whole_sorts": [(8, 3, 4_000_000), (9, 3, 4_100_000)],  # consecutive bucket slot ranges, both sorted whole
+    "nine_million": [(10, 6, 9_000_000)],  # every bucket beyond 7936 elements on average
+    "even_odd_ties": [(2, 1, 1_600_000), (7, 5, 1_600_000)],  # 3000 exact depth ties inside the first
+}
+
+
+def _cap_scene(segments, ties=0, seed=0):
+    """Rectangles and depth keys for `segments`: every Gaussian of a long segment covers its supertile's 2 x 2 tiles (one
+    element, an entry in each of the four tile lists), and 20 000 ordinary Gaussians of one tile each lie in the
+    supertiles BEHIND the last long one (rows 10-12), so that no long segment is the image's last.  Depth keys: random
+    float bits of [1, 64), uniform in key space (short runs of equal keys: sort_segment_global's run fix is quadratic in
+    a run); `ties` of the first segment share one key.  -> (N, rects, keys, [(first id, elements, supertile)])."""
+    g = torch.Generator().manual_seed(seed)
+    n_ord = 20_000
+    N = sum(n for _, _, n in segments) + n_ord
+    x0, y0 = torch.empty(N, dtype=torch.int64), torch.empty(N, dtype=torch.int64)
+    w, h = torch.full((N,), 2, dtype=torch.int64), torch.full((N,), 2, dtype=torch.int64)
+    segs, i = [], 0
+    for sx, sy, n in segments:
+        x0[i : i + n], y0[i : i + n] = 2 * sx, 2 * sy
+        segs.append((i, n, sy * 20 + sx))
+        i += n
+    x0[i:] = torch.randint(0, 40, (n_ord,), generator=g)
+    y0[i:] = torch.randint(20, 25, (n_ord,), generator=g)
+    w[i:], h[i:] = 1, 1
+    keys = torch.randint(0x3F800000, 0x42800000, (N,), generator=g, dtype=torch.int64).to(torch.int32)
+    if ties:
+        first, n, _ = segs[0]
+        keys[first + n // 3 : first + n // 3 + ties] = 0x40400000  # 3.0
+    return N, _pack_rects(x0, y0, w, h).to(DEV), keys, segs
+
+
+def _assert_long_lists_follow_the_rule(f, o, keys, segs):
+    """Each of a long segment's four tile lists is the segment's ids ordered by (depth bits, id) -- one argsort on the CPU."""
+    f, o = f.cpu(), o.cpu()
+    for first, n, st in segs:
+        ids = torch.arange(first, first + n, dtype=torch.int64)
+        want = ids[torch.argsort((keys[first : first + n].long() << 32) | ids)].to(torch.int32)
+        sx, sy = st % 20, st // 20
+        for t in (2 * sy * 40 + 2 * sx, 2 * sy * 40 + 2 * sx + 1, (2 * sy + 1) * 40 + 2 * sx, (2 * sy + 1) * 40 + 2 * sx + 1):
+            assert int(o[t + 1]) - int(o[t]) == n, (st, t)
+            assert torch.equal(f[int(o[t]) : int(o[t + 1])], want), (st, t)
+
+
+@pytest.mark.parametrize("shape", list(_CAP_SHAPES))
+def test_supertile_binning_at_the_bucket_cap(shape, monkeypatch):
+    """Supertile segments of 1.5M to 9M elements -- the sample sort at its 1008-bucket cap, buckets beyond their slabs, whole
+    segments through global memory in sb_long_overflow_kernel, two of them at once in adjacent bucket slot ranges (which
+    shared temp memory while the whole sort's temp was the buckets' slabs) -- through the four modes of
+    _supertile_vs_depth_first (depth-first; one workgroup per long segment; the sample sort; the sample sort with the
+    test's small slabs): `torch.equal` lists and ranges, and every long segment's tile lists against the rule.  Then a
+    fresh context's own sequence: an exact call (flagged: the count came first), a speculative call without the flag,
+    and one with the flag the unflagged call's count set again."""
+    N, rects, keys, segs = _cap_scene(_CAP_SHAPES[shape], ties=3000 if shape == "even_odd_ties" else 0)
+    W, H = 640, 400
+    f, o = _supertile_vs_depth_first(N, W, H, rects, keys.to(DEV), monkeypatch)
+    assert int(o[-1]) == f.numel() == 4 * sum(n for _, n, _ in segs) + 20_000
+    _assert_long_lists_follow_the_rule(f, o, keys, segs)
+    z = torch.zeros(N, device=DEV)
+    args = (torch.zeros(N, 2, device=DEV), z.int(), z, z.int(), 16, 40, 25)
+    ctx = ops.RasterContext()
+    ctx.binning, ctx.long_segments, ctx.direct_count = "supertile", "auto", True
+    with ops.use(ctx):
+        runs = [ops.bin_tiles(*args, keys_rects=(keys.to(DEV), rects), want_keys=False)]
+        assert ctx.long_calls == 1
+        ctx.long_shapes.clear()
+        runs.append(ops.bin_tiles(*args, keys_rects=(keys.to(DEV), rects), want_keys=False))
+        assert ctx.long_calls == 1 and ctx.long_shapes
+        runs.append(ops.bin_tiles(*args, keys_rects=(keys.to(DEV), rects), want_keys=False))
+        assert ctx.long_calls == 2
+    for _, fi, oi in runs:
+        assert torch.equal(fi, f) and torch.equal(oi, o)
+    ctx.release_workspaces()
+
+
 def test_long_segments_switch_the_sample_sort_on_for_a_while():
     """fg_stbin_count reports the longest supertile segment beside the list length; a shape that showed one beyond
     the LDS sorts' capacity (a dense cluster) gets FG_STBIN_LONG_SEGMENTS for its next `long_cooldown` calls, renewed
@@ -1866,6 +1950,79 @@ def test_clustered_1m_scene_lists_equal_the_oracles_through_the_long_segment_sor
             assert torch.equal(ids.cpu(), vals_s), k
     lens = torch.diff(offs_ref)
     assert int(lens.max()) > 100_000 and ctx.long_calls == 3
+
+
+def test_far_cluster_of_millions_renders_as_with_depth_first_binning():
+    """8M Gaussians in a cube of half-width 0.06 four units from the camera at 1920 x 1080: a handful of supertiles with
+    around two million elements each through rasterization() forward and backward, three times in the default context --
+    the shape's first call (stage-wise: it measures the list, and fills with FG_STBIN_LONG_SEGMENTS once the count has
+    come), then two on the one-call step path, without the flag (one workgroup sorts a segment through global memory) and
+    with it (the sample sort at its 1008-bucket cap, buckets beyond their slabs, segments sorted whole in
+    sb_long_overflow_kernel) -- and once with the depth-first binning (heavy tiles off throughout): equal lists, image and
+    alpha bit for bit, gradients up to the order of the backward's atomics; and a tile-aligned crop in the cluster against
+    the C oracle."""
+    from oracle import c_oracle as CO
+
+    sc = synthetic_scene(8_000_000, 1920, 1080, n_views=1, sh_degree=3, seed=13, log_scale_mean=math.log(0.004))
+    sc.means *= 0.03
+    W, H = sc.width, sc.height
+    vm, K = sc.viewmats[:1].to(DEV), sc.Ks[:1].to(DEV)
+    v = torch.randn(1, H, W, 3, generator=torch.Generator().manual_seed(0)).to(DEV)
+    outs = []
+    ctx = ops.RasterContext()
+    for binning in ("supertile", "supertile", "supertile", "depthfirst"):
+        if binning == "depthfirst":  # (stage-wise calls: the step path takes the supertile binning only)
+            ctx.release_workspaces()
+            ctx = ops.RasterContext()
+            ctx.binning = "depthfirst"
+        # (heavy tiles -- on from the second call for lists this long -- walk a long list in shares and fold them: an image
+        # within rounding, not bit for bit; what is compared here is the binning)
+        ctx.heavy_tiles = "never"
+        t = [x.to(DEV).requires_grad_(True) for x in (sc.means, sc.quats, sc.scales, sc.opacities, sc.colors)]
+        with ops.use(ctx):
+            r, a, info = rasterization(*t, vm, K, W, H, sh_degree=3, packed=False)
+            (r * v).sum().backward()
+        # (copies: the outputs are views of workspaces the context may hand out again)
+        keep = {k: info[k].detach().clone() for k in ("flatten_ids", "isect_offsets", "means2d", "conics")}
+        outs.append((r.detach().clone(), a.detach().clone(), [x.grad for x in t], keep))
+        del r, a, t
+        if len(outs) == 1:
+            assert ctx.stagewise_raster_calls == 1 and ctx.long_calls == 1
+            ctx.long_shapes.clear()  # (the next call: the step path without the flag)
+        elif len(outs) == 2:
+            assert ctx.step_calls and ctx.stagewise_raster_calls == 1 and ctx.long_calls == 1
+        elif len(outs) == 3:
+            assert ctx.stagewise_raster_calls == 1 and ctx.long_calls == 2
+            lens = torch.diff(info["isect_offsets"].reshape(-1).long())
+            assert int(lens.max()) > 1_548_288  # (a supertile's segment holds at least each of its tiles' lists)
+            # (measured on MI355X: a list of 25.6M entries, the longest tile list 4.08M; the compositing checkpoints of the
+            # backward's list shares take 446M floats = 1.7 GiB, inside the default FG_SEG_CKPT_BUDGET_MB of 2048: the
+            # step keeps them and the backward walks the long lists in shares)
+    ctx.release_workspaces()
+    r0, a0, g0, i0 = outs[0]
+    for r, a, g, i in outs[1:]:
+        assert torch.equal(i["flatten_ids"], i0["flatten_ids"]) and torch.equal(i["isect_offsets"], i0["isect_offsets"])
+        assert torch.equal(r, r0) and torch.equal(a, a0)
+        for x, y in zip(g, g0):
+            assert rel_l2(x, y) < 1e-5
+    # crop of two tiles at the cluster's centre against the scalar C oracle on the GPU's projection and lists
+    x0, y0, cw, ch = 944, 528, 32, 16
+    tw = (W + 15) // 16
+    offs_c, ids_c = i0["isect_offsets"].reshape(-1).cpu(), i0["flatten_ids"].cpu()
+    lists, coffs = [], [0]
+    for ty in range(ch // 16):
+        for tx in range(cw // 16):
+            tt = (y0 // 16 + ty) * tw + (x0 // 16 + tx)
+            lists.append(ids_c[int(offs_c[tt]) : int(offs_c[tt + 1])])
+            coffs.append(coffs[-1] + lists[-1].numel())
+    assert min(len(l) for l in lists) > 1_000_000
+    cv, coffs = torch.cat(lists), torch.tensor(coffs, dtype=torch.int32)
+    m2 = i0["means2d"][0].detach().cpu() - torch.tensor([float(x0), float(y0)])
+    campos = torch.linalg.inv(sc.viewmats[0])[:3, 3]
+    rgb = torch.clamp_min(O.sh_eval(3, sc.means - campos, sc.colors) + 0.5, 0.0)
+    rc, ac, _ = CO.raster_fwd(m2, i0["conics"][0].cpu(), rgb, sc.opacities, cw, ch, 16, coffs, cv)
+    assert close_except_knife_edge(r0[0, y0 : y0 + ch, x0 : x0 + cw], rc, REL_TOL)
+    assert close_except_knife_edge(a0[0, y0 : y0 + ch, x0 : x0 + cw], ac, REL_TOL)
 
 
 @pytest.mark.parametrize("form", ["wide", "three"])
