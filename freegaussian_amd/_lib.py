@@ -100,12 +100,15 @@ SIGNATURES = {
     "fg_reprojection_flow": (c_int, [c_int, c_int, P, P, P, P, c_float, P, P]),
     "fg_flow_fwd": (c_int, [c_int, P, P, P, P, P, P, P, P, P, P]),
     "fg_flow_bwd": (c_int, [c_int, P, P, P, P, P, P, P, P, P, P, P, P, P]),
+    "fg_knn_workspace_bytes": (c_size_t, [c_int64]),
+    "fg_knn": (c_int, [c_int64, P, c_int, P, P, P, c_size_t, P]),
 }  # fmt: skip
 
 # test hooks, not declared in the public header
-_EXTRA = {"fg_debug_wave_reduce16": (c_int, [P, P, P])}
+_EXTRA = {"fg_debug_wave_reduce16": (c_int, [P, P, P]), "fg_debug_knn_grid": (c_int, [c_int64, P, c_int, P, P])}
 
-ABI_VERSION = 9
+ABI_VERSION = 10
+KNN_MAX_K = 8  # FG_KNN_MAX_K
 STBIN_LONG_SEGMENTS = 1  # FG_STBIN_LONG_SEGMENTS
 STBIN_TEST_SMALL_SLABS = 4  # FG_STBIN_TEST_SMALL_SLABS (tests: the sample sort's overflow path)
 STEP_NO_FOOTPRINT_MASKS = 2  # FG_STEP_NO_FOOTPRINT_MASKS

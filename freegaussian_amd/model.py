@@ -140,17 +140,24 @@ class FreeGaussianModel(nn.Module):
 
     def __init__(self, config: Optional[FreeGaussianModelConfig] = None, num_points: Optional[int] = None,
                  seed_points: Optional[torch.Tensor] = None, is_blender: bool = True,
-                 init_scales: Optional[float] = None, num_train_data: Optional[int] = None):  # fmt: skip
+                 init_scales: Optional[float] = None, num_train_data: Optional[int] = None,
+                 device: Optional[Union[str, torch.device]] = None):  # fmt: skip
         """``num_train_data``: the number of training images (one bilateral grid each, :227-233).  ``init_scales``: None = the reference's initial scales, the mean distance to the three nearest neighbours
-        (:158-162; a tree query over all points: a minute at 1M); a float = that log-scale everywhere, for harnesses that
-        overwrite the scales anyway."""
+        (:158-162; on the GPU ``ops.knn``; on the CPU a tree query over all points with scikit-learn,
+        quadratic brute force without); a float = that log-scale everywhere, for harnesses
+        that overwrite the scales anyway.  ``device``: where every parameter is created and where the neighbour search
+        runs; the random draws still come from the CPU generator in the same order, so a seed gives the same model on
+        either device.  None = as before, the CPU -- or, for CUDA ``seed_points``, their device."""
         super().__init__()
         self.config = config or FreeGaussianModelConfig()
+        if device is None and seed_points is not None and seed_points.is_cuda:
+            device = seed_points.device
+        on = (lambda t: t) if device is None else (lambda t: t.to(device))
         if seed_points is not None:
-            means = seed_points.float()
+            means = on(seed_points.float())
         else:
             n = num_points or self.config.num_random
-            means = (torch.rand(n, 3) - 0.5) * self.config.random_scale
+            means = on((torch.rand(n, 3) - 0.5) * self.config.random_scale)
         n = means.shape[0]
         dim_sh = num_sh_bases(self.config.sh_degree)
         # layout and activations of reference gauss_params (:187-196): log-scales, logit-opacities
@@ -158,22 +165,22 @@ class FreeGaussianModel(nn.Module):
             {
                 "means": nn.Parameter(means),
                 "scales": nn.Parameter(torch.log(knn_mean_distance(means, 3)).repeat(1, 3) if init_scales is None
-                                       else torch.full((n, 3), float(init_scales))),
-                "quats": nn.Parameter(random_quat_tensor(n)),
-                "features_dc": nn.Parameter(torch.rand(n, 3)),
-                "features_rest": nn.Parameter(torch.zeros(n, dim_sh - 1, 3)),
-                "opacities": nn.Parameter(torch.logit(0.1 * torch.ones(n, 1))),
+                                       else on(torch.full((n, 3), float(init_scales)))),
+                "quats": nn.Parameter(on(random_quat_tensor(n))),
+                "features_dc": nn.Parameter(on(torch.rand(n, 3))),
+                "features_rest": nn.Parameter(on(torch.zeros(n, dim_sh - 1, 3))),
+                "opacities": nn.Parameter(on(torch.logit(0.1 * torch.ones(n, 1)))),
             }
         )
-        self.deform = FreeGaussianDeformableModel(is_blender=is_blender)  # :198
-        self.control = FreeGaussianControllableModel()  # :200
+        self.deform = on(FreeGaussianDeformableModel(is_blender=is_blender))  # :198
+        self.control = on(FreeGaussianControllableModel())  # :200
         if self.config.use_bilateral_grid:  # (:227-233)
             from .bilagrid import BilateralGrid
 
             if not num_train_data:
                 raise ValueError("use_bilateral_grid needs num_train_data (one grid per training image)")
             gx, gy, gw = self.config.grid_shape
-            self.bil_grids = BilateralGrid(num=int(num_train_data), grid_X=gx, grid_Y=gy, grid_W=gw)
+            self.bil_grids = on(BilateralGrid(num=int(num_train_data), grid_X=gx, grid_Y=gy, grid_W=gw))
         self.step = 0
         # (:221-226) Viser's default grey for "random", else the named colour: what an eval render composites over with
         # background "random" (:653), and the colour of the empty-crop output in every mode (:782)

@@ -1232,6 +1232,33 @@ def sort_pairs(keys: torch.Tensor, vals: torch.Tensor, end_bit: int = 64) -> Non
     _call("fg_sort_pairs", n, _ptr(keys), _ptr(vals), int(end_bit), _ptr(ws), ws.numel(), _stream())  # fmt: skip
 
 
+@torch.no_grad()
+def knn(x: torch.Tensor, k: int = 3, squared: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Exact k nearest neighbours of every row of ``x`` [N,3] among the other rows (``fg_knn``: a cell grid, the
+    existing radix sort, a ring search; DESIGN.md "neighbour search").  Returns ``(dist [N,k] float32, idx [N,k] int32)``
+    on ``x``'s device, ascending per row, ties by the lower row number; ``squared=True`` returns the squared distances
+    as the kernel computed them.  Fewer than k + 1 points: min(k, N - 1) columns.  Reads a few KB back to size the
+    grid, so it synchronises the stream and cannot be captured in a graph."""
+    if x.dim() != 2 or x.shape[1] != 3:
+        raise ValueError(f"knn wants [N,3] points, got {tuple(x.shape)}")
+    if not isinstance(k, int) or not 1 <= k <= _lib.KNN_MAX_K:
+        raise ValueError(f"knn wants 1 <= k <= {_lib.KNN_MAX_K}, got {k}")
+    xf = _f32(x.detach(), "x")
+    if not bool(torch.isfinite(xf).all()):
+        raise ValueError("knn: non-finite coordinates")
+    n = xf.shape[0]
+    kk = min(k, n - 1)
+    d2 = torch.empty(n, max(kk, 0), dtype=torch.float32, device=xf.device)
+    idx = torch.empty(n, max(kk, 0), dtype=torch.int32, device=xf.device)
+    if kk <= 0:
+        return d2, idx
+    with torch.cuda.device(xf.device):
+        # (a one-off call: its scratch comes from the caching allocator, not from the step's workspace pool)
+        ws = torch.empty(int(_lib.load().fg_knn_workspace_bytes(n)), dtype=torch.uint8, device=xf.device)
+        _call("fg_knn", n, _ptr(xf), kk, _ptr(d2), _ptr(idx), _ptr(ws), ws.numel(), _stream())
+    return (d2 if squared else d2.sqrt()), idx
+
+
 # --------------------------------------------------------------------------------------------
 # K5 / K6 compositing
 

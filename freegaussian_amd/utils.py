@@ -5,6 +5,7 @@ the path into ``rasterization`` -- verified against golden vectors captured from
 from __future__ import annotations
 
 import math
+import warnings
 from typing import Callable, Tuple
 
 import torch
@@ -114,15 +115,33 @@ def random_quat_tensor(n: int) -> torch.Tensor:
                         b * torch.sin(2 * math.pi * w), b * torch.cos(2 * math.pi * w)], dim=-1)  # fmt: skip
 
 
+# the brute-force fallback of knn_mean_distance holds one [rows, N] fp32 distance block at a time, at most this large
+KNN_FALLBACK_CHUNK_BYTES = 64 << 20
+
+
+def knn_fallback_rows(n: int) -> int:
+    """Rows per chunk of the brute-force fallback: the 2048 it always used while 2048 x n floats fit the budget,
+    fewer beyond (1M points: 16 rows, 64 MB instead of 8 GB a chunk)."""
+    return max(1, min(2048, KNN_FALLBACK_CHUNK_BYTES // (4 * max(n, 1))))
+
+
 def knn_mean_distance(x: torch.Tensor, k: int = 3) -> torch.Tensor:
     """[N,3] -> [N,1] mean Euclidean distance to the k nearest OTHER points: the initial scale of every Gaussian
     (reference freegaussian_model.py:158-162 through ``k_nearest_sklearn``, :293-311 -- sklearn's NearestNeighbors with
-    k + 1 neighbours, the point itself dropped).  The same tree query when sklearn imports; otherwise exact brute force
-    in row chunks (the two agree to rounding: both are exact searches).  Fewer than k + 1 points: the neighbours there are."""
+    k + 1 neighbours, the point itself dropped).  Fewer than k + 1 points: the neighbours there are.
+
+    A CUDA tensor is searched on its device by ``ops.knn`` (exact, hand-written HIP) and the result stays there.  A CPU
+    tensor takes the same tree query as the reference when sklearn imports; otherwise exact brute force in row chunks
+    of bounded size (the two agree to rounding: both are exact searches) -- hours beyond a few 100k points, hence the
+    warning."""
     n = x.shape[0]
     if n <= 1:
-        return torch.ones(n, 1)
+        return torch.ones(n, 1, device=x.device if x.is_cuda else None)
     kk = min(k, n - 1)
+    if x.is_cuda:
+        from . import ops
+
+        return ops.knn(x, kk)[0].mean(dim=-1, keepdim=True)
     xc = x.detach().cpu().float()
     try:
         from sklearn.neighbors import NearestNeighbors
@@ -130,10 +149,16 @@ def knn_mean_distance(x: torch.Tensor, k: int = 3) -> torch.Tensor:
         d, _ = NearestNeighbors(n_neighbors=kk + 1, algorithm="auto", metric="euclidean").fit(xc.numpy()).kneighbors(xc.numpy())
         return torch.from_numpy(d[:, 1:].astype("float32")).mean(dim=-1, keepdim=True)
     except ImportError:
+        if n > 100_000:
+            warnings.warn(f"knn_mean_distance: scikit-learn is missing, brute force over {n} points on the CPU is "
+                          "quadratic; move the points to the GPU (ops.knn) or install scikit-learn", RuntimeWarning)  # fmt: skip
         out = torch.empty(n, 1)
-        for i in range(0, n, 2048):
-            d = torch.cdist(xc[i : i + 2048], xc)
-            out[i : i + 2048, 0] = d.topk(kk + 1, dim=1, largest=False).values[:, 1:].mean(dim=1)
+        rows = knn_fallback_rows(n)
+        for i in range(0, n, rows):
+            # (differences, not the matrix-product form cdist picks at this size: that one loses 4e-4 of a
+            # neighbour's distance to cancellation)
+            d = torch.cdist(xc[i : i + rows], xc, compute_mode="donot_use_mm_for_euclid_dist")
+            out[i : i + rows, 0] = d.topk(kk + 1, dim=1, largest=False).values[:, 1:].mean(dim=1)
         return out
 
 

@@ -44,7 +44,7 @@ typedef void* fg_stream_t;
 #define FG_MAX_CHANNELS 8    /* composited feature channels per splat (RGB, depth, flow, ...) */
 #define FG_SPLAT_FLOATS 16   /* one 64-byte record per Gaussian, see fg_pack_splats */
 #define FG_SH_JAC_FLOATS 10  /* per-Gaussian note of the SH colour for the backward, see fg_preprocess_fwd */
-#define FG_ABI_VERSION 9
+#define FG_ABI_VERSION 10
 #define FG_COUNT_OUT_WORDS 16 /* int64 words of a count_out block (fg_stbin_count, fg_step_io): ABI 9 */
 
 int fg_abi_version(void);
@@ -775,6 +775,22 @@ typedef struct fg_adam_tensor {
   int64_t step;
 } fg_adam_tensor;
 int fg_adam_step_multi(int count, const fg_adam_tensor* tensors, fg_stream_t stream);
+
+/* ---- K9 (ABI 10): exact k nearest neighbours of every row of xyz[n,3] among the OTHER rows (the initial scales of the
+ * Gaussians: mean distance to the three nearest neighbours, freegaussian_model.py:158-162, :293-311).
+ * dist2_out[n,k]: SQUARED Euclidean distances, ascending per row, d2 = (dx dx + dy dy) + dz dz in fp32 without contraction,
+ * dx = x_query - x_neighbour; idx_out[n,k] (nullable): the neighbours' row numbers.  Rows are in the caller's order.
+ * Ties: candidates are ordered by (d2, row number), so among equal distances the lower row comes first -- and is the one
+ * kept at the k-th place; the query's own row is excluded by number, another row at the same position is a neighbour at
+ * distance 0.  1 <= k <= FG_KNN_MAX_K and n > k, n < 2^31 (else FG_ERR_INVALID_ARG, as for a workspace below
+ * fg_knn_workspace_bytes(n)); n == 0 does nothing.
+ * NOT capturable in a graph: the call reads a few KB of sampled coordinates back (one stream synchronisation) to size
+ * its cell grid.  Non-finite coordinates are the caller's responsibility: the call stays in bounds, the rows' results
+ * are unspecified. */
+#define FG_KNN_MAX_K 8
+size_t fg_knn_workspace_bytes(int64_t n);
+int fg_knn(int64_t n, const float* xyz, int k, float* dist2_out, int32_t* idx_out, void* workspace,
+           size_t workspace_bytes, fg_stream_t stream);
 
 #ifdef __cplusplus
 }
