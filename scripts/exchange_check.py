@@ -1,5 +1,9 @@
 """Factored view-DP exchange vs the plain flat all-reduce, W ranks (torchrun), real kernels.
-On a 1-GPU box: FG_BENCH_BACKEND=gloo and every rank shares the GPU.  Prints 'exchange ok' on rank 0."""
+On a 1-GPU box: FG_BENCH_BACKEND=gloo and every rank shares the GPU.  Prints 'exchange ok' on rank 0.
+
+This is a check of the exchange's plumbing across ranks, NOT of rows: one relative L2 per whole gradient tensor (one wrong
+row in 60 000 stays under it), SH degree 3 and a 16-coefficient table only.  The kernels themselves are pinned row by row
+against a float64 restatement, over every table layout, in tests/test_gpu_exchange_kernels.py."""
 import os
 import sys
 

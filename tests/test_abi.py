@@ -131,6 +131,46 @@ def test_argument_validation_of_the_newer_entry_points_without_gpu():
     assert _lib.STBIN_LONG_SEGMENTS == 1
 
 
+def test_argument_validation_of_the_exchange_kernels_without_gpu():
+    """The view-DP exchange entry points (tests/test_gpu_exchange_kernels.py pins what they compute): every call here
+    returns before a launch.  N = 0 with null pointers is FG_OK once the shape arguments are accepted, so a refusal at
+    N = 0 is a refusal of the shape argument itself, not of the null pointers."""
+    lib = _lib.load()
+    # expand: block_stride >= 4 + capacity (1 + payload floats), dense_stride >= 3 N + 3 | 6 N
+    assert lib.fg_payload_expand(0, 3, 2, None, 4 + 5 * 4, 5, None, 3, None) == 0
+    assert lib.fg_payload_expand(0, 3, 2, None, 4 + 5 * 4 - 1, 5, None, 3, None) == -1
+    assert lib.fg_payload_expand(0, 6, 2, None, 4 + 5 * 7, 5, None, 0, None) == 0
+    assert lib.fg_payload_expand(0, 6, 2, None, 4 + 5 * 7 - 1, 5, None, 0, None) == -1
+    assert lib.fg_payload_expand(0, 3, 2, None, 4 + 5 * 4, 5, None, 2, None) == -1  # no room for the camera position
+    assert lib.fg_payload_expand(8, 3, 2, None, 4 + 5 * 4, 5, None, 3 * 8 + 2, None) == -1
+    assert lib.fg_payload_expand(8, 6, 2, None, 4 + 5 * 7, 5, None, 6 * 8 - 1, None) == -1
+    assert lib.fg_payload_expand(8, 3, 2, None, 4 + 5 * 4 - 1, 5, None, 3 * 8 + 3, None) == -1
+    assert lib.fg_payload_expand(0, 4, 2, None, 64, 5, None, 64, None) == -1
+    assert lib.fg_payload_expand(0, 3, 0, None, 64, 5, None, 64, None) == -1  # no view
+    assert lib.fg_payload_expand(0, 3, 2, None, 64, -1, None, 64, None) == -1
+    # compact: payload floats 3 or 6, capacity >= 0 (0 is a block of the header alone)
+    assert lib.fg_payload_compact(0, 3, None, None, 0, None, None) == 0
+    assert lib.fg_payload_compact(0, 6, None, None, 0, None, None) == 0
+    for pf in (0, 2, 4, 5, 7):
+        assert lib.fg_payload_compact(0, pf, None, None, 8, None, None) == -1
+    assert lib.fg_payload_compact(0, 3, None, None, -1, None, None) == -1
+    assert lib.fg_payload_compact(-1, 3, None, None, 8, None, None) == -1
+    assert lib.fg_payload_compact(8, 3, None, None, 8, None, None) == -1  # rows, but no arrays
+    # rebuild: the table holds (degree+1)^2 .. 16 coefficients; the split form needs features_rest unless k_stored is 1
+    assert lib.fg_sh_grad_accumulate(0, 1, 3, 16, None, None, 3, 3, 1.0, None, None) == 0
+    assert lib.fg_sh_grad_accumulate(0, 1, 3, 17, None, None, 3, 3, 1.0, None, None) == -1
+    assert lib.fg_sh_grad_accumulate(0, 1, 2, 8, None, None, 3, 3, 1.0, None, None) == -1  # degree 2 needs 9
+    assert lib.fg_sh_grad_accumulate(0, 1, 0, 1, None, None, 0, 6, 1.0, None, None) == 0
+    assert lib.fg_sh_grad_accumulate_split(0, 1, 0, 1, None, None, 3, 3, 1.0, None, None, None) == 0
+    assert lib.fg_sh_grad_accumulate_split(0, 1, 0, 4, None, None, 3, 3, 1.0, None, None, None) == -1
+    assert lib.fg_sh_grad_accumulate_split(0, 1, 1, 4, None, None, 3, 3, 1.0, None, None, None) == -1
+    assert lib.fg_sh_grad_accumulate_split(0, 1, 3, 17, None, None, 3, 3, 1.0, None, None, None) == -1
+    rest = 256  # (an address nobody reads: N = 0 returns before any use of it)
+    assert lib.fg_sh_grad_accumulate_split(0, 1, 3, 16, None, None, 3, 3, 1.0, None, rest, None) == 0
+    assert lib.fg_sh_grad_accumulate_split(0, 1, 3, 17, None, None, 3, 3, 1.0, None, rest, None) == -1
+    assert lib.fg_sh_grad_accumulate_split(8, 1, 0, 1, None, None, 27, 3, 1.0, None, None, None) == -1  # rows, no arrays
+
+
 def test_step_api_layout_and_argument_validation_without_gpu():
     """fg_step_* (ABI 7): one workspace query per step shape, every buffer 256-byte aligned inside the two
     caller-allocated workspaces; descriptors and pointers are checked before any launch."""
