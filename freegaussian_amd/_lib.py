@@ -102,13 +102,18 @@ SIGNATURES = {
     "fg_flow_bwd": (c_int, [c_int, P, P, P, P, P, P, P, P, P, P, P, P, P]),
     "fg_knn_workspace_bytes": (c_size_t, [c_int64]),
     "fg_knn": (c_int, [c_int64, P, c_int, P, P, P, c_size_t, P]),
+    "fg_mlp_workspace_bytes": (c_size_t, [c_int64]),
+    "fg_mlp_fwd": (c_int, [c_int64, P, P, c_size_t, P]),  # (N, const fg_mlp_desc*, workspace, bytes, stream)
 }  # fmt: skip
 
 # test hooks, not declared in the public header
 _EXTRA = {"fg_debug_wave_reduce16": (c_int, [P, P, P]), "fg_debug_knn_grid": (c_int, [c_int64, P, c_int, P, P])}
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 KNN_MAX_K = 8  # FG_KNN_MAX_K
+MLP_ROW_TILE = 64  # FG_MLP_ROW_TILE
+MLP_MAX_HEADS = 4  # FG_MLP_MAX_HEADS
+MLP_SE3, MLP_PLAIN = 0, 1  # FG_MLP_SE3, FG_MLP_PLAIN
 STBIN_LONG_SEGMENTS = 1  # FG_STBIN_LONG_SEGMENTS
 STBIN_TEST_SMALL_SLABS = 4  # FG_STBIN_TEST_SMALL_SLABS (tests: the sample sort's overflow path)
 STEP_NO_FOOTPRINT_MASKS = 2  # FG_STEP_NO_FOOTPRINT_MASKS
@@ -174,6 +179,16 @@ class StepLayout(ctypes.Structure):
     _fields_ = [("keep_bytes", ctypes.c_int64), ("tmp_bytes", ctypes.c_int64),
                 ("offset", ctypes.c_int64 * len(STEP_BUFFERS)), ("nbytes", ctypes.c_int64 * len(STEP_BUFFERS)),
                 ("jobs_words", ctypes.c_int64), ("seg_ckpt_floats", ctypes.c_int64), ("channels", ctypes.c_int32)]  # fmt: skip
+
+
+class MlpDesc(ctypes.Structure):
+    """``fg_mlp_desc``: field order = the header's; device pointers as integers."""
+
+    _fields_ = [(n, ctypes.c_int32) for n in ("size", "mode", "depth", "width", "multires", "aux_width", "n_heads")] + [
+        ("head_rows", ctypes.c_int32 * MLP_MAX_HEADS), ("reserved", ctypes.c_int32), ("aux_stride", ctypes.c_int64),
+        ("x", ctypes.c_void_p), ("aux", ctypes.c_void_p), ("weight", ctypes.c_void_p * 8), ("bias", ctypes.c_void_p * 8),
+        ("head_weight", ctypes.c_void_p * MLP_MAX_HEADS), ("head_bias", ctypes.c_void_p * MLP_MAX_HEADS),
+        ("out", ctypes.c_void_p * MLP_MAX_HEADS)]  # fmt: skip
 
 
 def load() -> ctypes.CDLL:

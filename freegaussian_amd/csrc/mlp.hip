@@ -1,0 +1,349 @@
+// K10: fused fp32 forward of the deformation / control MLP (freegaussian_amd/deform.py) for inference: one call, two launches --
+// the weights re-ordered (pack), then the network, where a workgroup takes a
+// tile of FG_MLP_ROW_TILE rows from the positions to the rigid transforms (or the plain head outputs); no [N,256]
+// activation ever reaches global memory.
+//
+//   pack     : a small launch copies the trunk weights into the caller's workspace in the order the tiles read them
+//              (below) and the head weights / biases into one zero-padded [16,256] / [16] block.  ~2 MB read and written
+//              per call (measured: profiles/mlp_forward.md); nothing is kept between calls (the library has no state, and the weights of a
+//              module in training change every step).
+//   input    : row = [posenc(x, 10) (63), aux (A), 0 ...] written to LDS, K padded to a multiple of 8; sincosf is the
+//              accurate one (arguments reach 512 x), and x 2^k is exact, so the arguments are utils.positional_encoding's
+//   trunk    : 8 linears of 256 + ReLU, activations in place in LDS ([64][260] floats: the row stride of 4 mod 64 dwords
+//              makes the 16-byte operand reads conflict free).  Four waves, each owning 64 of the 256 output columns as
+//              2 x 2 tiles of v_mfma_f32_32x32x2_f32 (exact fp32: a k-ordered fmaf chain starting from the bias).  The
+//              layer after the skip first runs over the input row (kept in LDS), then over h: cat([inp, h]).
+//   k order  : K is walked in groups of 8; lane half h of a wave holds k = 8 g + 4 h + s in element s of one 16-byte read,
+//              for A (LDS) and for B (packed weights) alike, so a chain adds k = 8g, 8g+4, 8g+1, 8g+5, ... -- a fixed
+//              order per output element that depends on nothing but the element's own row: rows are independent, bit
+//              for bit, whatever tile or lane they land in.
+//   packed B : Wp[g][j][e] = W[j][8 g + e] (j = output column, zero beyond the layer's K): the 64 lanes of one B read
+//              fetch 1 KB contiguous.
+//   heads    : <= 16 output rows over the final h, v_mfma_f32_16x16x4_f32, one 16-row block per wave
+//   epilogue : one lane per row: exp_se3 + the transform of x (SE(3) mode) or plain stores
+// Plain C++ stores only; no atomics; the result is deterministic.
+#include <cmath>
+
+#include "fg_common.h"
+
+namespace {
+
+constexpr int MLP_M = FG_MLP_ROW_TILE;  // rows per workgroup
+constexpr int MLP_W = 256;              // hidden width
+constexpr int MLP_D = 8;                // trunk depth
+constexpr int MLP_SKIP = 4;             // the layer AFTER this index also takes the input row
+constexpr int MLP_FREQS = 10;
+constexpr int MLP_XCH = 3 * (1 + 2 * MLP_FREQS);  // 63
+constexpr int MLP_ACT_STRIDE = MLP_W + 4;         // 260: 4 mod 64 dwords
+constexpr int MLP_IN_STRIDE = 128 + 4;            // input row: <= 63 + 64 channels, padded to 128
+constexpr int MLP_HEAD_COL = 4;                   // head results land in columns 4..19 of the (then dead) input rows
+constexpr int MLP_BLOCK = 256;
+constexpr int MLP_GROUP_FLOATS = MLP_W * 8;  // one k-group of a packed layer
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+// packed workspace (floats): the trunk layers one after the other, then the heads
+struct MlpLayout {
+  int g0;               // k-groups of the input row
+  size_t layer[MLP_D];  // float offset of each packed layer
+  int groups[MLP_D];
+  size_t head_w, head_b, total;  // [16][256], [16]; total in floats
+};
+
+inline MlpLayout mlp_layout(int A) {
+  MlpLayout L;
+  L.g0 = (MLP_XCH + A + 7) / 8;
+  size_t at = 0;
+  for (int l = 0; l < MLP_D; ++l) {
+    L.groups[l] = l == 0 ? L.g0 : (l == MLP_SKIP + 1 ? L.g0 + MLP_W / 8 : MLP_W / 8);
+    L.layer[l] = at;
+    at += (size_t)L.groups[l] * MLP_GROUP_FLOATS;
+  }
+  L.head_w = at;
+  at += 16 * MLP_W;
+  L.head_b = at;
+  at += 16;
+  L.total = at;
+  return L;
+}
+
+struct MlpArgs {
+  const float* x;
+  const float* aux;
+  int64_t aux_stride;
+  const float* W[MLP_D];
+  const float* b[MLP_D];
+  const float* head_W[FG_MLP_MAX_HEADS];
+  const float* head_b[FG_MLP_MAX_HEADS];
+  int head_rows[FG_MLP_MAX_HEADS];
+  float* out[FG_MLP_MAX_HEADS];
+  int n_heads, A, mode;
+};
+
+__global__ void __launch_bounds__(MLP_BLOCK)
+mlp_pack_kernel(MlpArgs p, MlpLayout L, float* __restrict__ ws) {
+  const size_t at = (size_t)blockIdx.x * MLP_BLOCK + threadIdx.x;
+  if (at >= L.total) return;
+  const int in_ch = MLP_XCH + p.A;
+  if (at >= L.head_b) {
+    int o = (int)(at - L.head_b), v = 0;
+    float r = 0.f;
+    for (int h = 0; h < p.n_heads; ++h) {
+      if (o >= v && o < v + p.head_rows[h]) r = p.head_b[h][o - v];
+      v += p.head_rows[h];
+    }
+    ws[at] = r;
+    return;
+  }
+  if (at >= L.head_w) {
+    const int o = (int)(at - L.head_w) / MLP_W, k = (int)(at - L.head_w) % MLP_W;
+    int v = 0;
+    float r = 0.f;
+    for (int h = 0; h < p.n_heads; ++h) {
+      if (o >= v && o < v + p.head_rows[h]) r = p.head_W[h][(o - v) * MLP_W + k];
+      v += p.head_rows[h];
+    }
+    ws[at] = r;
+    return;
+  }
+  int l = 0;
+  while (l + 1 < MLP_D && at >= L.layer[l + 1]) ++l;
+  const size_t rel = at - L.layer[l];
+  const int g = (int)(rel / MLP_GROUP_FLOATS), j = (int)(rel % MLP_GROUP_FLOATS) / 8, e = (int)(rel % 8);
+  const float* W = p.W[l];
+  float r = 0.f;
+  if (l == 0) {
+    const int k = 8 * g + e;
+    if (k < in_ch) r = W[(size_t)j * in_ch + k];
+  } else if (l == MLP_SKIP + 1) {
+    const int ld = in_ch + MLP_W;
+    if (g < L.g0) {
+      const int k = 8 * g + e;
+      if (k < in_ch) r = W[(size_t)j * ld + k];
+    } else {
+      r = W[(size_t)j * ld + in_ch + 8 * (g - L.g0) + e];
+    }
+  } else {
+    r = W[(size_t)j * MLP_W + 8 * g + e];
+  }
+  ws[at] = r;
+}
+
+// acc += src[rows][8 groups ...] x Wp: `a` points at this lane's row of the LDS source (+ 4 h), `b` at this lane's column
+// of the packed layer (+ 4 h).  The next group's operands are fetched before the current group's 16 MFMAs.
+__device__ __forceinline__ void mlp_gemm_part(f32x16 (&acc)[2][2], const float* a, int stride, int groups,
+                                              const float* __restrict__ b) {
+  f32x4 a0 = *reinterpret_cast<const f32x4*>(a), a1 = *reinterpret_cast<const f32x4*>(a + 32 * stride);
+  f32x4 b0 = *reinterpret_cast<const f32x4*>(b), b1 = *reinterpret_cast<const f32x4*>(b + 32 * 8);
+  for (int g = 0; g < groups; ++g) {
+    f32x4 na0 = a0, na1 = a1, nb0 = b0, nb1 = b1;
+    if (g + 1 < groups) {
+      const float* an = a + 8 * (g + 1);
+      const float* bn = b + (size_t)(g + 1) * MLP_GROUP_FLOATS;
+      na0 = *reinterpret_cast<const f32x4*>(an);
+      na1 = *reinterpret_cast<const f32x4*>(an + 32 * stride);
+      nb0 = *reinterpret_cast<const f32x4*>(bn);
+      nb1 = *reinterpret_cast<const f32x4*>(bn + 32 * 8);
+    }
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[s], b0[s], acc[0][0], 0, 0, 0);
+      acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[s], b1[s], acc[0][1], 0, 0, 0);
+      acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[s], b0[s], acc[1][0], 0, 0, 0);
+      acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[s], b1[s], acc[1][1], 0, 0, 0);
+    }
+    a0 = na0, a1 = na1, b0 = nb0, b1 = nb1;
+  }
+}
+
+// exp_se3 of (w / |w| + 1e-5, v / |w| + 1e-5; |w|) in the arithmetic of utils.exp_se3, and the transform of x
+__device__ __forceinline__ void mlp_se3_row(const float* hd, const float* x, int64_t row, const MlpArgs& p) {
+  const float theta = sqrtf(hd[0] * hd[0] + hd[1] * hd[1] + hd[2] * hd[2]);
+  const float w0 = hd[0] / theta + 1e-5f, w1 = hd[1] / theta + 1e-5f, w2 = hd[2] / theta + 1e-5f;
+  const float v[3] = {hd[3] / theta + 1e-5f, hd[4] / theta + 1e-5f, hd[5] / theta + 1e-5f};
+  const float Wm[3][3] = {{0.f, -w2, w1}, {w2, 0.f, -w0}, {-w1, w0, 0.f}};
+  float W2[3][3];
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) W2[i][j] = Wm[i][0] * Wm[0][j] + Wm[i][1] * Wm[1][j] + Wm[i][2] * Wm[2][j];
+  float s, c;
+  sincosf(theta, &s, &c);
+  float T[3][4];
+  for (int i = 0; i < 3; ++i) {
+    float G[3];
+    for (int j = 0; j < 3; ++j) {
+      const float eye = i == j ? 1.f : 0.f;
+      T[i][j] = eye + s * Wm[i][j] + (1.f - c) * W2[i][j];
+      G[j] = theta * eye + (1.f - c) * Wm[i][j] + (theta - s) * W2[i][j];
+    }
+    T[i][3] = G[0] * v[0] + G[1] * v[1] + G[2] * v[2];
+  }
+  if (float* d = p.out[0]) {
+    d += row * 16;
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 4; ++j) d[4 * i + j] = T[i][j];
+    d[12] = 0.f, d[13] = 0.f, d[14] = 0.f, d[15] = 1.f;
+  }
+  if (float* d = p.out[1])
+    for (int j = 0; j < 4; ++j) d[row * 4 + j] = hd[6 + j];
+  if (float* d = p.out[2])
+    for (int j = 0; j < 3; ++j) d[row * 3 + j] = hd[10 + j];
+  if (float* d = p.out[3])  // (the homogeneous coordinate of a rigid transform is exactly 1: no divide)
+    for (int i = 0; i < 3; ++i) d[row * 3 + i] = T[i][0] * x[0] + T[i][1] * x[1] + T[i][2] * x[2] + T[i][3];
+}
+
+__global__ void __launch_bounds__(MLP_BLOCK)
+mlp_fwd_kernel(int64_t N, MlpArgs p, MlpLayout L, const float* __restrict__ ws) {
+  __shared__ __attribute__((aligned(16))) float act[MLP_M * MLP_ACT_STRIDE];
+  __shared__ __attribute__((aligned(16))) float inp[MLP_M * MLP_IN_STRIDE];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t row0 = (int64_t)blockIdx.x * MLP_M;
+
+  // ---- the input rows: four lanes per row
+  {
+    const int r = tid >> 2, q = tid & 3;
+    const int64_t row = row0 + r;
+    const bool live = row < N;
+    float* dst = inp + r * MLP_IN_STRIDE;
+    float x[3] = {0.f, 0.f, 0.f};
+    if (live)
+      for (int c = 0; c < 3; ++c) x[c] = p.x[row * 3 + c];
+    if (q == 3)
+      for (int c = 0; c < 3; ++c) dst[c] = x[c];
+    for (int k = q; k < MLP_FREQS; k += 4) {
+      const float f = (float)(1 << k);
+      for (int c = 0; c < 3; ++c) {
+        float s, co;
+        sincosf(x[c] * f, &s, &co);
+        dst[3 + 6 * k + c] = s;
+        dst[3 + 6 * k + 3 + c] = co;
+      }
+    }
+    const float* aux = p.aux + row * p.aux_stride;
+    for (int a = q; a < p.A; a += 4) dst[MLP_XCH + a] = live ? aux[a] : 0.f;
+    for (int k = MLP_XCH + p.A + q; k < 8 * L.g0; k += 4) dst[k] = 0.f;
+  }
+  __syncthreads();
+
+  // ---- trunk
+  const int li = lane & 31, lh = lane >> 5;
+  const float* a_inp = inp + li * MLP_IN_STRIDE + 4 * lh;
+  const float* a_act = act + li * MLP_ACT_STRIDE + 4 * lh;
+  const size_t b_lane = (size_t)(wave * 64 + li) * 8 + 4 * lh;
+  for (int l = 0; l < MLP_D; ++l) {
+    f32x16 acc[2][2];
+    const float* bias = p.b[l] + wave * 64 + li;
+    for (int cb = 0; cb < 2; ++cb) {
+      const float bv = bias[32 * cb];
+      for (int e = 0; e < 16; ++e) acc[0][cb][e] = bv, acc[1][cb][e] = bv;
+    }
+    const float* wp = ws + L.layer[l] + b_lane;
+    if (l == 0) {
+      mlp_gemm_part(acc, a_inp, MLP_IN_STRIDE, L.g0, wp);
+    } else if (l == MLP_SKIP + 1) {
+      mlp_gemm_part(acc, a_inp, MLP_IN_STRIDE, L.g0, wp);
+      mlp_gemm_part(acc, a_act, MLP_ACT_STRIDE, MLP_W / 8, wp + (size_t)L.g0 * MLP_GROUP_FLOATS);
+    } else {
+      mlp_gemm_part(acc, a_act, MLP_ACT_STRIDE, MLP_W / 8, wp);
+    }
+    __syncthreads();  // every wave has read the whole of the previous layer
+    // C/D map of the 32x32 MFMA: column = lane & 31, row = (e & 3) + 8 (e >> 2) + 4 (lane >> 5)
+    for (int rb = 0; rb < 2; ++rb)
+      for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+          const int r = 32 * rb + (e & 3) + 8 * (e >> 2) + 4 * lh;
+          act[r * MLP_ACT_STRIDE + wave * 64 + 32 * cb + li] = fmaxf(acc[rb][cb][e], 0.f);
+        }
+    __syncthreads();
+  }
+
+  // ---- heads: wave w takes rows 16 w .. 16 w + 15; A[row = lane & 15][k = lane >> 4], four k per MFMA
+  {
+    const int hi = lane & 15, hq = lane >> 4;
+    const float* a = act + (wave * 16 + hi) * MLP_ACT_STRIDE + 4 * hq;
+    const float* b = ws + L.head_w + hi * MLP_W + 4 * hq;
+    const float bv = ws[L.head_b + hi];
+    f32x4 acc = {bv, bv, bv, bv};
+    for (int g = 0; g < MLP_W / 16; ++g) {
+      const f32x4 av = *reinterpret_cast<const f32x4*>(a + 16 * g);
+      const f32x4 bw = *reinterpret_cast<const f32x4*>(b + 16 * g);
+#pragma unroll
+      for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[s], bw[s], acc, 0, 0, 0);
+    }
+    // C/D map of the 16x16 MFMA: column = lane & 15, row = 4 (lane >> 4) + e
+    for (int e = 0; e < 4; ++e) inp[(wave * 16 + 4 * hq + e) * MLP_IN_STRIDE + MLP_HEAD_COL + hi] = acc[e];
+  }
+  __syncthreads();
+
+  // ---- epilogue: one lane per row
+  if (tid < MLP_M && row0 + tid < N) {
+    const int64_t row = row0 + tid;
+    const float* src = inp + tid * MLP_IN_STRIDE;
+    float hd[16];
+    for (int o = 0; o < 16; ++o) hd[o] = src[MLP_HEAD_COL + o];
+    if (p.mode == FG_MLP_SE3) {
+      const float x[3] = {src[0], src[1], src[2]};
+      mlp_se3_row(hd, x, row, p);
+    } else {
+      int v = 0;
+      for (int h = 0; h < p.n_heads; ++h) {
+        const int rows = p.head_rows[h];
+        if (float* d = p.out[h])
+          for (int j = 0; j < rows; ++j) d[row * rows + j] = hd[v + j];
+        v += rows;
+      }
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" size_t fg_mlp_workspace_bytes(int64_t N) {
+  // (the packed weights alone: the same for every N; sized for the widest input row)
+  return N < 0 ? 0 : mlp_layout(64).total * sizeof(float);
+}
+
+extern "C" int fg_mlp_fwd(int64_t N, const fg_mlp_desc* d, void* workspace, size_t workspace_bytes, fg_stream_t stream) {
+  if (N < 0) return FG_ERR_INVALID_ARG;
+  if (N == 0) return FG_OK;
+  if (!d || d->size != (int32_t)sizeof(fg_mlp_desc)) return FG_ERR_INVALID_ARG;
+  if (d->aux_width < 1 || d->aux_width > 64 || d->aux_stride < 0) return FG_ERR_INVALID_ARG;
+  if (d->mode != FG_MLP_SE3 && d->mode != FG_MLP_PLAIN) return FG_ERR_INVALID_ARG;
+  if (d->n_heads < 1 || d->n_heads > FG_MLP_MAX_HEADS) return FG_ERR_INVALID_ARG;
+  int total = 0;
+  for (int h = 0; h < d->n_heads; ++h) {
+    if (d->head_rows[h] < 1 || d->head_rows[h] > 16) return FG_ERR_INVALID_ARG;
+    total += d->head_rows[h];
+  }
+  if (total > 16) return FG_ERR_INVALID_ARG;
+  if (d->mode == FG_MLP_SE3 &&
+      (d->n_heads != 4 || d->head_rows[0] != 3 || d->head_rows[1] != 3 || d->head_rows[2] != 4 || d->head_rows[3] != 3))
+    return FG_ERR_INVALID_ARG;
+  if (d->depth != MLP_D || d->width != MLP_W || d->multires != MLP_FREQS) return FG_ERR_UNSUPPORTED;
+  if (!d->x || !d->aux || !workspace) return FG_ERR_INVALID_ARG;
+  for (int l = 0; l < MLP_D; ++l)
+    if (!d->weight[l] || !d->bias[l]) return FG_ERR_INVALID_ARG;
+  for (int h = 0; h < d->n_heads; ++h)
+    if (!d->head_weight[h] || !d->head_bias[h]) return FG_ERR_INVALID_ARG;
+  if (N > ((int64_t)1 << 31) * MLP_M - MLP_M) return FG_ERR_INVALID_ARG;  // (the grid's x extent)
+  const MlpLayout L = mlp_layout(d->aux_width);
+  if (workspace_bytes < fg_mlp_workspace_bytes(N)) return FG_ERR_WORKSPACE;  // (the documented size, whatever aux_width)
+  if (reinterpret_cast<uintptr_t>(workspace) % 16) return FG_ERR_INVALID_ARG;
+
+  MlpArgs p = {};
+  p.x = d->x, p.aux = d->aux, p.aux_stride = d->aux_stride;
+  for (int l = 0; l < MLP_D; ++l) p.W[l] = d->weight[l], p.b[l] = d->bias[l];
+  for (int h = 0; h < d->n_heads; ++h) {
+    p.head_W[h] = d->head_weight[h], p.head_b[h] = d->head_bias[h], p.head_rows[h] = d->head_rows[h];
+    p.out[h] = d->out[h];
+  }
+  p.n_heads = d->n_heads, p.A = d->aux_width, p.mode = d->mode;
+  hipStream_t s = fg_hip_stream(stream);
+  float* ws = static_cast<float*>(workspace);
+  hipLaunchKernelGGL(mlp_pack_kernel, dim3((unsigned)((L.total + MLP_BLOCK - 1) / MLP_BLOCK)), dim3(MLP_BLOCK), 0, s, p, L, ws);
+  FG_RETURN_IF_LAUNCH_FAILED();
+  hipLaunchKernelGGL(mlp_fwd_kernel, dim3((unsigned)((N + MLP_M - 1) / MLP_M)), dim3(MLP_BLOCK), 0, s, N, p, L, ws);
+  FG_RETURN_IF_LAUNCH_FAILED();
+  return FG_OK;
+}

@@ -1,9 +1,12 @@
-"""Deformation / control MLPs that feed the rasterizer (dense GEMMs: they stay on PyTorch-ROCm /
-hipBLASLt).  Behaviour and ``state_dict`` key names follow the reference's
+"""Deformation / control MLPs that feed the rasterizer.  Training runs the dense GEMMs on PyTorch-ROCm / hipBLASLt
+(SURVEY.md §2 row 5); a forward that needs no gradient over at least ``FUSED_MIN_ROWS`` rows is one fused HIP call
+(``ops.mlp_forward``: a weight re-ordering launch and the network's launch; ``FG_FUSED_MLP=0`` turns it off).  Behaviour and ``state_dict`` key names follow the reference's
 ``FreeGaussianDeformableModel`` / ``FreeGaussianControllableModel``
 (freegaussian/freegaussian_model.py:1054-1145) so stage-1 checkpoints load unchanged; outputs are
 checked against golden vectors produced by the reference classes (tests/golden/g_mlp.npz)."""
 from __future__ import annotations
+
+import os
 
 import torch
 import torch.nn as nn
@@ -65,6 +68,42 @@ def _run_trunk(layers: nn.ModuleList, inp: torch.Tensor, skip_at: int) -> torch.
     return h
 
 
+# Rows from which a gradient-free forward takes the fused kernel: the threshold `_linear` uses, so every small scene keeps
+# the torch path bit for bit.  Raised if the measured crossover lies above it, never lowered
+# (profiles/mlp_forward.md: the fused forward takes 0.70 x the torch path's time at 33 000 rows, 0.61 x at 240 000 and 1M).
+FUSED_MIN_ROWS = 4 * _TallLinear.CHUNK
+# What an unset FG_FUSED_MLP means: "1" only where the measurement of profiles/mlp_forward.md meets the default-on rule
+# (fused median <= 0.8 x the torch median from FUSED_MIN_ROWS rows on)
+FUSED_DEFAULT = "1"
+
+
+def fused_applies(module: nn.Module, x: torch.Tensor, other: torch.Tensor) -> bool:
+    """Whether ``module(x, other)`` runs as one ``ops.mlp_forward`` call: CUDA fp32 inputs, nothing that wants a gradient,
+    enough rows, the one network shape the kernel is built for, and ``FG_FUSED_MLP`` (read here, on the host; unset =
+    ``FUSED_DEFAULT``) not "0".  Anything else: the torch ops."""
+    if os.environ.get("FG_FUSED_MLP", FUSED_DEFAULT) == "0":
+        return False
+    if not (x.is_cuda and other.is_cuda and x.dtype == other.dtype == torch.float32 and x.dim() == other.dim() == 2):
+        return False
+    other_ch = 3 if isinstance(module, FreeGaussianControllableModel) else 1
+    if x.shape[0] < FUSED_MIN_ROWS or other.shape[0] != x.shape[0] or x.shape[1] != 3 or other.shape[1] != other_ch:
+        return False
+    if (module.D, module.W, module.multires, module.skip_at) != (8, 256, 10, 4):
+        return False
+    taped = torch.is_grad_enabled()
+    if taped and (x.requires_grad or other.requires_grad):
+        return False
+    for p in module.parameters():
+        if not p.is_cuda or p.dtype != torch.float32 or (taped and p.requires_grad):
+            return False
+    return True
+
+
+def _one_row_if_broadcast(t: torch.Tensor) -> torch.Tensor:
+    """``times.expand(N, -1)`` has row stride 0: its encoding is computed on one row and broadcast by the kernel."""
+    return t[:1] if t.stride(0) == 0 else t
+
+
 class FreeGaussianDeformableModel(nn.Module):
     """(x [N,3], t [N,1]) -> (SE(3) per Gaussian [N,4,4], d_rotation [N,4], d_scaling [N,3])."""
 
@@ -87,7 +126,25 @@ class FreeGaussianDeformableModel(nn.Module):
         self.gaussian_rotation = nn.Linear(W, 4)
         self.gaussian_scaling = nn.Linear(W, 3)
 
+    def _fused(self, x: torch.Tensor, t: torch.Tensor, outs):
+        from . import ops
+
+        with torch.no_grad():
+            aux = positional_encoding(_one_row_if_broadcast(t), self.t_multires)
+            if self.is_blender:
+                aux = self.timenet(aux)
+            heads = (self.branch_w, self.branch_v, self.gaussian_rotation, self.gaussian_scaling)
+            return ops.mlp_forward(x, aux, self.linear, heads, mode="se3", outs=outs)
+
+    def deformed_points(self, x: torch.Tensor, t: torch.Tensor):
+        """(transform_points(d_xyz, x) [N,3], d_rotation, d_scaling) without the [N,4,4] transforms: what a render that
+        needs no gradient reads.  Only where ``fused_applies(self, x, t)``."""
+        _, rot, scale, pts = self._fused(x, t, (False, None, None, None))
+        return pts, rot, scale
+
     def forward(self, x: torch.Tensor, t: torch.Tensor):
+        if fused_applies(self, x, t):
+            return tuple(self._fused(x, t, (None, None, None, False))[:3])
         t_emb = positional_encoding(t, self.t_multires)
         if self.is_blender:
             t_emb = self.timenet(t_emb)
@@ -114,6 +171,12 @@ class FreeGaussianControllableModel(nn.Module):
         self.d_rot = nn.Linear(W, 4)
 
     def forward(self, x: torch.Tensor, value: torch.Tensor):
+        if fused_applies(self, x, value):
+            from . import ops
+
+            with torch.no_grad():
+                aux = positional_encoding(_one_row_if_broadcast(value), self.multires)
+                return tuple(ops.mlp_forward(x, aux, self.linear, (self.d_xyz, self.d_rot, self.d_scale), mode="plain"))
         inp = torch.cat([positional_encoding(x, self.multires), positional_encoding(value, self.multires)], dim=-1)
         h = _run_trunk(self.linear, inp, self.skip_at)
         return _linear(self.d_xyz, h), _linear(self.d_rot, h), _linear(self.d_scale, h)

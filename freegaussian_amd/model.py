@@ -19,7 +19,7 @@ from typing import Dict, List, Optional, Union
 import torch
 from torch import nn
 
-from .deform import FreeGaussianControllableModel, FreeGaussianDeformableModel
+from .deform import FreeGaussianControllableModel, FreeGaussianDeformableModel, fused_applies
 from .rasterization import num_sh_bases, rasterization
 from .utils import get_viewmat, knn_mean_distance, random_quat_tensor, resize_image, transform_points
 
@@ -496,8 +496,12 @@ class FreeGaussianModel(nn.Module):
         else:
             pts = self.means
             times = times.to(self.device).expand(pts.shape[0], -1)
-            d_xyz, d_rotation, d_scaling = self.deform(pts.detach(), times)
-            means = transform_points(d_xyz, pts)  # (:840-843; not torch.bmm: utils.small_bmm)
+            if not torch.is_grad_enabled() and fused_applies(self.deform, pts, times):
+                # (no gradient wanted: the fused forward applies the transform itself and never writes [N,4,4])
+                means, d_rotation, d_scaling = self.deform.deformed_points(pts.detach(), times)
+            else:
+                d_xyz, d_rotation, d_scaling = self.deform(pts.detach(), times)
+                means = transform_points(d_xyz, pts)  # (:840-843; not torch.bmm: utils.small_bmm)
         return self._render(means, d_rotation, d_scaling, viewmat, K, W, H)
 
     @torch.no_grad()
@@ -586,7 +590,10 @@ class FreeGaussianControlModel(FreeGaussianModel):
         else:
             with torch.no_grad():  # (:128-138)
                 def deformed(t):
-                    T, _, _ = self.deform(pts, t.to(self.device).expand(pts.shape[0], -1))
+                    t = t.to(self.device).expand(pts.shape[0], -1)
+                    if fused_applies(self.deform, pts, t):
+                        return self.deform.deformed_points(pts, t)[0]
+                    T, _, _ = self.deform(pts, t)
                     return transform_points(T, pts)
 
                 delta = deformed(camera.times) - deformed(self.init_camera.times)

@@ -1259,6 +1259,81 @@ def knn(x: torch.Tensor, k: int = 3, squared: bool = False) -> Tuple[torch.Tenso
     return (d2 if squared else d2.sqrt()), idx
 
 
+MLP_ROW_TILE = _lib.MLP_ROW_TILE  # rows of one workgroup of fg_mlp_fwd (tests place their sizes around it)
+_MLP_OUT_COLS = {"se3": ((4, 4), (4,), (3,), (3,)), "plain": None}
+
+
+@torch.no_grad()
+def mlp_forward(x: torch.Tensor, aux: torch.Tensor, trunk, heads, mode: str = "se3", outs=None):
+    """Fused fp32 forward of the deformation / control MLP (``fg_mlp_fwd``): per row
+    ``[posenc(x, 10), aux]`` -> 8 linears of 256 with ReLU and the skip after layer 4 -> the head linears in one call of two launches (the weights
+    re-ordered into scratch, then the whole network), no activation in global memory.  Inference only: nothing here is recorded for autograd.
+
+    ``x`` [N,3]; ``aux`` [N,A] or one row [1,A] (or any tensor whose row stride is 0) for all, 1 <= A <= 64;
+    ``trunk``: the 8 ``nn.Linear`` (or ``(weight, bias)`` pairs); ``heads``: the head linears in output order.
+    ``mode="se3"``: heads (w, v, rotation, scaling) -> ``[d_xyz [N,4,4], d_rot [N,4], d_scale [N,3], pts [N,3]]``
+    (``pts`` = the transform applied to ``x``); ``mode="plain"``: one ``[N, rows]`` array per head.
+    ``outs``: one entry per output -- ``None`` allocates it, a tensor is written in place, ``False`` leaves it out (the
+    returned list holds ``None`` there)."""
+    if mode not in _MLP_OUT_COLS:
+        raise ValueError(f"mlp_forward: unknown mode {mode!r}")
+    if x.dim() != 2 or x.shape[1] != 3:
+        raise ValueError(f"mlp_forward wants [N,3] points, got {tuple(x.shape)}")
+    pairs = [(m.weight, m.bias) if hasattr(m, "weight") else tuple(m) for m in trunk]
+    hpairs = [(m.weight, m.bias) if hasattr(m, "weight") else tuple(m) for m in heads]
+    if len(pairs) != 8 or not 1 <= len(hpairs) <= _lib.MLP_MAX_HEADS:
+        raise ValueError(f"mlp_forward wants 8 trunk layers and 1..{_lib.MLP_MAX_HEADS} heads, got {len(pairs)} and {len(hpairs)}")
+    N = x.shape[0]
+    if aux.dim() != 2 or aux.shape[0] not in (1, N) or not 1 <= aux.shape[1] <= 64:
+        raise ValueError(f"mlp_forward wants aux [N or 1, 1..64], got {tuple(aux.shape)} for N = {N}")
+    xf = _f32(x.detach(), "x")
+    broadcast = aux.shape[0] == 1 or aux.stride(0) == 0
+    af = _f32(aux.detach()[:1] if broadcast else aux.detach(), "aux")
+    A, in_ch, width = af.shape[1], 63 + af.shape[1], pairs[0][0].shape[0]
+    keep = [xf, af]  # (contiguous copies stay alive until the call is enqueued)
+    d = _lib.MlpDesc()
+    d.size, d.mode = ctypes.sizeof(_lib.MlpDesc), _lib.MLP_SE3 if mode == "se3" else _lib.MLP_PLAIN
+    d.depth, d.width, d.multires, d.aux_width, d.n_heads = len(pairs), width, 10, A, len(hpairs)
+    d.aux_stride = 0 if broadcast else A
+    d.x, d.aux = xf.data_ptr(), af.data_ptr()
+    for i, (w, b) in enumerate(pairs):
+        want = (width, in_ch if i == 0 else (in_ch + width if i == 5 else width))
+        if b is None or tuple(w.shape) != want or tuple(b.shape) != (width,):
+            raise ValueError(f"mlp_forward: trunk layer {i} wants weight {want} and a bias, got {tuple(w.shape)}")
+        w, b = _f32(w.detach(), "weight"), _f32(b.detach(), "bias")
+        keep += [w, b]
+        d.weight[i], d.bias[i] = w.data_ptr(), b.data_ptr()
+    cols = []
+    for i, (w, b) in enumerate(hpairs):
+        if b is None or w.dim() != 2 or w.shape[1] != width or tuple(b.shape) != (w.shape[0],):
+            raise ValueError(f"mlp_forward: head {i} wants weight [rows, {width}] and a bias, got {tuple(w.shape)}")
+        w, b = _f32(w.detach(), "head weight"), _f32(b.detach(), "head bias")
+        keep += [w, b]
+        d.head_weight[i], d.head_bias[i], d.head_rows[i] = w.data_ptr(), b.data_ptr(), w.shape[0]
+        cols.append((w.shape[0],))
+    shapes = _MLP_OUT_COLS[mode] or tuple(cols)
+    outs = [None] * len(shapes) if outs is None else list(outs)
+    if len(outs) != len(shapes):
+        raise ValueError(f"mlp_forward: mode {mode!r} with {len(hpairs)} heads has {len(shapes)} outputs, got {len(outs)}")
+    result = []
+    for i, (o, shape) in enumerate(zip(outs, shapes)):
+        if o is False:
+            result.append(None)
+            continue
+        if o is None:
+            o = torch.empty(N, *shape, dtype=torch.float32, device=xf.device)
+        elif not (o.is_cuda and o.dtype == torch.float32 and o.is_contiguous() and tuple(o.shape) == (N, *shape)):
+            raise ValueError(f"mlp_forward: output {i} wants a contiguous CUDA float32 {(N, *shape)}")
+        d.out[i] = o.data_ptr()
+        result.append(o)
+    if N == 0:
+        return result
+    with torch.cuda.device(xf.device):
+        ws = torch.empty(int(_lib.load().fg_mlp_workspace_bytes(N)), dtype=torch.uint8, device=xf.device)
+        _call("fg_mlp_fwd", N, ctypes.addressof(d), _ptr(ws), ws.numel(), _stream())
+    return result
+
+
 # --------------------------------------------------------------------------------------------
 # K5 / K6 compositing
 

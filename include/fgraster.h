@@ -44,7 +44,7 @@ typedef void* fg_stream_t;
 #define FG_MAX_CHANNELS 8    /* composited feature channels per splat (RGB, depth, flow, ...) */
 #define FG_SPLAT_FLOATS 16   /* one 64-byte record per Gaussian, see fg_pack_splats */
 #define FG_SH_JAC_FLOATS 10  /* per-Gaussian note of the SH colour for the backward, see fg_preprocess_fwd */
-#define FG_ABI_VERSION 10
+#define FG_ABI_VERSION 11
 #define FG_COUNT_OUT_WORDS 16 /* int64 words of a count_out block (fg_stbin_count, fg_step_io): ABI 9 */
 
 int fg_abi_version(void);
@@ -791,6 +791,47 @@ int fg_adam_step_multi(int count, const fg_adam_tensor* tensors, fg_stream_t str
 size_t fg_knn_workspace_bytes(int64_t n);
 int fg_knn(int64_t n, const float* xyz, int k, float* dist2_out, int32_t* idx_out, void* workspace,
            size_t workspace_bytes, fg_stream_t stream);
+
+/* ---- K10 (ABI 11): fused fp32 FORWARD of the deformation / control MLP (inference; training keeps the library GEMMs):
+ * one call, two launches (the weights re-ordered into the workspace, then the network).
+ * Per row: [posenc(x, 10) (63 wide, computed in the kernel with the accurate sin / cos), aux (aux_width wide)] -> 8 linears
+ * of 256 with ReLU, the input row re-injected IN FRONT of h after layer 4 (layer 5's weight is [256, in_ch + 256]) -> up
+ * to FG_MLP_MAX_HEADS head linears of together <= 16 rows over the final h.  Weights and biases as nn.Linear stores them
+ * ([out, in] row-major).  aux[N, aux_width] has a row stride in floats; stride 0 = one row for all.  Products run on the
+ * exact-fp32 matrix instructions: every output element is one fmaf chain over its own row in a fixed order, so a row's
+ * result does not depend on the other rows or on its place; no atomics.
+ *   FG_MLP_SE3   heads (3, 3, 4, 3) = (w, v, rotation, scaling): theta = |w|, screw = (w / theta + 1e-5, v / theta + 1e-5),
+ *                out[0] = exp_se3 [N,4,4] (bottom row 0,0,0,1), out[1] = rotation [N,4], out[2] = scaling [N,3],
+ *                out[3] = the transform applied to x [N,3]
+ *   FG_MLP_PLAIN out[h] = head h [N, head_rows[h]]
+ * Every out[] pointer is nullable (that array is not written).  The workspace receives a re-ordered copy of the weights in
+ * the same call (about 2 MB read and written, nothing kept between calls); 16-byte aligned, fg_mlp_workspace_bytes(N)
+ * bytes (FG_ERR_WORKSPACE below that).  N == 0 does nothing.  FG_ERR_INVALID_ARG: a null required pointer, aux_width
+ * outside 1..64, head rows outside 1..16 (or more than 16 together, or not (3,3,4,3) in SE(3) mode), an unknown mode;
+ * FG_ERR_UNSUPPORTED: depth / width / multires other than 8 / 256 / 10.  Asynchronous and capturable in a graph. */
+#define FG_MLP_ROW_TILE 64 /* rows per workgroup */
+#define FG_MLP_MAX_HEADS 4
+#define FG_MLP_SE3 0
+#define FG_MLP_PLAIN 1
+typedef struct fg_mlp_desc {
+  int32_t size; /* sizeof(fg_mlp_desc) */
+  int32_t mode;
+  int32_t depth, width, multires;
+  int32_t aux_width;
+  int32_t n_heads;
+  int32_t head_rows[FG_MLP_MAX_HEADS];
+  int32_t reserved;
+  int64_t aux_stride;
+  const float* x;   /* [N,3] */
+  const float* aux; /* [N or 1, aux_width] */
+  const float* weight[8];
+  const float* bias[8];
+  const float* head_weight[FG_MLP_MAX_HEADS];
+  const float* head_bias[FG_MLP_MAX_HEADS];
+  float* out[FG_MLP_MAX_HEADS];
+} fg_mlp_desc;
+size_t fg_mlp_workspace_bytes(int64_t N);
+int fg_mlp_fwd(int64_t N, const fg_mlp_desc* desc, void* workspace, size_t workspace_bytes, fg_stream_t stream);
 
 #ifdef __cplusplus
 }
