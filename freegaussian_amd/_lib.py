@@ -104,16 +104,26 @@ SIGNATURES = {
     "fg_knn": (c_int, [c_int64, P, c_int, P, P, P, c_size_t, P]),
     "fg_mlp_workspace_bytes": (c_size_t, [c_int64]),
     "fg_mlp_fwd": (c_int, [c_int64, P, P, c_size_t, P]),  # (N, const fg_mlp_desc*, workspace, bytes, stream)
+    "fg_mlp_train_workspace_bytes": (c_size_t, [c_int64]),
+    "fg_mlp_train_fwd": (c_int, [c_int64, P, P, P, P, P, c_size_t, P]),  # (N, desc, heads, enc, acts, workspace, bytes, stream)
+    "fg_mlp_bwd": (c_int, [c_int64, P, P, P, P, P, c_size_t, P]),  # (N, desc, g_heads, acts, g_pre, workspace, bytes, stream)
 }  # fmt: skip
 
 # test hooks, not declared in the public header
 _EXTRA = {"fg_debug_wave_reduce16": (c_int, [P, P, P]), "fg_debug_knn_grid": (c_int, [c_int64, P, c_int, P, P])}
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 KNN_MAX_K = 8  # FG_KNN_MAX_K
 MLP_ROW_TILE = 64  # FG_MLP_ROW_TILE
 MLP_MAX_HEADS = 4  # FG_MLP_MAX_HEADS
 MLP_SE3, MLP_PLAIN = 0, 1  # FG_MLP_SE3, FG_MLP_PLAIN
+
+
+def mlp_enc_width(aux_width: int) -> int:
+    """FG_MLP_ENC_WIDTH: floats of one encoded input row as fg_mlp_train_fwd stores it (padded to a multiple of 8)."""
+    return (63 + aux_width + 7) // 8 * 8
+
+
 STBIN_LONG_SEGMENTS = 1  # FG_STBIN_LONG_SEGMENTS
 STBIN_TEST_SMALL_SLABS = 4  # FG_STBIN_TEST_SMALL_SLABS (tests: the sample sort's overflow path)
 STEP_NO_FOOTPRINT_MASKS = 2  # FG_STEP_NO_FOOTPRINT_MASKS

@@ -22,6 +22,16 @@
 //   heads    : <= 16 output rows over the final h, v_mfma_f32_16x16x4_f32, one 16-row block per wave
 //   epilogue : one lane per row: exp_se3 + the transform of x (SE(3) mode) or plain stores
 // Plain C++ stores only; no atomics; the result is deterministic.
+//
+// Training (fg_mlp_train_fwd / fg_mlp_bwd) is the same tile twice more:
+//   forward  : mlp_fwd_kernel<true> -- the code above, which also stores the encoded input row, each layer's post-ReLU
+//              tile (from the accumulators, as it goes to LDS) and the raw heads.  Same k order, same chains.
+//   backward : mlp_bwd_kernel -- the data chain g(h_7) = g_heads W_h, P_l = g(h_l) where h_l > 0, g(h_{l-1}) = P_l W_l[:, hidden],
+//              l = 7 .. 0, through the same mlp_gemm_part: the gradient tile sits in LDS where the activations sat, the mask
+//              comes from the saved activations, and every P_l tile is stored once.  The reduction runs over a layer's OUTPUT
+//              index, so the weights are packed a second way: Tp[g][k][e] = W[8 g + e][first hidden column + k].
+//              Nothing flows to the input row (layer 0, the input columns of layer 5): the inputs want no gradient.
+//              The weight gradients are [256, N] x [N, 256] products over all tiles: the caller's.
 #include <cmath>
 
 #include "fg_common.h"
@@ -67,6 +77,12 @@ inline MlpLayout mlp_layout(int A) {
   L.total = at;
   return L;
 }
+
+// the backward's packed workspace: the hidden columns of layers 1..7, then the heads as two k-groups ([16 head rows] x 256)
+constexpr int MLP_T_LAYER_FLOATS = (MLP_W / 8) * MLP_GROUP_FLOATS;
+constexpr size_t MLP_T_HEAD = (size_t)(MLP_D - 1) * MLP_T_LAYER_FLOATS;
+constexpr size_t MLP_T_TOTAL = MLP_T_HEAD + 2 * MLP_GROUP_FLOATS;
+constexpr int MLP_GH_STRIDE = 16 + 4;  // the head cotangents of a tile in LDS
 
 struct MlpArgs {
   const float* x;
@@ -126,6 +142,28 @@ mlp_pack_kernel(MlpArgs p, MlpLayout L, float* __restrict__ ws) {
     }
   } else {
     r = W[(size_t)j * MLP_W + 8 * g + e];
+  }
+  ws[at] = r;
+}
+
+// the backward's weights: Tp[l - 1][g][k][e] = W_l[8 g + e][off_l + k] (off_5 = in_ch, else 0), heads: Tp[g][k][e] = W_h[8 g + e][k]
+__global__ void __launch_bounds__(MLP_BLOCK)
+mlp_pack_t_kernel(MlpArgs p, float* __restrict__ ws) {
+  const size_t at = (size_t)blockIdx.x * MLP_BLOCK + threadIdx.x;
+  if (at >= MLP_T_TOTAL) return;
+  const int in_ch = MLP_XCH + p.A;
+  const size_t rel = at < MLP_T_HEAD ? at % MLP_T_LAYER_FLOATS : at - MLP_T_HEAD;
+  const int j = 8 * (int)(rel / MLP_GROUP_FLOATS) + (int)(rel % 8), k = (int)(rel % MLP_GROUP_FLOATS) / 8;
+  float r = 0.f;
+  if (at < MLP_T_HEAD) {
+    const int l = 1 + (int)(at / MLP_T_LAYER_FLOATS);
+    r = l == MLP_SKIP + 1 ? p.W[l][(size_t)j * (in_ch + MLP_W) + in_ch + k] : p.W[l][(size_t)j * MLP_W + k];
+  } else {
+    int v = 0;
+    for (int h = 0; h < p.n_heads; ++h) {
+      if (j >= v && j < v + p.head_rows[h]) r = p.head_W[h][(j - v) * MLP_W + k];
+      v += p.head_rows[h];
+    }
   }
   ws[at] = r;
 }
@@ -192,8 +230,17 @@ __device__ __forceinline__ void mlp_se3_row(const float* hd, const float* x, int
     for (int i = 0; i < 3; ++i) d[row * 3 + i] = T[i][0] * x[0] + T[i][1] * x[1] + T[i][2] * x[2] + T[i][3];
 }
 
+// what the training forward stores besides (fg_mlp_train_fwd)
+struct MlpSaved {
+  float* heads;  // [N, rows_total]
+  float* enc;    // [N, 8 g0]
+  float* acts;   // [8, N, 256]
+  int rows_total;
+};
+
+template <bool TRAIN>
 __global__ void __launch_bounds__(MLP_BLOCK)
-mlp_fwd_kernel(int64_t N, MlpArgs p, MlpLayout L, const float* __restrict__ ws) {
+mlp_fwd_kernel(int64_t N, MlpArgs p, MlpLayout L, const float* __restrict__ ws, MlpSaved sv) {
   __shared__ __attribute__((aligned(16))) float act[MLP_M * MLP_ACT_STRIDE];
   __shared__ __attribute__((aligned(16))) float inp[MLP_M * MLP_IN_STRIDE];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -224,6 +271,13 @@ mlp_fwd_kernel(int64_t N, MlpArgs p, MlpLayout L, const float* __restrict__ ws) 
     for (int k = MLP_XCH + p.A + q; k < 8 * L.g0; k += 4) dst[k] = 0.f;
   }
   __syncthreads();
+  if (TRAIN) {  // the encoded rows, zero pad included: consecutive lanes, consecutive floats
+    const int w = 8 * L.g0;
+    for (int i = tid; i < MLP_M * w; i += MLP_BLOCK) {
+      const int r = i / w, k = i % w;
+      if (row0 + r < N) sv.enc[(row0 + r) * w + k] = inp[r * MLP_IN_STRIDE + k];
+    }
+  }
 
   // ---- trunk
   const int li = lane & 31, lh = lane >> 5;
@@ -253,7 +307,9 @@ mlp_fwd_kernel(int64_t N, MlpArgs p, MlpLayout L, const float* __restrict__ ws) 
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
           const int r = 32 * rb + (e & 3) + 8 * (e >> 2) + 4 * lh;
-          act[r * MLP_ACT_STRIDE + wave * 64 + 32 * cb + li] = fmaxf(acc[rb][cb][e], 0.f);
+          const float h = fmaxf(acc[rb][cb][e], 0.f);
+          act[r * MLP_ACT_STRIDE + wave * 64 + 32 * cb + li] = h;
+          if (TRAIN && row0 + r < N) sv.acts[((int64_t)l * N + row0 + r) * MLP_W + wave * 64 + 32 * cb + li] = h;
         }
     __syncthreads();
   }
@@ -282,7 +338,9 @@ mlp_fwd_kernel(int64_t N, MlpArgs p, MlpLayout L, const float* __restrict__ ws) 
     const float* src = inp + tid * MLP_IN_STRIDE;
     float hd[16];
     for (int o = 0; o < 16; ++o) hd[o] = src[MLP_HEAD_COL + o];
-    if (p.mode == FG_MLP_SE3) {
+    if (TRAIN) {
+      for (int o = 0; o < sv.rows_total; ++o) sv.heads[row * sv.rows_total + o] = hd[o];
+    } else if (p.mode == FG_MLP_SE3) {
       const float x[3] = {src[0], src[1], src[2]};
       mlp_se3_row(hd, x, row, p);
     } else {
@@ -297,16 +355,60 @@ mlp_fwd_kernel(int64_t N, MlpArgs p, MlpLayout L, const float* __restrict__ ws) 
   }
 }
 
-}  // namespace
+__global__ void __launch_bounds__(MLP_BLOCK)
+mlp_bwd_kernel(int64_t N, int rows_total, const float* __restrict__ g_heads, const float* __restrict__ acts,
+               float* __restrict__ g_pre, const float* __restrict__ ws) {
+  __shared__ __attribute__((aligned(16))) float grad[MLP_M * MLP_ACT_STRIDE];
+  __shared__ __attribute__((aligned(16))) float gh[MLP_M * MLP_GH_STRIDE];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t row0 = (int64_t)blockIdx.x * MLP_M;
 
-extern "C" size_t fg_mlp_workspace_bytes(int64_t N) {
-  // (the packed weights alone: the same for every N; sized for the widest input row)
-  return N < 0 ? 0 : mlp_layout(64).total * sizeof(float);
+  // ---- the head cotangents: [64][16], zero beyond rows_total and beyond N
+  for (int i = tid; i < MLP_M * 16; i += MLP_BLOCK) {
+    const int r = i >> 4, o = i & 15;
+    gh[r * MLP_GH_STRIDE + o] = (row0 + r < N && o < rows_total) ? g_heads[(row0 + r) * rows_total + o] : 0.f;
+  }
+  __syncthreads();
+
+  const int li = lane & 31, lh = lane >> 5;
+  const float* a_grad = grad + li * MLP_ACT_STRIDE + 4 * lh;
+  const size_t b_lane = (size_t)(wave * 64 + li) * 8 + 4 * lh;
+  f32x16 acc[2][2];
+  for (int rb = 0; rb < 2; ++rb)
+    for (int cb = 0; cb < 2; ++cb)
+      for (int e = 0; e < 16; ++e) acc[rb][cb][e] = 0.f;
+  mlp_gemm_part(acc, gh + li * MLP_GH_STRIDE + 4 * lh, MLP_GH_STRIDE, 2, ws + MLP_T_HEAD + b_lane);  // g(h_7)
+  for (int l = MLP_D - 1; l >= 0; --l) {
+    // P_l = g(h_l) where h_l > 0: to g_pre and, for the next product, in place of the previous tile
+    const float* h = acts + (int64_t)l * N * MLP_W;
+    float* out = g_pre + (int64_t)l * N * MLP_W;
+    for (int rb = 0; rb < 2; ++rb)
+      for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+          const int r = 32 * rb + (e & 3) + 8 * (e >> 2) + 4 * lh, c = wave * 64 + 32 * cb + li;
+          const bool live = row0 + r < N;
+          const float v = live && h[(row0 + r) * MLP_W + c] > 0.f ? acc[rb][cb][e] : 0.f;
+          if (live) out[(row0 + r) * MLP_W + c] = v;
+          acc[rb][cb][e] = v;
+        }
+    if (l == 0) break;
+    __syncthreads();  // every wave has read the whole of the tile behind (l = 7: nothing to wait for, one barrier)
+    for (int rb = 0; rb < 2; ++rb)
+      for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+          const int r = 32 * rb + (e & 3) + 8 * (e >> 2) + 4 * lh;
+          grad[r * MLP_ACT_STRIDE + wave * 64 + 32 * cb + li] = acc[rb][cb][e];
+          acc[rb][cb][e] = 0.f;
+        }
+    __syncthreads();
+    mlp_gemm_part(acc, a_grad, MLP_ACT_STRIDE, MLP_W / 8, ws + (size_t)(l - 1) * MLP_T_LAYER_FLOATS + b_lane);  // g(h_{l-1})
+  }
 }
 
-extern "C" int fg_mlp_fwd(int64_t N, const fg_mlp_desc* d, void* workspace, size_t workspace_bytes, fg_stream_t stream) {
-  if (N < 0) return FG_ERR_INVALID_ARG;
-  if (N == 0) return FG_OK;
+// the descriptor checks every entry point shares; `inputs`: x and aux are read
+int mlp_check_desc(const fg_mlp_desc* d, bool inputs) {
   if (!d || d->size != (int32_t)sizeof(fg_mlp_desc)) return FG_ERR_INVALID_ARG;
   if (d->aux_width < 1 || d->aux_width > 64 || d->aux_stride < 0) return FG_ERR_INVALID_ARG;
   if (d->mode != FG_MLP_SE3 && d->mode != FG_MLP_PLAIN) return FG_ERR_INVALID_ARG;
@@ -321,16 +423,24 @@ extern "C" int fg_mlp_fwd(int64_t N, const fg_mlp_desc* d, void* workspace, size
       (d->n_heads != 4 || d->head_rows[0] != 3 || d->head_rows[1] != 3 || d->head_rows[2] != 4 || d->head_rows[3] != 3))
     return FG_ERR_INVALID_ARG;
   if (d->depth != MLP_D || d->width != MLP_W || d->multires != MLP_FREQS) return FG_ERR_UNSUPPORTED;
-  if (!d->x || !d->aux || !workspace) return FG_ERR_INVALID_ARG;
+  if (inputs && (!d->x || !d->aux)) return FG_ERR_INVALID_ARG;
   for (int l = 0; l < MLP_D; ++l)
     if (!d->weight[l] || !d->bias[l]) return FG_ERR_INVALID_ARG;
   for (int h = 0; h < d->n_heads; ++h)
     if (!d->head_weight[h] || !d->head_bias[h]) return FG_ERR_INVALID_ARG;
-  if (N > ((int64_t)1 << 31) * MLP_M - MLP_M) return FG_ERR_INVALID_ARG;  // (the grid's x extent)
-  const MlpLayout L = mlp_layout(d->aux_width);
-  if (workspace_bytes < fg_mlp_workspace_bytes(N)) return FG_ERR_WORKSPACE;  // (the documented size, whatever aux_width)
-  if (reinterpret_cast<uintptr_t>(workspace) % 16) return FG_ERR_INVALID_ARG;
+  return FG_OK;
+}
 
+// (N > 0) the grid's x extent, then the workspace: present, the documented size, 16-byte aligned
+int mlp_check_launch(int64_t N, const void* workspace, size_t workspace_bytes, size_t need) {
+  if (!workspace) return FG_ERR_INVALID_ARG;
+  if (N > ((int64_t)1 << 31) * MLP_M - MLP_M) return FG_ERR_INVALID_ARG;
+  if (workspace_bytes < need) return FG_ERR_WORKSPACE;
+  if (reinterpret_cast<uintptr_t>(workspace) % 16) return FG_ERR_INVALID_ARG;
+  return FG_OK;
+}
+
+MlpArgs mlp_args(const fg_mlp_desc* d) {
   MlpArgs p = {};
   p.x = d->x, p.aux = d->aux, p.aux_stride = d->aux_stride;
   for (int l = 0; l < MLP_D; ++l) p.W[l] = d->weight[l], p.b[l] = d->bias[l];
@@ -339,11 +449,72 @@ extern "C" int fg_mlp_fwd(int64_t N, const fg_mlp_desc* d, void* workspace, size
     p.out[h] = d->out[h];
   }
   p.n_heads = d->n_heads, p.A = d->aux_width, p.mode = d->mode;
+  return p;
+}
+
+// pack, then the network: the two launches of fg_mlp_fwd and fg_mlp_train_fwd
+template <bool TRAIN>
+int mlp_launch_fwd(int64_t N, const MlpArgs& p, const MlpSaved& sv, void* workspace, fg_stream_t stream) {
+  const MlpLayout L = mlp_layout(p.A);
   hipStream_t s = fg_hip_stream(stream);
   float* ws = static_cast<float*>(workspace);
   hipLaunchKernelGGL(mlp_pack_kernel, dim3((unsigned)((L.total + MLP_BLOCK - 1) / MLP_BLOCK)), dim3(MLP_BLOCK), 0, s, p, L, ws);
   FG_RETURN_IF_LAUNCH_FAILED();
-  hipLaunchKernelGGL(mlp_fwd_kernel, dim3((unsigned)((N + MLP_M - 1) / MLP_M)), dim3(MLP_BLOCK), 0, s, N, p, L, ws);
+  hipLaunchKernelGGL(mlp_fwd_kernel<TRAIN>, dim3((unsigned)((N + MLP_M - 1) / MLP_M)), dim3(MLP_BLOCK), 0, s, N, p, L, ws, sv);
+  FG_RETURN_IF_LAUNCH_FAILED();
+  return FG_OK;
+}
+
+}  // namespace
+
+extern "C" size_t fg_mlp_workspace_bytes(int64_t N) {
+  // (the packed weights alone: the same for every N; sized for the widest input row)
+  return N < 0 ? 0 : mlp_layout(64).total * sizeof(float);
+}
+
+extern "C" int fg_mlp_fwd(int64_t N, const fg_mlp_desc* d, void* workspace, size_t workspace_bytes, fg_stream_t stream) {
+  if (N < 0) return FG_ERR_INVALID_ARG;
+  if (N == 0) return FG_OK;
+  if (int rc = mlp_check_desc(d, true)) return rc;
+  // (the documented size, whatever aux_width)
+  if (int rc = mlp_check_launch(N, workspace, workspace_bytes, fg_mlp_workspace_bytes(N))) return rc;
+  return mlp_launch_fwd<false>(N, mlp_args(d), MlpSaved{}, workspace, stream);
+}
+
+extern "C" size_t fg_mlp_train_workspace_bytes(int64_t N) {
+  // (one size for both calls: the larger of the forward's and the backward's packed weights; the same for every N)
+  const size_t fwd = fg_mlp_workspace_bytes(N), bwd = MLP_T_TOTAL * sizeof(float);
+  return N < 0 ? 0 : (fwd > bwd ? fwd : bwd);
+}
+
+extern "C" int fg_mlp_train_fwd(int64_t N, const fg_mlp_desc* d, float* heads, float* enc, float* acts, void* workspace,
+                                size_t workspace_bytes, fg_stream_t stream) {
+  if (N < 0) return FG_ERR_INVALID_ARG;
+  if (N == 0) return FG_OK;
+  if (int rc = mlp_check_desc(d, true)) return rc;
+  if (d->mode != FG_MLP_PLAIN || !heads || !enc || !acts) return FG_ERR_INVALID_ARG;
+  if (int rc = mlp_check_launch(N, workspace, workspace_bytes, fg_mlp_train_workspace_bytes(N))) return rc;
+  MlpSaved sv = {heads, enc, acts, 0};
+  for (int h = 0; h < d->n_heads; ++h) sv.rows_total += d->head_rows[h];
+  return mlp_launch_fwd<true>(N, mlp_args(d), sv, workspace, stream);
+}
+
+extern "C" int fg_mlp_bwd(int64_t N, const fg_mlp_desc* d, const float* g_heads, const float* acts, float* g_pre,
+                          void* workspace, size_t workspace_bytes, fg_stream_t stream) {
+  if (N < 0) return FG_ERR_INVALID_ARG;
+  if (N == 0) return FG_OK;
+  if (int rc = mlp_check_desc(d, false)) return rc;
+  if (d->mode != FG_MLP_PLAIN || !g_heads || !acts || !g_pre) return FG_ERR_INVALID_ARG;
+  if (int rc = mlp_check_launch(N, workspace, workspace_bytes, fg_mlp_train_workspace_bytes(N))) return rc;
+  const MlpArgs p = mlp_args(d);
+  int rows_total = 0;
+  for (int h = 0; h < d->n_heads; ++h) rows_total += d->head_rows[h];
+  hipStream_t s = fg_hip_stream(stream);
+  float* ws = static_cast<float*>(workspace);
+  hipLaunchKernelGGL(mlp_pack_t_kernel, dim3((unsigned)((MLP_T_TOTAL + MLP_BLOCK - 1) / MLP_BLOCK)), dim3(MLP_BLOCK), 0, s, p, ws);
+  FG_RETURN_IF_LAUNCH_FAILED();
+  hipLaunchKernelGGL(mlp_bwd_kernel, dim3((unsigned)((N + MLP_M - 1) / MLP_M)), dim3(MLP_BLOCK), 0, s, N, rows_total, g_heads, acts,
+                     g_pre, ws);
   FG_RETURN_IF_LAUNCH_FAILED();
   return FG_OK;
 }

@@ -1,6 +1,9 @@
 """Deformation / control MLPs that feed the rasterizer.  Training runs the dense GEMMs on PyTorch-ROCm / hipBLASLt
 (SURVEY.md §2 row 5); a forward that needs no gradient over at least ``FUSED_MIN_ROWS`` rows is one fused HIP call
-(``ops.mlp_forward``: a weight re-ordering launch and the network's launch; ``FG_FUSED_MLP=0`` turns it off).  Behaviour and ``state_dict`` key names follow the reference's
+(``ops.mlp_forward``: a weight re-ordering launch and the network's launch; ``FG_FUSED_MLP=0`` turns it off).
+With ``FG_FUSED_MLP_TRAIN=1`` (opt-in; unset = off) a taped forward over as many rows runs as ``ops.mlp_train``: the fused
+forward with saved activations, the fused backward data chain, and the weight gradients as chunked library products
+(``mlp_param_grads``).  Behaviour and ``state_dict`` key names follow the reference's
 ``FreeGaussianDeformableModel`` / ``FreeGaussianControllableModel``
 (freegaussian/freegaussian_model.py:1054-1145) so stage-1 checkpoints load unchanged; outputs are
 checked against golden vectors produced by the reference classes (tests/golden/g_mlp.npz)."""
@@ -20,6 +23,18 @@ def _trunk(in_ch: int, width: int, depth: int, skip_at: int) -> nn.ModuleList:
     for i in range(depth - 1):
         layers.append(nn.Linear(width + in_ch if i == skip_at else width, width))
     return nn.ModuleList(layers)
+
+
+def _tall_weight_grad(go: torch.Tensor, x: torch.Tensor, chunk: int = 8192) -> torch.Tensor:
+    """go^T x ([N,out], [N,in] -> [out,in]) as a batched product over chunks of `chunk` rows, a sum of the partial
+    matrices, and the product of the tail (see ``_TallLinear``)."""
+    N = x.shape[0]
+    B = N // chunk
+    n0 = B * chunk
+    gw = torch.bmm(go[:n0].view(B, chunk, go.shape[1]).transpose(1, 2), x[:n0].view(B, chunk, x.shape[1])).sum(0)
+    if n0 < N:
+        gw = gw + go[n0:].t() @ x[n0:]
+    return gw
 
 
 class _TallLinear(torch.autograd.Function):
@@ -43,12 +58,7 @@ class _TallLinear(torch.autograd.Function):
         gx = go @ weight if ctx.needs_input_grad[0] else None
         gw = None
         if ctx.needs_input_grad[1]:
-            N, C = x.shape[0], _TallLinear.CHUNK
-            B = N // C
-            n0 = B * C
-            gw = torch.bmm(go[:n0].view(B, C, -1).transpose(1, 2), x[:n0].view(B, C, -1)).sum(0)
-            if n0 < N:
-                gw = gw + go[n0:].t() @ x[n0:]
+            gw = _tall_weight_grad(go, x, _TallLinear.CHUNK)
         gb = go.sum(0) if ctx.needs_input_grad[2] else None
         return gx, gw, gb
 
@@ -99,6 +109,47 @@ def fused_applies(module: nn.Module, x: torch.Tensor, other: torch.Tensor) -> bo
     return True
 
 
+def fused_train_applies(module: nn.Module, x: torch.Tensor, other: torch.Tensor) -> bool:
+    """Whether a taped ``module(x, other)`` runs as one ``ops.mlp_train`` call: ``FG_FUSED_MLP_TRAIN=1`` (read here, on the
+    host, on every call; unset = off), grad mode on and a parameter that wants a gradient, inputs that want none, CUDA
+    fp32, enough rows, the one network shape the kernels are built for, and not the blender net (its ``timenet`` would
+    need the gradient of the encoded time, which the fused backward does not form).  Anything else: the torch ops."""
+    if os.environ.get("FG_FUSED_MLP_TRAIN", "0") != "1":
+        return False
+    if not torch.is_grad_enabled() or x.requires_grad or other.requires_grad:
+        return False
+    if not (x.is_cuda and other.is_cuda and x.dtype == other.dtype == torch.float32 and x.dim() == other.dim() == 2):
+        return False
+    other_ch = 3 if isinstance(module, FreeGaussianControllableModel) else 1
+    if x.shape[0] < FUSED_MIN_ROWS or other.shape[0] != x.shape[0] or x.shape[1] != 3 or other.shape[1] != other_ch:
+        return False
+    if (module.D, module.W, module.multires, module.skip_at) != (8, 256, 10, 4) or getattr(module, "is_blender", False):
+        return False
+    params = list(module.parameters())
+    return all(p.is_cuda and p.dtype == torch.float32 for p in params) and any(p.requires_grad for p in params)
+
+
+def mlp_param_grads(inp: torch.Tensor, H: torch.Tensor, G: torch.Tensor, g_heads: torch.Tensor, head_rows):
+    """The parameter gradients of the trunk and the heads from what the fused training calls leave behind (any device,
+    any float type): ``inp`` [N,in_ch] the encoded input rows, ``H`` [8,N,W] the post-ReLU activations, ``G`` [8,N,W] the
+    gradients of the pre-activations (``P_l`` of include/fgraster.h), ``g_heads`` [N, rows_total] the head cotangents.
+    Returns ``(gW x 8, gb x 8, gW_head per head, gb_head per head)``: ``gW_l = P_l^T in_l`` with ``in_l = h_{l-1}``,
+    ``in_0 = inp`` and ``in_5 = [inp, h_4]`` (two products side by side), every product chunked as ``_TallLinear``'s."""
+    C = _TallLinear.CHUNK
+    gW = []
+    for l in range(H.shape[0]):
+        if l == 0:
+            gW.append(_tall_weight_grad(G[0], inp, C))
+        elif l == H.shape[0] // 2 + 1:
+            gW.append(torch.cat([_tall_weight_grad(G[l], inp, C), _tall_weight_grad(G[l], H[l - 1], C)], dim=1))
+        else:
+            gW.append(_tall_weight_grad(G[l], H[l - 1], C))
+    gb = G.sum(1).unbind(0)
+    gWh = _tall_weight_grad(g_heads, H[-1], C).split(list(head_rows), dim=0)
+    gbh = g_heads.sum(0).split(list(head_rows))
+    return gW, gb, gWh, gbh
+
+
 def _one_row_if_broadcast(t: torch.Tensor) -> torch.Tensor:
     """``times.expand(N, -1)`` has row stride 0: its encoding is computed on one row and broadcast by the kernel."""
     return t[:1] if t.stride(0) == 0 else t
@@ -145,16 +196,27 @@ class FreeGaussianDeformableModel(nn.Module):
     def forward(self, x: torch.Tensor, t: torch.Tensor):
         if fused_applies(self, x, t):
             return tuple(self._fused(x, t, (None, None, None, False))[:3])
+        if fused_train_applies(self, x, t):
+            from . import ops
+
+            aux = positional_encoding(_one_row_if_broadcast(t), self.t_multires)
+            heads = (self.branch_w, self.branch_v, self.gaussian_rotation, self.gaussian_scaling)
+            w, v, rot, scale = ops.mlp_train(x, aux, self.linear, heads).split((3, 3, 4, 3), dim=-1)
+            return self._se3(w, v), rot, scale
         t_emb = positional_encoding(t, self.t_multires)
         if self.is_blender:
             t_emb = self.timenet(t_emb)
         inp = torch.cat([positional_encoding(x, self.multires), t_emb], dim=-1)
         h = _run_trunk(self.linear, inp, self.skip_at)
         w, v = _linear(self.branch_w, h), _linear(self.branch_v, h)
+        return self._se3(w, v), _linear(self.gaussian_rotation, h), _linear(self.gaussian_scaling, h)
+
+    @staticmethod
+    def _se3(w: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
         theta = w.norm(dim=-1, keepdim=True)
         # the reference adds 1e-5 AFTER the division (freegaussian_model.py:1106-1107)
         screw = torch.cat([w / theta + 1e-5, v / theta + 1e-5], dim=-1)
-        return exp_se3(screw, theta), _linear(self.gaussian_rotation, h), _linear(self.gaussian_scaling, h)
+        return exp_se3(screw, theta)
 
 
 class FreeGaussianControllableModel(nn.Module):
@@ -177,6 +239,11 @@ class FreeGaussianControllableModel(nn.Module):
             with torch.no_grad():
                 aux = positional_encoding(_one_row_if_broadcast(value), self.multires)
                 return tuple(ops.mlp_forward(x, aux, self.linear, (self.d_xyz, self.d_rot, self.d_scale), mode="plain"))
+        if fused_train_applies(self, x, value):
+            from . import ops
+
+            aux = positional_encoding(_one_row_if_broadcast(value), self.multires)
+            return ops.mlp_train(x, aux, self.linear, (self.d_xyz, self.d_rot, self.d_scale)).split((3, 4, 3), dim=-1)
         inp = torch.cat([positional_encoding(x, self.multires), positional_encoding(value, self.multires)], dim=-1)
         h = _run_trunk(self.linear, inp, self.skip_at)
         return _linear(self.d_xyz, h), _linear(self.d_rot, h), _linear(self.d_scale, h)

@@ -1263,6 +1263,52 @@ MLP_ROW_TILE = _lib.MLP_ROW_TILE  # rows of one workgroup of fg_mlp_fwd (tests p
 _MLP_OUT_COLS = {"se3": ((4, 4), (4,), (3,), (3,)), "plain": None}
 
 
+def _mlp_desc(who: str, x, aux, trunk, heads, mode: int):
+    """The ``fg_mlp_desc`` of one call (``who`` names the caller in the errors): ``(desc, N, head rows, tensors the desc
+    points into)``.  ``x`` / ``aux`` None: left null (``fg_mlp_bwd`` reads neither), ``aux`` then an int, the aux width."""
+    pairs = [(m.weight, m.bias) if hasattr(m, "weight") else tuple(m) for m in trunk]
+    hpairs = [(m.weight, m.bias) if hasattr(m, "weight") else tuple(m) for m in heads]
+    if len(pairs) != 8 or not 1 <= len(hpairs) <= _lib.MLP_MAX_HEADS:
+        raise ValueError(f"{who} wants 8 trunk layers and 1..{_lib.MLP_MAX_HEADS} heads, got {len(pairs)} and {len(hpairs)}")
+    d = _lib.MlpDesc()
+    keep = []  # (contiguous copies stay alive until the call is enqueued)
+    N = None
+    if x is None:
+        A = aux
+    else:
+        if x.dim() != 2 or x.shape[1] != 3:
+            raise ValueError(f"{who} wants [N,3] points, got {tuple(x.shape)}")
+        N = x.shape[0]
+        if aux.dim() != 2 or aux.shape[0] not in (1, N) or not 1 <= aux.shape[1] <= 64:
+            raise ValueError(f"{who} wants aux [N or 1, 1..64], got {tuple(aux.shape)} for N = {N}")
+        xf = _f32(x.detach(), "x")
+        broadcast = aux.shape[0] == 1 or aux.stride(0) == 0
+        af = _f32(aux.detach()[:1] if broadcast else aux.detach(), "aux")
+        A = af.shape[1]
+        keep += [xf, af]
+        d.aux_stride = 0 if broadcast else A
+        d.x, d.aux = xf.data_ptr(), af.data_ptr()
+    in_ch, width = 63 + A, pairs[0][0].shape[0]
+    d.size, d.mode = ctypes.sizeof(_lib.MlpDesc), mode
+    d.depth, d.width, d.multires, d.aux_width, d.n_heads = len(pairs), width, 10, A, len(hpairs)
+    for i, (w, b) in enumerate(pairs):
+        want = (width, in_ch if i == 0 else (in_ch + width if i == 5 else width))
+        if b is None or tuple(w.shape) != want or tuple(b.shape) != (width,):
+            raise ValueError(f"{who}: trunk layer {i} wants weight {want} and a bias, got {tuple(w.shape)}")
+        w, b = _f32(w.detach(), "weight"), _f32(b.detach(), "bias")
+        keep += [w, b]
+        d.weight[i], d.bias[i] = w.data_ptr(), b.data_ptr()
+    rows = []
+    for i, (w, b) in enumerate(hpairs):
+        if b is None or w.dim() != 2 or w.shape[1] != width or tuple(b.shape) != (w.shape[0],):
+            raise ValueError(f"{who}: head {i} wants weight [rows, {width}] and a bias, got {tuple(w.shape)}")
+        w, b = _f32(w.detach(), "head weight"), _f32(b.detach(), "head bias")
+        keep += [w, b]
+        d.head_weight[i], d.head_bias[i], d.head_rows[i] = w.data_ptr(), b.data_ptr(), w.shape[0]
+        rows.append(w.shape[0])
+    return d, N, rows, keep
+
+
 @torch.no_grad()
 def mlp_forward(x: torch.Tensor, aux: torch.Tensor, trunk, heads, mode: str = "se3", outs=None):
     """Fused fp32 forward of the deformation / control MLP (``fg_mlp_fwd``): per row
@@ -1277,61 +1323,88 @@ def mlp_forward(x: torch.Tensor, aux: torch.Tensor, trunk, heads, mode: str = "s
     returned list holds ``None`` there)."""
     if mode not in _MLP_OUT_COLS:
         raise ValueError(f"mlp_forward: unknown mode {mode!r}")
-    if x.dim() != 2 or x.shape[1] != 3:
-        raise ValueError(f"mlp_forward wants [N,3] points, got {tuple(x.shape)}")
-    pairs = [(m.weight, m.bias) if hasattr(m, "weight") else tuple(m) for m in trunk]
-    hpairs = [(m.weight, m.bias) if hasattr(m, "weight") else tuple(m) for m in heads]
-    if len(pairs) != 8 or not 1 <= len(hpairs) <= _lib.MLP_MAX_HEADS:
-        raise ValueError(f"mlp_forward wants 8 trunk layers and 1..{_lib.MLP_MAX_HEADS} heads, got {len(pairs)} and {len(hpairs)}")
-    N = x.shape[0]
-    if aux.dim() != 2 or aux.shape[0] not in (1, N) or not 1 <= aux.shape[1] <= 64:
-        raise ValueError(f"mlp_forward wants aux [N or 1, 1..64], got {tuple(aux.shape)} for N = {N}")
-    xf = _f32(x.detach(), "x")
-    broadcast = aux.shape[0] == 1 or aux.stride(0) == 0
-    af = _f32(aux.detach()[:1] if broadcast else aux.detach(), "aux")
-    A, in_ch, width = af.shape[1], 63 + af.shape[1], pairs[0][0].shape[0]
-    keep = [xf, af]  # (contiguous copies stay alive until the call is enqueued)
-    d = _lib.MlpDesc()
-    d.size, d.mode = ctypes.sizeof(_lib.MlpDesc), _lib.MLP_SE3 if mode == "se3" else _lib.MLP_PLAIN
-    d.depth, d.width, d.multires, d.aux_width, d.n_heads = len(pairs), width, 10, A, len(hpairs)
-    d.aux_stride = 0 if broadcast else A
-    d.x, d.aux = xf.data_ptr(), af.data_ptr()
-    for i, (w, b) in enumerate(pairs):
-        want = (width, in_ch if i == 0 else (in_ch + width if i == 5 else width))
-        if b is None or tuple(w.shape) != want or tuple(b.shape) != (width,):
-            raise ValueError(f"mlp_forward: trunk layer {i} wants weight {want} and a bias, got {tuple(w.shape)}")
-        w, b = _f32(w.detach(), "weight"), _f32(b.detach(), "bias")
-        keep += [w, b]
-        d.weight[i], d.bias[i] = w.data_ptr(), b.data_ptr()
-    cols = []
-    for i, (w, b) in enumerate(hpairs):
-        if b is None or w.dim() != 2 or w.shape[1] != width or tuple(b.shape) != (w.shape[0],):
-            raise ValueError(f"mlp_forward: head {i} wants weight [rows, {width}] and a bias, got {tuple(w.shape)}")
-        w, b = _f32(w.detach(), "head weight"), _f32(b.detach(), "head bias")
-        keep += [w, b]
-        d.head_weight[i], d.head_bias[i], d.head_rows[i] = w.data_ptr(), b.data_ptr(), w.shape[0]
-        cols.append((w.shape[0],))
-    shapes = _MLP_OUT_COLS[mode] or tuple(cols)
+    d, N, rows, keep = _mlp_desc("mlp_forward", x, aux, trunk, heads, _lib.MLP_SE3 if mode == "se3" else _lib.MLP_PLAIN)
+    dev = keep[0].device
+    shapes = _MLP_OUT_COLS[mode] or tuple((r,) for r in rows)
     outs = [None] * len(shapes) if outs is None else list(outs)
     if len(outs) != len(shapes):
-        raise ValueError(f"mlp_forward: mode {mode!r} with {len(hpairs)} heads has {len(shapes)} outputs, got {len(outs)}")
+        raise ValueError(f"mlp_forward: mode {mode!r} with {len(rows)} heads has {len(shapes)} outputs, got {len(outs)}")
     result = []
     for i, (o, shape) in enumerate(zip(outs, shapes)):
         if o is False:
             result.append(None)
             continue
         if o is None:
-            o = torch.empty(N, *shape, dtype=torch.float32, device=xf.device)
+            o = torch.empty(N, *shape, dtype=torch.float32, device=dev)
         elif not (o.is_cuda and o.dtype == torch.float32 and o.is_contiguous() and tuple(o.shape) == (N, *shape)):
             raise ValueError(f"mlp_forward: output {i} wants a contiguous CUDA float32 {(N, *shape)}")
         d.out[i] = o.data_ptr()
         result.append(o)
     if N == 0:
         return result
-    with torch.cuda.device(xf.device):
-        ws = torch.empty(int(_lib.load().fg_mlp_workspace_bytes(N)), dtype=torch.uint8, device=xf.device)
+    with torch.cuda.device(dev):
+        ws = torch.empty(int(_lib.load().fg_mlp_workspace_bytes(N)), dtype=torch.uint8, device=dev)
         _call("fg_mlp_fwd", N, ctypes.addressof(d), _ptr(ws), ws.numel(), _stream())
     return result
+
+
+class _MlpTrain(torch.autograd.Function):
+    """``fg_mlp_train_fwd`` / ``fg_mlp_bwd`` around the saved ``enc`` [N, padded in_ch] and ``H`` [8,N,256]; the inputs are
+    ``x``, ``aux``, the number of heads, then the 8 trunk weights, the 8 trunk biases, the head weights, the head biases."""
+
+    @staticmethod
+    def forward(ctx, x, aux, n_heads, *params):
+        trunk, heads = list(zip(params[:8], params[8:16])), list(zip(params[16 : 16 + n_heads], params[16 + n_heads :]))
+        d, N, rows, keep = _mlp_desc("mlp_train", x, aux, trunk, heads, _lib.MLP_PLAIN)
+        dev = keep[0].device
+        out = torch.empty(N, sum(rows), dtype=torch.float32, device=dev)
+        enc = torch.empty(N, _lib.mlp_enc_width(d.aux_width), dtype=torch.float32, device=dev)
+        H = torch.empty(8, N, d.width, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            ws = torch.empty(int(_lib.load().fg_mlp_train_workspace_bytes(N)), dtype=torch.uint8, device=dev)
+            _call("fg_mlp_train_fwd", N, ctypes.addressof(d), _ptr(out), _ptr(enc), _ptr(H), _ptr(ws), ws.numel(), _stream())
+        ctx.save_for_backward(enc, H, *params)
+        ctx.aux_width, ctx.head_rows = d.aux_width, rows
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_heads):
+        from .deform import mlp_param_grads
+
+        enc, H, *params = ctx.saved_tensors
+        n = len(ctx.head_rows)
+        trunk, heads = list(zip(params[:8], params[8:16])), list(zip(params[16 : 16 + n], params[16 + n :]))
+        d, _, rows, keep = _mlp_desc("mlp_train", None, ctx.aux_width, trunk, heads, _lib.MLP_PLAIN)
+        g_heads = _f32(g_heads, "g_heads")
+        N = g_heads.shape[0]
+        G = torch.empty_like(H)
+        with torch.cuda.device(G.device):
+            ws = torch.empty(int(_lib.load().fg_mlp_train_workspace_bytes(N)), dtype=torch.uint8, device=G.device)
+            _call("fg_mlp_bwd", N, ctypes.addressof(d), _ptr(g_heads), _ptr(H), _ptr(G), _ptr(ws), ws.numel(), _stream())
+        gW, gb, gWh, gbh = mlp_param_grads(enc[:, : 63 + ctx.aux_width], H, G, g_heads, rows)
+        grads = (*gW, *gb, *gWh, *gbh)
+        return (None, None, None, *(g if need else None for g, need in zip(grads, ctx.needs_input_grad[3:])))
+
+
+def mlp_train(x: torch.Tensor, aux: torch.Tensor, trunk, heads) -> torch.Tensor:
+    """The network of ``mlp_forward`` for training (``fg_mlp_train_fwd`` / ``fg_mlp_bwd``): the raw head outputs
+    ``[N, rows_total]`` (the heads side by side in the order given, bit for bit ``mlp_forward(mode="plain")``), recorded
+    for autograd.  The forward keeps the encoded input row and the eight post-ReLU activations (``[8,N,256]``); the
+    backward runs the hidden-activation chain in one fused call into a second ``[8,N,256]`` array and forms the parameter
+    gradients from the two (``deform.mlp_param_grads``: the chunked products of ``_TallLinear``).  ``x`` and ``aux`` get
+    no gradient.  CUDA float32 tensors, N >= 1; ``aux`` as for ``mlp_forward``.  No host synchronisation: capturable."""
+    trunk = [(m.weight, m.bias) if hasattr(m, "weight") else tuple(m) for m in trunk]
+    heads = [(m.weight, m.bias) if hasattr(m, "weight") else tuple(m) for m in heads]
+    if len(trunk) != 8 or not 1 <= len(heads) <= _lib.MLP_MAX_HEADS:
+        raise ValueError(f"mlp_train wants 8 trunk layers and 1..{_lib.MLP_MAX_HEADS} heads, got {len(trunk)} and {len(heads)}")
+    tensors = [x, aux, *(t for pair in (*trunk, *heads) for t in pair)]
+    if any(not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 for t in tensors):
+        raise ValueError("mlp_train wants CUDA float32 tensors (and a bias on every layer)")
+    if x.dim() != 2 or x.shape[0] < 1:
+        raise ValueError(f"mlp_train wants [N,3] points with N >= 1, got {tuple(x.shape)}")
+    params = [w for w, _ in trunk] + [b for _, b in trunk] + [w for w, _ in heads] + [b for _, b in heads]
+    return _MlpTrain.apply(x, aux, len(heads), *params)
 
 
 # --------------------------------------------------------------------------------------------

@@ -44,7 +44,7 @@ typedef void* fg_stream_t;
 #define FG_MAX_CHANNELS 8    /* composited feature channels per splat (RGB, depth, flow, ...) */
 #define FG_SPLAT_FLOATS 16   /* one 64-byte record per Gaussian, see fg_pack_splats */
 #define FG_SH_JAC_FLOATS 10  /* per-Gaussian note of the SH colour for the backward, see fg_preprocess_fwd */
-#define FG_ABI_VERSION 11
+#define FG_ABI_VERSION 12
 #define FG_COUNT_OUT_WORDS 16 /* int64 words of a count_out block (fg_stbin_count, fg_step_io): ABI 9 */
 
 int fg_abi_version(void);
@@ -832,6 +832,36 @@ typedef struct fg_mlp_desc {
 } fg_mlp_desc;
 size_t fg_mlp_workspace_bytes(int64_t N);
 int fg_mlp_fwd(int64_t N, const fg_mlp_desc* desc, void* workspace, size_t workspace_bytes, fg_stream_t stream);
+
+/* ---- K10 training (ABI 12): the same network with what a backward needs, and the backward's data chain.  Both take the
+ * descriptor of fg_mlp_fwd with mode = FG_MLP_PLAIN (FG_ERR_INVALID_ARG otherwise); desc->out is not read, and
+ * fg_mlp_bwd does not read desc->x / desc->aux.  rows_total = the sum of head_rows.  Trunk layers are 0-based:
+ * h_0 = relu(W_0 inp + b_0), h_l = relu(W_l in_l + b_l) with in_l = h_{l-1} except in_5 = [inp, h_4].
+ *   fg_mlp_train_fwd  the forward of fg_mlp_fwd (the same kernel tile, k order and fmaf chains: heads is bit for bit what
+ *                     FG_MLP_PLAIN writes), which also stores per row
+ *                       heads [N, rows_total]  the raw head outputs, packed in head order
+ *                       enc   [N, FG_MLP_ENC_WIDTH(aux_width)]  the encoded input row [posenc(x, 10), aux, 0 ...]
+ *                       acts  [8, N, 256]      the post-ReLU activations h_0 .. h_7
+ *   fg_mlp_bwd        from the head cotangents g_heads [N, rows_total] and acts: g(h_7) = g_heads W_h, then for l = 7 .. 0
+ *                       P_l = g(h_l) where h_l > 0, else 0 (the rule of the ReLU's backward), stored to g_pre [8, N, 256];
+ *                       g(h_{l-1}) = P_l W_l[:, hidden columns]  (l >= 1; layer 5's hidden columns are W_5[:, in_ch:])
+ *                     No gradient is formed for the input row (layer 0's input, layer 5's input columns): in training the
+ *                     network's inputs want none.  The parameter gradients are products of these arrays
+ *                     (gW_l = P_l^T in_l, gb_l = sum of P_l over the rows, gW_head = g_heads^T h_7), left to the caller.
+ *                     Every element of g_pre is one fmaf chain over its own row in a fixed order (64-row tiles on the exact
+ *                     fp32 matrix instructions, the gradient tile in place in shared memory): rows are independent and two
+ *                     runs are bit for bit equal; plain stores, no atomics.  A second re-ordered copy of the weights (the
+ *                     transpose of the forward's: the reduction runs over a layer's output index) is written into the
+ *                     workspace by a launch of the same call; nothing is kept between calls.
+ * Rows >= N of the last tile are neither read nor written.  The workspace: 16-byte aligned, fg_mlp_train_workspace_bytes(N)
+ * bytes for either call (FG_ERR_WORKSPACE below that).  N == 0 does nothing; error codes as fg_mlp_fwd.  Asynchronous and
+ * capturable in a graph. */
+#define FG_MLP_ENC_WIDTH(aux_width) ((63 + (aux_width) + 7) / 8 * 8)
+size_t fg_mlp_train_workspace_bytes(int64_t N);
+int fg_mlp_train_fwd(int64_t N, const fg_mlp_desc* desc, float* heads, float* enc, float* acts, void* workspace,
+                     size_t workspace_bytes, fg_stream_t stream);
+int fg_mlp_bwd(int64_t N, const fg_mlp_desc* desc, const float* g_heads, const float* acts, float* g_pre, void* workspace,
+               size_t workspace_bytes, fg_stream_t stream);
 
 #ifdef __cplusplus
 }

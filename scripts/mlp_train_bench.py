@@ -1,0 +1,312 @@
+#!/usr/bin/env python3
+"""Deformation-MLP training call (forward + backward to the parameter gradients): the fused path (``FG_FUSED_MLP_TRAIN=1``:
+``ops.mlp_train`` through the module's dispatch) against the torch path of the same module (the variable unset), which is
+what runs without this knob.  Writes profiles/mlp_train.md.
+
+    python scripts/mlp_train_bench.py [--trace] [--parity FILE] [--out DIR] [--md profiles/mlp_train.md]
+
+runs the steps below as child processes, each under its own ``timeout -k 10``, stopping at the first that fails (a
+fault or a time limit in one step starts nothing more on the GPU):
+
+    --step time    N = 33 000, 240 000, 1 000 000: the two paths ALTERNATE call by call in one process, 10 warm-up and
+                   50 timed calls each between device events; median, p10, p90; FLOPs per row from the layer shapes
+    --step error   both paths at N = 40 000 against a float64 run of the same module on the CPU (default init, one time
+                   per row): outputs and parameter gradients, the fused path's margin beside the torch fp32 path's own,
+                   over all rows and over the rows clear of the ReLU's kink (the tests' filter)
+    --step model   ``get_outputs`` + ``get_loss_dict`` + backward of a ``FreeGaussianModel`` in training mode behind
+                   ``warm_up``, knob on and off alternating: 240 000 random Gaussians at 960 x 540 (the half resolution
+                   of the reference's deform phase), the non-blender net (the blender net keeps the torch path)
+    --step trace   three fused calls at N = 240 000 for ``rocprofv3 --kernel-trace --stats`` (with --trace; a run of its own)
+    --step report  profiles/mlp_train.md from these; --parity: a ``FG_PARITY_REPORT`` file of tests/test_mlp_train_gpu.py,
+                   whose margins are quoted
+"""
+import argparse
+import copy
+import csv
+import glob
+import json
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+SIZES = (33_000, 240_000, 1_000_000)
+WARM, TIMED = 10, 50
+PEAK_TF = 157.0  # fp32 matrix peak of an MI355X
+KNOB = "FG_FUSED_MLP_TRAIN"
+
+
+def flops_per_row(m):
+    """Forward: 2 x in x out over every linear.  Backward: the same again for each weight gradient, and once more for the
+    data gradient of every linear whose input is an activation (not layer 0, not the input columns of layer 5)."""
+    fwd = data = 0
+    for i, layer in enumerate(m.linear):
+        fwd += 2 * layer.in_features * layer.out_features
+        data += 0 if i == 0 else 2 * m.W * layer.out_features
+    for head in (m.branch_w, m.branch_v, m.gaussian_rotation, m.gaussian_scaling):
+        fwd += 2 * head.in_features * head.out_features
+        data += 2 * head.in_features * head.out_features
+    return 2 * fwd + data
+
+
+def _quantiles(ms):
+    s = sorted(ms)
+    q = lambda p: s[min(len(s) - 1, int(round(p * (len(s) - 1))))]  # noqa: E731
+    return {"median": q(0.5), "p10": q(0.1), "p90": q(0.9)}
+
+
+def _timed_pair(run_fused, run_torch, warm=WARM, timed=TIMED):
+    """Alternate the two callables; -> (fused ms list, torch ms list) from device events."""
+    out = {"fused": [], "torch": []}
+    for i in range(warm + timed):
+        for name, fn in (("fused", run_fused), ("torch", run_torch)):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            if i >= warm:
+                out[name].append(a.elapsed_time(b))
+    return out["fused"], out["torch"]
+
+
+def _module():
+    from freegaussian_amd.deform import FreeGaussianDeformableModel
+
+    torch.manual_seed(0)
+    return FreeGaussianDeformableModel()
+
+
+def _knob(on):
+    if on:
+        os.environ[KNOB] = "1"
+    else:
+        os.environ.pop(KNOB, None)
+
+
+def _count_fused_calls():
+    from freegaussian_amd import ops
+
+    calls = []
+    real = ops.mlp_train
+    ops.mlp_train = lambda *a, **k: calls.append(1) or real(*a, **k)
+    return calls
+
+
+def _train_call(m, x, t, cots):
+    m.zero_grad(set_to_none=True)
+    torch.autograd.backward(m(x, t), cots)
+
+
+def step_time(out):
+    m = _module().cuda()
+    fl = flops_per_row(m)
+    res = {"flops_per_row": fl, "sizes": {}}
+    calls = _count_fused_calls()
+    for n in SIZES:
+        g = torch.Generator().manual_seed(n)
+        x = (torch.rand(n, 3, generator=g) * 2 - 1).cuda()
+        t = torch.full((1, 1), 0.4, device="cuda").expand(n, -1)
+        cots = [torch.randn(n, *s, generator=g).cuda() for s in ((4, 4), (4,), (3,))]
+
+        def run_fused():
+            _knob(True)
+            _train_call(m, x, t, cots)
+
+        def run_torch():
+            _knob(False)
+            _train_call(m, x, t, cots)
+
+        before = len(calls)
+        f, p = _timed_pair(run_fused, run_torch)
+        assert len(calls) - before == WARM + TIMED  # the fused path ran the kernels, the torch path never did
+        qf, qp = _quantiles(f), _quantiles(p)
+        res["sizes"][str(n)] = {"fused_ms": qf, "torch_ms": qp, "ratio": qf["median"] / qp["median"],
+                                "fused_tflops": fl * n / qf["median"] / 1e9, "torch_tflops": fl * n / qp["median"] / 1e9,
+                                "peak_alloc_gb": torch.cuda.max_memory_allocated() / 1e9}  # fmt: skip
+        print(n, res["sizes"][str(n)], flush=True)
+    json.dump(res, open(os.path.join(out, "time.json"), "w"), indent=1)
+
+
+def step_error(out):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from mlp_train_common import rows_clear_of_the_kink  # (the row filter of tests/test_mlp_train_gpu.py)
+
+    from freegaussian_amd.deform import FUSED_MIN_ROWS
+
+    n = 40_000  # (enough for the clear rows alone to reach the dispatch threshold)
+    m = _module()
+    g = torch.Generator().manual_seed(1)
+    x, t = torch.rand(n, 3, generator=g) * 2 - 1, torch.rand(n, 1, generator=g)
+    cots = [torch.randn(n, *s, generator=g, dtype=torch.float64) for s in ((4, 4), (4,), (3,))]
+    clear = rows_clear_of_the_kink(m, x, t)
+    assert int(clear.sum()) >= FUSED_MIN_ROWS
+    md = copy.deepcopy(m).cuda()
+    calls = _count_fused_calls()
+
+    def rel(a, b):
+        return float((a.detach().double().cpu() - b).abs().max() / b.abs().max())
+
+    res = {"rows": {"all rows": n, "rows clear of the ReLU kink": int(clear.sum())}}
+    for label, rows in (("all rows", torch.ones(n, dtype=torch.bool)), ("rows clear of the ReLU kink", clear)):
+        xr, tr, cr = x[rows], t[rows], [c[rows] for c in cots]
+        m64 = copy.deepcopy(m).double()
+        want_out = m64(xr.double(), tr.double())
+        torch.autograd.backward(want_out, cr)
+        want = {k: p.grad for k, p in m64.named_parameters()}
+        xd, td, cd = xr.cuda(), tr.cuda(), [c.float().cuda() for c in cr]
+        for name, on in (("fused", True), ("torch_fp32", False)):
+            _knob(on)
+            md.zero_grad(set_to_none=True)
+            outs = md(xd, td)
+            torch.autograd.backward(outs, cd)
+            worst = {}
+            for k, o, w in zip(("d_xyz", "d_rot", "d_scale"), outs, want_out):
+                worst[k] = rel(o, w.detach())
+            for k, p in md.named_parameters():
+                kind = "weight gradients" if k.endswith("weight") else "bias gradients"
+                worst[kind] = max(worst.get(kind, 0.0), rel(p.grad, want[k]))
+            for k, v in worst.items():
+                res.setdefault(f"{k}, {label}", {})[name] = v
+    assert len(calls) == 2
+    print(res, flush=True)
+    json.dump(res, open(os.path.join(out, "error.json"), "w"), indent=1)
+
+
+def step_model(out):
+    from freegaussian_amd.model import Camera, FreeGaussianModel, FreeGaussianModelConfig
+    from freegaussian_amd.scenes import look_at_viewmat
+
+    torch.manual_seed(0)
+    n, W, H = 240_000, 960, 540
+    cfg = FreeGaussianModelConfig(background_color="white", num_downscales=0, warm_up=3000)
+    model = FreeGaussianModel(cfg, seed_points=(torch.rand(n, 3) - 0.5) * 2.0, init_scales=-4.5, is_blender=False)
+    with torch.no_grad():
+        for q in model.deform.parameters():
+            q.mul_(0.3)
+    model.step = 4000
+    model = model.cuda().train()
+    c2w = torch.linalg.inv(look_at_viewmat(torch.tensor([0.3, -0.2, -3.0]), torch.zeros(3)))
+    c2w[:3, 1:3] *= -1  # OpenCV -> OpenGL camera axes (utils.get_viewmat flips them back)
+    cam = Camera(c2w[None, :3], 750.0, 750.0, W / 2, H / 2, W, H, times=torch.tensor([[0.4]]))
+    gt = torch.rand(H, W, 3, device="cuda")
+    calls = _count_fused_calls()
+
+    def step(on):
+        def run():
+            _knob(on)
+            model.zero_grad(set_to_none=True)
+            model.get_loss_dict(model.get_outputs(cam), {"image": gt})["main_loss"].backward()
+        return run
+
+    warm, timed = 5, 30
+    f, p = _timed_pair(step(True), step(False), warm=warm, timed=timed)
+    assert len(calls) == warm + timed
+    res = {"n": n, "width": W, "height": H, "fused_ms": _quantiles(f), "torch_ms": _quantiles(p)}
+    print(res, flush=True)
+    json.dump(res, open(os.path.join(out, "model.json"), "w"), indent=1)
+
+
+def step_trace(out):
+    m = _module().cuda()
+    n = 240_000
+    x = (torch.rand(n, 3) * 2 - 1).cuda()
+    t = torch.full((1, 1), 0.4, device="cuda").expand(n, -1)
+    cots = [torch.randn(n, *s).cuda() for s in ((4, 4), (4,), (3,))]
+    _knob(True)
+    for _ in range(3):
+        _train_call(m, x, t, cots)
+    torch.cuda.synchronize()
+
+
+def _ms(q):
+    return f"{q['median']:.3f} ({q['p10']:.3f} .. {q['p90']:.3f})"
+
+
+def step_report(out, md, parity):
+    from freegaussian_amd.deform import FUSED_MIN_ROWS
+
+    tm = json.load(open(os.path.join(out, "time.json")))
+    L = ["# Fused fp32 MLP training call (`ops.mlp_train`) against the torch path", "",
+         "Written by `scripts/mlp_train_bench.py` on an MI355X.  Deformation net (D = 8, W = 256, multires 10, 21-wide time",
+         "encoding, one time for all rows), forward + backward to the 24 parameter gradients from fixed output cotangents;",
+         f"{tm['flops_per_row']} FLOP per row from the layer shapes (forward, weight gradients, and the data gradients of the hidden",
+         f"activations).  `{KNOB}=1` against the variable unset, alternating call by call in one process, {WARM} warm-up and {TIMED}",
+         f"timed calls each between device events.  TFLOP/s: that count over the call's time, a whole-call rate (of the {PEAK_TF:.0f}",
+         "TFLOP/s fp32 matrix peak), not a kernel's.", "",
+         "| N | fused ms median (p10 .. p90) | torch ms median (p10 .. p90) | fused / torch | fused TFLOP/s | torch TFLOP/s | peak allocated GB |",
+         "|---|---|---|---|---|---|---|"]  # fmt: skip
+    for n, r in tm["sizes"].items():
+        L.append(f"| {int(n):,} | {_ms(r['fused_ms'])} | {_ms(r['torch_ms'])} | {r['ratio']:.2f} | {r['fused_tflops']:.1f} | "
+                 f"{r['torch_tflops']:.1f} | {r['peak_alloc_gb']:.1f} |")  # fmt: skip
+    L += ["", f"The knob is off unless set; dispatch from `deform.FUSED_MIN_ROWS` = {FUSED_MIN_ROWS:,} rows.  (Peak allocated: of the",
+          "process up to that size, both paths.)"]
+    if os.path.exists(os.path.join(out, "error.json")):
+        er = json.load(open(os.path.join(out, "error.json")))
+        rows = er.pop("rows")
+        L += ["", "## Error against float64 (default init, a time per row; max |a - b| / max |b|, worst array; the bar is 1e-4)", "",
+              f"Over {' and over '.join(f'{v:,} {k}' for k, v in rows.items())} (`rows_clear_of_the_kink` of tests/mlp_train_common.py:",
+              "no float64 pre-activation within 1e-5 of its layer's largest from zero).  Within fp32 rounding of zero a unit's mask is",
+              "either path's to choose, and one flipped unit moves a sum over N rows by about 1 / sqrt(N) of its scale.", "",
+              "| | fused path | torch fp32 on the GPU |", "|---|---|---|"]  # fmt: skip
+        L += [f"| {k} | {v['fused']:.2e} | {v['torch_fp32']:.2e} |" for k, v in er.items()]
+    if parity and os.path.exists(parity):
+        worst = {}
+        for line in open(parity):
+            r = json.loads(line)
+            if "test_mlp_train_gpu.py" in r["test"] and r["kind"] == "rel_err":
+                name = r["test"].split("::")[1].split("[")[0]
+                worst[name] = max(worst.get(name, 0.0), r["value"])
+        L += ["", "## Margins of tests/test_mlp_train_gpu.py (`FG_PARITY_REPORT`: the largest `rel_err` each test saw; the bar is 1e-4)", "",
+              "| test | largest rel_err |", "|---|---|"]  # fmt: skip
+        L += [f"| `{k}` | {v:.2e} |" for k, v in sorted(worst.items())]
+    if os.path.exists(os.path.join(out, "model.json")):
+        fr = json.load(open(os.path.join(out, "model.json")))
+        L += ["", f"## Model training step (`get_outputs` + `get_loss_dict` + backward; {fr['n']:,} random Gaussians behind `warm_up`, "
+              f"{fr['width']} x {fr['height']}, non-blender net)", "",
+              "| knob | ms per step median (p10 .. p90) |", "|---|---|",
+              f"| unset (the torch path) | {_ms(fr['torch_ms'])} |", f"| `{KNOB}=1` | {_ms(fr['fused_ms'])} |"]  # fmt: skip
+    stats = sorted(glob.glob(os.path.join(out, "trace", "**", "*kernel_stats.csv"), recursive=True))
+    if stats:
+        L += ["", "## Kernels of three fused calls at N = 240 000 (`rocprofv3 --kernel-trace --stats`, a run of its own)", "",
+              "| kernel | calls | average us | share % |", "|---|---|---|---|"]  # fmt: skip
+        for r in list(csv.DictReader(open(stats[0])))[:12]:
+            L.append(f"| `{r['Name'][:80]}` | {r['Calls']} | {float(r['AverageNs']) / 1e3:.1f} | {float(r['Percentage']):.1f} |")
+    # (hand-written sections of the file -- everything from the first "## Notes" heading on -- are kept)
+    if os.path.exists(md) and "\n## Notes" in open(md).read():
+        L += ["", "## Notes" + open(md).read().split("\n## Notes", 1)[1].rstrip()]
+    open(md, "w").write("\n".join(L) + "\n")
+    print("\n".join(L))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--step", choices=["time", "error", "model", "trace", "report"])
+    ap.add_argument("--trace", action="store_true", help="also one rocprofv3 --kernel-trace --stats run of the fused calls")
+    ap.add_argument("--parity", default=None, help="FG_PARITY_REPORT file of tests/test_mlp_train_gpu.py to quote")
+    ap.add_argument("--out", default=os.path.join(ROOT, "results", "mlp_train"))
+    ap.add_argument("--md", default=os.path.join(ROOT, "profiles", "mlp_train.md"))
+    a = ap.parse_args()
+    os.makedirs(a.out, exist_ok=True)
+    if a.step:
+        if a.step == "report":
+            return step_report(a.out, a.md, a.parity)
+        return {"time": step_time, "error": step_error, "model": step_model, "trace": step_trace}[a.step](a.out)
+    me = [sys.executable, os.path.abspath(__file__), "--out", a.out, "--md", a.md, "--step"]
+    steps = [(300, me + ["time"]), (180, me + ["error"]), (240, me + ["model"])]
+    if a.trace:
+        steps.append((180, ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", os.path.join(a.out, "trace"),
+                            "-o", "mlp", "--"] + me + ["trace"]))  # fmt: skip
+    steps.append((60, me + ["report"] + (["--parity", a.parity] if a.parity else [])))
+    for limit, cmd in steps:  # chained like &&: the first failure ends the job
+        rc = subprocess.call(["timeout", "-k", "10", str(limit)] + cmd)
+        if rc != 0:
+            sys.exit(f"step failed ({rc}): {' '.join(cmd[-2:])}")
+
+
+if __name__ == "__main__":
+    main()
