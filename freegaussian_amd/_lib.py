@@ -107,12 +107,15 @@ SIGNATURES = {
     "fg_mlp_train_workspace_bytes": (c_size_t, [c_int64]),
     "fg_mlp_train_fwd": (c_int, [c_int64, P, P, P, P, P, c_size_t, P]),  # (N, desc, heads, enc, acts, workspace, bytes, stream)
     "fg_mlp_bwd": (c_int, [c_int64, P, P, P, P, P, c_size_t, P]),  # (N, desc, g_heads, acts, g_pre, workspace, bytes, stream)
+    "fg_mlp_bwd_inputs_workspace_bytes": (c_size_t, [c_int64]),
+    # (N, desc, g_heads, acts, g_pre, g_enc, workspace, bytes, stream)
+    "fg_mlp_bwd_inputs": (c_int, [c_int64, P, P, P, P, P, P, c_size_t, P]),
 }  # fmt: skip
 
 # test hooks, not declared in the public header
 _EXTRA = {"fg_debug_wave_reduce16": (c_int, [P, P, P]), "fg_debug_knn_grid": (c_int, [c_int64, P, c_int, P, P])}
 
-ABI_VERSION = 12
+ABI_VERSION = 13
 KNN_MAX_K = 8  # FG_KNN_MAX_K
 MLP_ROW_TILE = 64  # FG_MLP_ROW_TILE
 MLP_MAX_HEADS = 4  # FG_MLP_MAX_HEADS

@@ -31,6 +31,12 @@
 //              comes from the saved activations, and every P_l tile is stored once.  The reduction runs over a layer's OUTPUT
 //              index, so the weights are packed a second way: Tp[g][k][e] = W[8 g + e][first hidden column + k].
 //              Nothing flows to the input row (layer 0, the input columns of layer 5): the inputs want no gradient.
+//   backward with input-row gradients (fg_mlp_bwd_inputs): mlp_bwd_kernel<true> -- the same chain, and two products more per
+//              tile: g_enc = P_5 W_5[:, :in_ch] + P_0 W_0, a [64, <= 128] tile, wave w owning columns 32 w .. 32 w + 31 as a
+//              2 x 1 block of the 32x32x2 MFMA (a wave whose block lies beyond the row's padded width skips it).  The layer-5
+//              part is taken while P_5 sits in LDS and waits in g_enc (stored and read back by the same lane) until l = 0, where
+//              P_0 goes to the same LDS tile for the second part: no third tile, two workgroups per CU as before.  Third packing:
+//              Tin[{0,5}][g][k][e] = W_l[8 g + e][k], k < 128, zero from in_ch on.
 //              The weight gradients are [256, N] x [N, 256] products over all tiles: the caller's.
 #include <cmath>
 
@@ -83,6 +89,11 @@ constexpr int MLP_T_LAYER_FLOATS = (MLP_W / 8) * MLP_GROUP_FLOATS;
 constexpr size_t MLP_T_HEAD = (size_t)(MLP_D - 1) * MLP_T_LAYER_FLOATS;
 constexpr size_t MLP_T_TOTAL = MLP_T_HEAD + 2 * MLP_GROUP_FLOATS;
 constexpr int MLP_GH_STRIDE = 16 + 4;  // the head cotangents of a tile in LDS
+// the input-row backward's third block, behind the two above: the input columns of layers 0 and 5, [2][32 groups][128][8]
+constexpr int MLP_IN_COLS = 128;
+constexpr int MLP_TIN_GROUP_FLOATS = MLP_IN_COLS * 8;
+constexpr int MLP_TIN_LAYER_FLOATS = (MLP_W / 8) * MLP_TIN_GROUP_FLOATS;
+constexpr size_t MLP_TIN_TOTAL = 2 * (size_t)MLP_TIN_LAYER_FLOATS;
 
 struct MlpArgs {
   const float* x;
@@ -168,6 +179,18 @@ mlp_pack_t_kernel(MlpArgs p, float* __restrict__ ws) {
   ws[at] = r;
 }
 
+// the input-row backward's weights: Tin[i][g][k][e] = W_l[8 g + e][k] for l = (0, 5)[i] and k < in_ch, zero up to k = 127
+__global__ void __launch_bounds__(MLP_BLOCK)
+mlp_pack_tin_kernel(MlpArgs p, float* __restrict__ tin) {
+  const size_t at = (size_t)blockIdx.x * MLP_BLOCK + threadIdx.x;
+  if (at >= MLP_TIN_TOTAL) return;
+  const int in_ch = MLP_XCH + p.A;
+  const int l = at < MLP_TIN_LAYER_FLOATS ? 0 : MLP_SKIP + 1;
+  const int rel = (int)(at % MLP_TIN_LAYER_FLOATS);
+  const int j = 8 * (rel / MLP_TIN_GROUP_FLOATS) + rel % 8, k = rel % MLP_TIN_GROUP_FLOATS / 8;
+  tin[at] = k < in_ch ? p.W[l][(size_t)j * (l == 0 ? in_ch : in_ch + MLP_W) + k] : 0.f;
+}
+
 // acc += src[rows][8 groups ...] x Wp: `a` points at this lane's row of the LDS source (+ 4 h), `b` at this lane's column
 // of the packed layer (+ 4 h).  The next group's operands are fetched before the current group's 16 MFMAs.
 __device__ __forceinline__ void mlp_gemm_part(f32x16 (&acc)[2][2], const float* a, int stride, int groups,
@@ -192,6 +215,27 @@ __device__ __forceinline__ void mlp_gemm_part(f32x16 (&acc)[2][2], const float* 
       acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[s], b1[s], acc[1][1], 0, 0, 0);
     }
     a0 = na0, a1 = na1, b0 = nb0, b1 = nb1;
+  }
+}
+
+// mlp_gemm_part for a 2 x 1 block over the 128-column packing Tin: the same operand reads, k order and prefetch
+__device__ __forceinline__ void mlp_gemm_in(f32x16 (&acc)[2], const float* a, int stride, int groups, const float* __restrict__ b) {
+  f32x4 a0 = *reinterpret_cast<const f32x4*>(a), a1 = *reinterpret_cast<const f32x4*>(a + 32 * stride);
+  f32x4 b0 = *reinterpret_cast<const f32x4*>(b);
+  for (int g = 0; g < groups; ++g) {
+    f32x4 na0 = a0, na1 = a1, nb0 = b0;
+    if (g + 1 < groups) {
+      const float* an = a + 8 * (g + 1);
+      na0 = *reinterpret_cast<const f32x4*>(an);
+      na1 = *reinterpret_cast<const f32x4*>(an + 32 * stride);
+      nb0 = *reinterpret_cast<const f32x4*>(b + (size_t)(g + 1) * MLP_TIN_GROUP_FLOATS);
+    }
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[s], b0[s], acc[0], 0, 0, 0);
+      acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[s], b0[s], acc[1], 0, 0, 0);
+    }
+    a0 = na0, a1 = na1, b0 = nb0;
   }
 }
 
@@ -355,9 +399,13 @@ mlp_fwd_kernel(int64_t N, MlpArgs p, MlpLayout L, const float* __restrict__ ws, 
   }
 }
 
-__global__ void __launch_bounds__(MLP_BLOCK)
+// INPUTS: also g_enc [N, enc_w] = P_5 W_5[:, :in_ch] + P_0 W_0 from `tin` (fg_mlp_bwd_inputs); false: neither is looked at, and
+// the code is the backward kernel's of before, instruction for instruction
+template <bool INPUTS>
+__global__ void __launch_bounds__(MLP_BLOCK) __attribute__((amdgpu_waves_per_eu(INPUTS ? 2 : 1)))
 mlp_bwd_kernel(int64_t N, int rows_total, const float* __restrict__ g_heads, const float* __restrict__ acts,
-               float* __restrict__ g_pre, const float* __restrict__ ws) {
+               float* __restrict__ g_pre, const float* __restrict__ ws, const float* __restrict__ tin,
+               float* __restrict__ g_enc, int in_ch, int enc_w) {
   __shared__ __attribute__((aligned(16))) float grad[MLP_M * MLP_ACT_STRIDE];
   __shared__ __attribute__((aligned(16))) float gh[MLP_M * MLP_GH_STRIDE];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -377,6 +425,9 @@ mlp_bwd_kernel(int64_t N, int rows_total, const float* __restrict__ g_heads, con
   for (int rb = 0; rb < 2; ++rb)
     for (int cb = 0; cb < 2; ++cb)
       for (int e = 0; e < 16; ++e) acc[rb][cb][e] = 0.f;
+  // (INPUTS) whether any of this wave's 64 x 32 block of g_enc lies inside the row, and its column of the packed weights
+  const bool in_block = INPUTS && 32 * wave < enc_w;
+  const float* b_in = tin + (size_t)(wave * 32 + li) * 8 + 4 * lh;
   mlp_gemm_part(acc, gh + li * MLP_GH_STRIDE + 4 * lh, MLP_GH_STRIDE, 2, ws + MLP_T_HEAD + b_lane);  // g(h_7)
   for (int l = MLP_D - 1; l >= 0; --l) {
     // P_l = g(h_l) where h_l > 0: to g_pre and, for the next product, in place of the previous tile
@@ -392,7 +443,7 @@ mlp_bwd_kernel(int64_t N, int rows_total, const float* __restrict__ g_heads, con
           if (live) out[(row0 + r) * MLP_W + c] = v;
           acc[rb][cb][e] = v;
         }
-    if (l == 0) break;
+    if (l == 0 && !INPUTS) break;
     __syncthreads();  // every wave has read the whole of the tile behind (l = 7: nothing to wait for, one barrier)
     for (int rb = 0; rb < 2; ++rb)
       for (int cb = 0; cb < 2; ++cb)
@@ -403,6 +454,27 @@ mlp_bwd_kernel(int64_t N, int rows_total, const float* __restrict__ g_heads, con
           acc[rb][cb][e] = 0.f;
         }
     __syncthreads();
+    if (INPUTS && in_block && (l == MLP_SKIP + 1 || l == 0)) {
+      // the chain of a g_enc element: from 0, layer 5's 256 terms, then layer 0's.  The partial sum waits in g_enc itself,
+      // written and read back by the same lane, so no register is held across the layers between (rows >= N: zeros in
+      // the tile, nothing stored)
+      const int c = wave * 32 + li;
+      f32x16 gin[2];
+      for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+          const int r = 32 * rb + (e & 3) + 8 * (e >> 2) + 4 * lh;
+          gin[rb][e] = l == 0 && row0 + r < N && c < enc_w ? g_enc[(row0 + r) * enc_w + c] : 0.f;
+        }
+      mlp_gemm_in(gin, a_grad, MLP_ACT_STRIDE, MLP_W / 8, b_in + (l == 0 ? 0 : MLP_TIN_LAYER_FLOATS));
+      for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+          const int r = 32 * rb + (e & 3) + 8 * (e >> 2) + 4 * lh;
+          if (row0 + r < N && c < enc_w) g_enc[(row0 + r) * enc_w + c] = c < in_ch ? gin[rb][e] : 0.f;
+        }
+    }
+    if (INPUTS && l == 0) break;
     mlp_gemm_part(acc, a_grad, MLP_ACT_STRIDE, MLP_W / 8, ws + (size_t)(l - 1) * MLP_T_LAYER_FLOATS + b_lane);  // g(h_{l-1})
   }
 }
@@ -499,6 +571,36 @@ extern "C" int fg_mlp_train_fwd(int64_t N, const fg_mlp_desc* d, float* heads, f
   return mlp_launch_fwd<true>(N, mlp_args(d), sv, workspace, stream);
 }
 
+namespace {
+
+// the launches of fg_mlp_bwd (g_enc null) and fg_mlp_bwd_inputs: the packed weights, then the chain
+int mlp_launch_bwd(int64_t N, const fg_mlp_desc* d, const float* g_heads, const float* acts, float* g_pre, float* g_enc,
+                   void* workspace, fg_stream_t stream) {
+  const MlpArgs p = mlp_args(d);
+  int rows_total = 0;
+  for (int h = 0; h < d->n_heads; ++h) rows_total += d->head_rows[h];
+  hipStream_t s = fg_hip_stream(stream);
+  float* ws = static_cast<float*>(workspace);
+  const dim3 tiles((unsigned)((N + MLP_M - 1) / MLP_M));
+  hipLaunchKernelGGL(mlp_pack_t_kernel, dim3((unsigned)((MLP_T_TOTAL + MLP_BLOCK - 1) / MLP_BLOCK)), dim3(MLP_BLOCK), 0, s, p, ws);
+  FG_RETURN_IF_LAUNCH_FAILED();
+  if (!g_enc) {
+    hipLaunchKernelGGL(mlp_bwd_kernel<false>, tiles, dim3(MLP_BLOCK), 0, s, N, rows_total, g_heads, acts, g_pre, ws, nullptr, nullptr,
+                       0, 0);
+    FG_RETURN_IF_LAUNCH_FAILED();
+    return FG_OK;
+  }
+  float* tin = ws + MLP_T_TOTAL;
+  hipLaunchKernelGGL(mlp_pack_tin_kernel, dim3((unsigned)((MLP_TIN_TOTAL + MLP_BLOCK - 1) / MLP_BLOCK)), dim3(MLP_BLOCK), 0, s, p, tin);
+  FG_RETURN_IF_LAUNCH_FAILED();
+  hipLaunchKernelGGL(mlp_bwd_kernel<true>, tiles, dim3(MLP_BLOCK), 0, s, N, rows_total, g_heads, acts, g_pre, ws, tin, g_enc,
+                     MLP_XCH + p.A, FG_MLP_ENC_WIDTH(p.A));
+  FG_RETURN_IF_LAUNCH_FAILED();
+  return FG_OK;
+}
+
+}  // namespace
+
 extern "C" int fg_mlp_bwd(int64_t N, const fg_mlp_desc* d, const float* g_heads, const float* acts, float* g_pre,
                           void* workspace, size_t workspace_bytes, fg_stream_t stream) {
   if (N < 0) return FG_ERR_INVALID_ARG;
@@ -506,15 +608,20 @@ extern "C" int fg_mlp_bwd(int64_t N, const fg_mlp_desc* d, const float* g_heads,
   if (int rc = mlp_check_desc(d, false)) return rc;
   if (d->mode != FG_MLP_PLAIN || !g_heads || !acts || !g_pre) return FG_ERR_INVALID_ARG;
   if (int rc = mlp_check_launch(N, workspace, workspace_bytes, fg_mlp_train_workspace_bytes(N))) return rc;
-  const MlpArgs p = mlp_args(d);
-  int rows_total = 0;
-  for (int h = 0; h < d->n_heads; ++h) rows_total += d->head_rows[h];
-  hipStream_t s = fg_hip_stream(stream);
-  float* ws = static_cast<float*>(workspace);
-  hipLaunchKernelGGL(mlp_pack_t_kernel, dim3((unsigned)((MLP_T_TOTAL + MLP_BLOCK - 1) / MLP_BLOCK)), dim3(MLP_BLOCK), 0, s, p, ws);
-  FG_RETURN_IF_LAUNCH_FAILED();
-  hipLaunchKernelGGL(mlp_bwd_kernel, dim3((unsigned)((N + MLP_M - 1) / MLP_M)), dim3(MLP_BLOCK), 0, s, N, rows_total, g_heads, acts,
-                     g_pre, ws);
-  FG_RETURN_IF_LAUNCH_FAILED();
-  return FG_OK;
+  return mlp_launch_bwd(N, d, g_heads, acts, g_pre, nullptr, workspace, stream);
+}
+
+extern "C" size_t fg_mlp_bwd_inputs_workspace_bytes(int64_t N) {
+  // (the training workspace and, behind it, the input columns of layers 0 and 5; the same for every N)
+  return N < 0 ? 0 : fg_mlp_train_workspace_bytes(N) + MLP_TIN_TOTAL * sizeof(float);
+}
+
+extern "C" int fg_mlp_bwd_inputs(int64_t N, const fg_mlp_desc* d, const float* g_heads, const float* acts, float* g_pre,
+                                 float* g_enc, void* workspace, size_t workspace_bytes, fg_stream_t stream) {
+  if (N < 0) return FG_ERR_INVALID_ARG;
+  if (N == 0) return FG_OK;
+  if (int rc = mlp_check_desc(d, false)) return rc;
+  if (d->mode != FG_MLP_PLAIN || !g_heads || !acts || !g_pre || !g_enc) return FG_ERR_INVALID_ARG;
+  if (int rc = mlp_check_launch(N, workspace, workspace_bytes, fg_mlp_bwd_inputs_workspace_bytes(N))) return rc;
+  return mlp_launch_bwd(N, d, g_heads, acts, g_pre, g_enc, workspace, stream);
 }

@@ -3,8 +3,9 @@
 (``ops.mlp_forward``: a weight re-ordering launch and the network's launch; ``FG_FUSED_MLP=0`` turns it off).
 With ``FG_FUSED_MLP_TRAIN=1`` (opt-in; unset = off) a taped forward over as many rows runs as ``ops.mlp_train``: the fused
 forward with saved activations, the fused backward data chain, and the weight gradients as chunked library products
-(``mlp_param_grads``).  Behaviour and ``state_dict`` key names follow the reference's
-``FreeGaussianDeformableModel`` / ``FreeGaussianControllableModel``
+(``mlp_param_grads``); ``FG_FUSED_MLP_TRAIN=2`` also takes the blender net and inputs that want a gradient
+(``ops.mlp_train(..., input_grads=True)``: the backward that forms the gradient of the input row).  Behaviour and
+``state_dict`` key names follow the reference's ``FreeGaussianDeformableModel`` / ``FreeGaussianControllableModel``
 (freegaussian/freegaussian_model.py:1054-1145) so stage-1 checkpoints load unchanged; outputs are
 checked against golden vectors produced by the reference classes (tests/golden/g_mlp.npz)."""
 from __future__ import annotations
@@ -109,24 +110,40 @@ def fused_applies(module: nn.Module, x: torch.Tensor, other: torch.Tensor) -> bo
     return True
 
 
-def fused_train_applies(module: nn.Module, x: torch.Tensor, other: torch.Tensor) -> bool:
-    """Whether a taped ``module(x, other)`` runs as one ``ops.mlp_train`` call: ``FG_FUSED_MLP_TRAIN=1`` (read here, on the
-    host, on every call; unset = off), grad mode on and a parameter that wants a gradient, inputs that want none, CUDA
-    fp32, enough rows, the one network shape the kernels are built for, and not the blender net (its ``timenet`` would
-    need the gradient of the encoded time, which the fused backward does not form).  Anything else: the torch ops."""
-    if os.environ.get("FG_FUSED_MLP_TRAIN", "0") != "1":
-        return False
-    if not torch.is_grad_enabled() or x.requires_grad or other.requires_grad:
-        return False
+def fused_train_mode(module: nn.Module, x: torch.Tensor, other: torch.Tensor) -> str:
+    """How a taped ``module(x, other)`` runs: "" = the torch ops, "1" or "2" = one ``ops.mlp_train`` call, the value being
+    ``FG_FUSED_MLP_TRAIN`` (read here and nowhere else, on the host, on every call; unset = off).  Either wants grad mode on
+    and a parameter that wants a gradient, CUDA fp32, enough rows and the one network shape the kernels are built for.
+    "1" wants inputs that need no gradient and not the blender net (its ``timenet`` needs the gradient of the encoded time,
+    which ``fg_mlp_bwd`` does not form); "2" takes those too, through ``ops.mlp_train(..., input_grads=True)``
+    (``fg_mlp_bwd_inputs``)."""
+    knob = os.environ.get("FG_FUSED_MLP_TRAIN", "0")
+    if knob not in ("1", "2"):
+        return ""
+    if not torch.is_grad_enabled() or (knob == "1" and (x.requires_grad or other.requires_grad)):
+        return ""
     if not (x.is_cuda and other.is_cuda and x.dtype == other.dtype == torch.float32 and x.dim() == other.dim() == 2):
-        return False
+        return ""
     other_ch = 3 if isinstance(module, FreeGaussianControllableModel) else 1
     if x.shape[0] < FUSED_MIN_ROWS or other.shape[0] != x.shape[0] or x.shape[1] != 3 or other.shape[1] != other_ch:
-        return False
-    if (module.D, module.W, module.multires, module.skip_at) != (8, 256, 10, 4) or getattr(module, "is_blender", False):
-        return False
+        return ""
+    if (module.D, module.W, module.multires, module.skip_at) != (8, 256, 10, 4):
+        return ""
+    if knob == "1" and getattr(module, "is_blender", False):
+        return ""
     params = list(module.parameters())
-    return all(p.is_cuda and p.dtype == torch.float32 for p in params) and any(p.requires_grad for p in params)
+    ok = all(p.is_cuda and p.dtype == torch.float32 for p in params) and any(p.requires_grad for p in params)
+    return knob if ok else ""
+
+
+def fused_train_applies(module: nn.Module, x: torch.Tensor, other: torch.Tensor) -> bool:
+    """Whether a taped ``module(x, other)`` runs as one ``ops.mlp_train`` call (``fused_train_mode``)."""
+    return fused_train_mode(module, x, other) != ""
+
+
+def _train_keywords(mode: str) -> dict:
+    """``ops.mlp_train``'s keywords for a ``fused_train_mode``: "2" = the call also returns the gradients of its inputs."""
+    return {"input_grads": True} if mode == "2" else {}
 
 
 def mlp_param_grads(inp: torch.Tensor, H: torch.Tensor, G: torch.Tensor, g_heads: torch.Tensor, head_rows):
@@ -196,12 +213,16 @@ class FreeGaussianDeformableModel(nn.Module):
     def forward(self, x: torch.Tensor, t: torch.Tensor):
         if fused_applies(self, x, t):
             return tuple(self._fused(x, t, (None, None, None, False))[:3])
-        if fused_train_applies(self, x, t):
+        mode = fused_train_mode(self, x, t)
+        if mode:
             from . import ops
 
+            # (taped: under "2" a time that wants a gradient, and the blender net's timenet, get theirs through aux)
             aux = positional_encoding(_one_row_if_broadcast(t), self.t_multires)
+            if self.is_blender:
+                aux = self.timenet(aux)
             heads = (self.branch_w, self.branch_v, self.gaussian_rotation, self.gaussian_scaling)
-            w, v, rot, scale = ops.mlp_train(x, aux, self.linear, heads).split((3, 3, 4, 3), dim=-1)
+            w, v, rot, scale = ops.mlp_train(x, aux, self.linear, heads, **_train_keywords(mode)).split((3, 3, 4, 3), dim=-1)
             return self._se3(w, v), rot, scale
         t_emb = positional_encoding(t, self.t_multires)
         if self.is_blender:
@@ -239,11 +260,13 @@ class FreeGaussianControllableModel(nn.Module):
             with torch.no_grad():
                 aux = positional_encoding(_one_row_if_broadcast(value), self.multires)
                 return tuple(ops.mlp_forward(x, aux, self.linear, (self.d_xyz, self.d_rot, self.d_scale), mode="plain"))
-        if fused_train_applies(self, x, value):
+        mode = fused_train_mode(self, x, value)
+        if mode:
             from . import ops
 
             aux = positional_encoding(_one_row_if_broadcast(value), self.multires)
-            return ops.mlp_train(x, aux, self.linear, (self.d_xyz, self.d_rot, self.d_scale)).split((3, 4, 3), dim=-1)
+            heads = (self.d_xyz, self.d_rot, self.d_scale)
+            return ops.mlp_train(x, aux, self.linear, heads, **_train_keywords(mode)).split((3, 4, 3), dim=-1)
         inp = torch.cat([positional_encoding(x, self.multires), positional_encoding(value, self.multires)], dim=-1)
         h = _run_trunk(self.linear, inp, self.skip_at)
         return _linear(self.d_xyz, h), _linear(self.d_rot, h), _linear(self.d_scale, h)

@@ -1348,12 +1348,33 @@ def mlp_forward(x: torch.Tensor, aux: torch.Tensor, trunk, heads, mode: str = "s
     return result
 
 
+def mlp_input_grads(g_enc: torch.Tensor, enc: torch.Tensor, aux_width: int, want_x: bool = True, want_aux: bool = True,
+                    one_row_aux: bool = False):
+    """The chain from the gradient of the encoded input row to the inputs (any device, any float type): ``g_enc`` and
+    ``enc`` [N, >= 63 + aux_width] as ``fg_mlp_bwd_inputs`` / ``fg_mlp_train_fwd`` store them ->  ``(g_x [N,3], g_aux)``,
+    ``None`` where not wanted.  ``g_aux`` is ``g_enc[:, 63:63 + A]``, for a one-row ``aux`` its column sum ``[1, A]`` (one
+    reduction launch, no atomics); ``g_x = g_enc[:, :3] + sum_k 2^k (g_sin_k cos_k - g_cos_k sin_k)`` with sin_k / cos_k the
+    saved encoding (``enc[3 + 6 k + c]`` / ``enc[3 + 6 k + 3 + c]``)."""
+    g_x = g_aux = None
+    if want_aux:
+        g_aux = g_enc[:, 63 : 63 + aux_width]
+        g_aux = g_aux.sum(0, keepdim=True) if one_row_aux else g_aux.contiguous()
+    if want_x:
+        N = g_enc.shape[0]
+        sc, g_sc = enc[:, 3:63].reshape(N, 10, 2, 3), g_enc[:, 3:63].reshape(N, 10, 2, 3)
+        # (2^k made on the device: no host copy, so the step stays capturable)
+        freq = torch.bitwise_left_shift(1, torch.arange(10, device=g_enc.device)).to(g_enc.dtype).view(1, 10, 1)
+        g_x = g_enc[:, :3] + ((g_sc[:, :, 0] * sc[:, :, 1] - g_sc[:, :, 1] * sc[:, :, 0]) * freq).sum(1)
+    return g_x, g_aux
+
+
 class _MlpTrain(torch.autograd.Function):
     """``fg_mlp_train_fwd`` / ``fg_mlp_bwd`` around the saved ``enc`` [N, padded in_ch] and ``H`` [8,N,256]; the inputs are
-    ``x``, ``aux``, the number of heads, then the 8 trunk weights, the 8 trunk biases, the head weights, the head biases."""
+    ``x``, ``aux``, the number of heads, whether ``x`` / ``aux`` may get a gradient (then ``fg_mlp_bwd_inputs`` where one
+    of them wants it), then the 8 trunk weights, the 8 trunk biases, the head weights, the head biases."""
 
     @staticmethod
-    def forward(ctx, x, aux, n_heads, *params):
+    def forward(ctx, x, aux, n_heads, input_grads, *params):
         trunk, heads = list(zip(params[:8], params[8:16])), list(zip(params[16 : 16 + n_heads], params[16 + n_heads :]))
         d, N, rows, keep = _mlp_desc("mlp_train", x, aux, trunk, heads, _lib.MLP_PLAIN)
         dev = keep[0].device
@@ -1365,6 +1386,7 @@ class _MlpTrain(torch.autograd.Function):
             _call("fg_mlp_train_fwd", N, ctypes.addressof(d), _ptr(out), _ptr(enc), _ptr(H), _ptr(ws), ws.numel(), _stream())
         ctx.save_for_backward(enc, H, *params)
         ctx.aux_width, ctx.head_rows = d.aux_width, rows
+        ctx.input_grads, ctx.one_row_aux = bool(input_grads), d.aux_stride == 0
         return out
 
     @staticmethod
@@ -1379,21 +1401,33 @@ class _MlpTrain(torch.autograd.Function):
         g_heads = _f32(g_heads, "g_heads")
         N = g_heads.shape[0]
         G = torch.empty_like(H)
+        want_x, want_aux = (ctx.input_grads and need for need in ctx.needs_input_grad[:2])
+        g_x = g_aux = None
         with torch.cuda.device(G.device):
-            ws = torch.empty(int(_lib.load().fg_mlp_train_workspace_bytes(N)), dtype=torch.uint8, device=G.device)
-            _call("fg_mlp_bwd", N, ctypes.addressof(d), _ptr(g_heads), _ptr(H), _ptr(G), _ptr(ws), ws.numel(), _stream())
+            if want_x or want_aux:
+                g_enc = torch.empty_like(enc)
+                ws = torch.empty(int(_lib.load().fg_mlp_bwd_inputs_workspace_bytes(N)), dtype=torch.uint8, device=G.device)
+                _call("fg_mlp_bwd_inputs", N, ctypes.addressof(d), _ptr(g_heads), _ptr(H), _ptr(G), _ptr(g_enc), _ptr(ws),
+                      ws.numel(), _stream())  # fmt: skip
+                g_x, g_aux = mlp_input_grads(g_enc, enc, ctx.aux_width, want_x, want_aux, ctx.one_row_aux)
+            else:
+                ws = torch.empty(int(_lib.load().fg_mlp_train_workspace_bytes(N)), dtype=torch.uint8, device=G.device)
+                _call("fg_mlp_bwd", N, ctypes.addressof(d), _ptr(g_heads), _ptr(H), _ptr(G), _ptr(ws), ws.numel(), _stream())
         gW, gb, gWh, gbh = mlp_param_grads(enc[:, : 63 + ctx.aux_width], H, G, g_heads, rows)
         grads = (*gW, *gb, *gWh, *gbh)
-        return (None, None, None, *(g if need else None for g, need in zip(grads, ctx.needs_input_grad[3:])))
+        return (g_x, g_aux, None, None, *(g if need else None for g, need in zip(grads, ctx.needs_input_grad[4:])))
 
 
-def mlp_train(x: torch.Tensor, aux: torch.Tensor, trunk, heads) -> torch.Tensor:
+def mlp_train(x: torch.Tensor, aux: torch.Tensor, trunk, heads, input_grads: bool = False) -> torch.Tensor:
     """The network of ``mlp_forward`` for training (``fg_mlp_train_fwd`` / ``fg_mlp_bwd``): the raw head outputs
     ``[N, rows_total]`` (the heads side by side in the order given, bit for bit ``mlp_forward(mode="plain")``), recorded
     for autograd.  The forward keeps the encoded input row and the eight post-ReLU activations (``[8,N,256]``); the
     backward runs the hidden-activation chain in one fused call into a second ``[8,N,256]`` array and forms the parameter
     gradients from the two (``deform.mlp_param_grads``: the chunked products of ``_TallLinear``).  ``x`` and ``aux`` get
-    no gradient.  CUDA float32 tensors, N >= 1; ``aux`` as for ``mlp_forward``.  No host synchronisation: capturable."""
+    no gradient unless ``input_grads``: then, where either wants one, the backward is ``fg_mlp_bwd_inputs`` -- the same
+    chain and the gradient of the encoded input row -- and ``mlp_input_grads`` takes that to ``x`` (through the
+    positional encoding, in closed form) and to ``aux`` (a one-row ``aux`` gets the sum over the rows).  CUDA float32
+    tensors, N >= 1; ``aux`` as for ``mlp_forward``.  No host synchronisation: capturable."""
     trunk = [(m.weight, m.bias) if hasattr(m, "weight") else tuple(m) for m in trunk]
     heads = [(m.weight, m.bias) if hasattr(m, "weight") else tuple(m) for m in heads]
     if len(trunk) != 8 or not 1 <= len(heads) <= _lib.MLP_MAX_HEADS:
@@ -1403,8 +1437,10 @@ def mlp_train(x: torch.Tensor, aux: torch.Tensor, trunk, heads) -> torch.Tensor:
         raise ValueError("mlp_train wants CUDA float32 tensors (and a bias on every layer)")
     if x.dim() != 2 or x.shape[0] < 1:
         raise ValueError(f"mlp_train wants [N,3] points with N >= 1, got {tuple(x.shape)}")
+    if input_grads and aux.requires_grad and aux.dim() == 2 and aux.shape[0] > 1 and aux.stride(0) == 0:
+        aux = aux[:1]  # (one row for all: autograd's own expand carries the [1, A] sum back)
     params = [w for w, _ in trunk] + [b for _, b in trunk] + [w for w, _ in heads] + [b for _, b in heads]
-    return _MlpTrain.apply(x, aux, len(heads), *params)
+    return _MlpTrain.apply(x, aux, len(heads), bool(input_grads), *params)
 
 
 # --------------------------------------------------------------------------------------------

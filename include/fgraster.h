@@ -44,7 +44,7 @@ typedef void* fg_stream_t;
 #define FG_MAX_CHANNELS 8    /* composited feature channels per splat (RGB, depth, flow, ...) */
 #define FG_SPLAT_FLOATS 16   /* one 64-byte record per Gaussian, see fg_pack_splats */
 #define FG_SH_JAC_FLOATS 10  /* per-Gaussian note of the SH colour for the backward, see fg_preprocess_fwd */
-#define FG_ABI_VERSION 12
+#define FG_ABI_VERSION 13
 #define FG_COUNT_OUT_WORDS 16 /* int64 words of a count_out block (fg_stbin_count, fg_step_io): ABI 9 */
 
 int fg_abi_version(void);
@@ -846,7 +846,7 @@ int fg_mlp_fwd(int64_t N, const fg_mlp_desc* desc, void* workspace, size_t works
  *                       P_l = g(h_l) where h_l > 0, else 0 (the rule of the ReLU's backward), stored to g_pre [8, N, 256];
  *                       g(h_{l-1}) = P_l W_l[:, hidden columns]  (l >= 1; layer 5's hidden columns are W_5[:, in_ch:])
  *                     No gradient is formed for the input row (layer 0's input, layer 5's input columns): in training the
- *                     network's inputs want none.  The parameter gradients are products of these arrays
+ *                     network's inputs want none (fg_mlp_bwd_inputs, below, forms it).  The parameter gradients are products of these arrays
  *                     (gW_l = P_l^T in_l, gb_l = sum of P_l over the rows, gW_head = g_heads^T h_7), left to the caller.
  *                     Every element of g_pre is one fmaf chain over its own row in a fixed order (64-row tiles on the exact
  *                     fp32 matrix instructions, the gradient tile in place in shared memory): rows are independent and two
@@ -862,6 +862,29 @@ int fg_mlp_train_fwd(int64_t N, const fg_mlp_desc* desc, float* heads, float* en
                      size_t workspace_bytes, fg_stream_t stream);
 int fg_mlp_bwd(int64_t N, const fg_mlp_desc* desc, const float* g_heads, const float* acts, float* g_pre, void* workspace,
                size_t workspace_bytes, fg_stream_t stream);
+
+/* ---- K10 training with input-row gradients (ABI 13): fg_mlp_bwd, which also forms the gradient of the encoded input row
+ * that fg_mlp_train_fwd stores as enc -- what a network in front of the trunk (the blender net's timenet), a per-row aux
+ * or the points themselves need.  Descriptor, g_heads, acts and error codes as fg_mlp_bwd (FG_MLP_PLAIN only; desc->x /
+ * desc->aux / desc->out are not read); a null g_enc is FG_ERR_INVALID_ARG.
+ *   g_pre [8, N, 256]   exactly what fg_mlp_bwd writes: the same chains, bit for bit
+ *   g_enc [N, FG_MLP_ENC_WIDTH(aux_width)]
+ *                       g_enc[row, k] = sum_j P_5[row, j] W_5[j, k] + sum_j P_0[row, j] W_0[j, k] for k < in_ch = 63 +
+ *                       aux_width; the pad columns k >= in_ch are written as exact zeros.  One fmaf chain per element over
+ *                       its own row in a fixed order: from 0, layer 5's 256 terms in the k order of the other products, then
+ *                       layer 0's.  Rows are independent and two runs are bit for bit equal; plain stores, no atomics.
+ * The chain from g_enc to the inputs is the caller's: g_aux = g_enc[:, 63:63 + aux_width] (summed over the rows for a
+ * one-row aux), g_x = g_enc[:, :3] + sum_k 2^k (g_sin_k cos_k - g_cos_k sin_k) with sin_k = enc[3 + 6 k + c] and
+ * cos_k = enc[3 + 6 k + 3 + c].  The kernel is fg_mlp_bwd's tile with two products more (8/7 of its matrix instructions):
+ * the layer-5 part is taken while P_5 sits in shared memory and waits in g_enc, written and read back by the same lane, until
+ * layer 0; no more shared memory.
+ * A third re-ordered block of weights (the input columns of layers 0 and 5, 256 KB) is written behind the other two by a
+ * launch of the same call.  Rows >= N of the last tile are neither read nor written.  The workspace: 16-byte aligned,
+ * fg_mlp_bwd_inputs_workspace_bytes(N) bytes (FG_ERR_WORKSPACE below that; fg_mlp_train_workspace_bytes is unchanged).
+ * N == 0 does nothing.  Asynchronous and capturable in a graph. */
+size_t fg_mlp_bwd_inputs_workspace_bytes(int64_t N);
+int fg_mlp_bwd_inputs(int64_t N, const fg_mlp_desc* desc, const float* g_heads, const float* acts, float* g_pre, float* g_enc,
+                      void* workspace, size_t workspace_bytes, fg_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -4,6 +4,7 @@
 what runs without this knob.  Writes profiles/mlp_train.md.
 
     python scripts/mlp_train_bench.py [--trace] [--parity FILE] [--out DIR] [--md profiles/mlp_train.md]
+    python scripts/mlp_train_bench.py --blender [--trace] [--parity FILE]     (writes profiles/mlp_train_inputs.md)
 
 runs the steps below as child processes, each under its own ``timeout -k 10``, stopping at the first that fails (a
 fault or a time limit in one step starts nothing more on the GPU):
@@ -19,6 +20,15 @@ fault or a time limit in one step starts nothing more on the GPU):
     --step trace   three fused calls at N = 240 000 for ``rocprofv3 --kernel-trace --stats`` (with --trace; a run of its own)
     --step report  profiles/mlp_train.md from these; --parity: a ``FG_PARITY_REPORT`` file of tests/test_mlp_train_gpu.py,
                    whose margins are quoted
+
+``--blender`` is the same protocol for the blender net (a 30-wide learned time code: ``timenet`` in front of the trunk)
+under ``FG_FUSED_MLP_TRAIN=2``, whose backward also forms the gradient of the input row (``fg_mlp_bwd_inputs``): the steps
+time, model (the default ``FreeGaussianModel``, which builds that net) and trace -- not error: the row filter it needs knows
+the non-blender net only, and tests/test_mlp_inputs_gpu.py holds this path to float64, whose margins --parity quotes -- and
+
+    --step kernel  ``fg_mlp_bwd`` and ``fg_mlp_bwd_inputs`` on the same saved activations and head cotangents at N = 240 000,
+                   alternating call by call between device events (each call: its weight re-ordering launches and the
+                   kernel); the trace step runs both as well, so that the kernel table holds each kernel's own time
 """
 import argparse
 import copy
@@ -38,15 +48,19 @@ SIZES = (33_000, 240_000, 1_000_000)
 WARM, TIMED = 10, 50
 PEAK_TF = 157.0  # fp32 matrix peak of an MI355X
 KNOB = "FG_FUSED_MLP_TRAIN"
+BLENDER = False  # --blender: the blender net under KNOB=2 (the backward with input-row gradients)
 
 
 def flops_per_row(m):
     """Forward: 2 x in x out over every linear.  Backward: the same again for each weight gradient, and once more for the
-    data gradient of every linear whose input is an activation (not layer 0, not the input columns of layer 5)."""
+    data gradient of every linear whose input is an activation (not layer 0, not the input columns of layer 5; the
+    blender net: those two as well -- its input row wants a gradient; ``timenet`` runs on one row and is not counted)."""
     fwd = data = 0
     for i, layer in enumerate(m.linear):
         fwd += 2 * layer.in_features * layer.out_features
         data += 0 if i == 0 else 2 * m.W * layer.out_features
+        if m.is_blender and i in (0, m.skip_at + 1):
+            data += 2 * m.input_ch * layer.out_features
     for head in (m.branch_w, m.branch_v, m.gaussian_rotation, m.gaussian_scaling):
         fwd += 2 * head.in_features * head.out_features
         data += 2 * head.in_features * head.out_features
@@ -78,12 +92,12 @@ def _module():
     from freegaussian_amd.deform import FreeGaussianDeformableModel
 
     torch.manual_seed(0)
-    return FreeGaussianDeformableModel()
+    return FreeGaussianDeformableModel(is_blender=BLENDER)
 
 
 def _knob(on):
     if on:
-        os.environ[KNOB] = "1"
+        os.environ[KNOB] = "2" if BLENDER else "1"
     else:
         os.environ.pop(KNOB, None)
 
@@ -184,7 +198,7 @@ def step_model(out):
     torch.manual_seed(0)
     n, W, H = 240_000, 960, 540
     cfg = FreeGaussianModelConfig(background_color="white", num_downscales=0, warm_up=3000)
-    model = FreeGaussianModel(cfg, seed_points=(torch.rand(n, 3) - 0.5) * 2.0, init_scales=-4.5, is_blender=False)
+    model = FreeGaussianModel(cfg, seed_points=(torch.rand(n, 3) - 0.5) * 2.0, init_scales=-4.5, is_blender=BLENDER)
     with torch.no_grad():
         for q in model.deform.parameters():
             q.mul_(0.3)
@@ -221,15 +235,132 @@ def step_trace(out):
     for _ in range(3):
         _train_call(m, x, t, cots)
     torch.cuda.synchronize()
+    if BLENDER:  # both backward kernels on the same inputs, for the table
+        run_plain, run_inputs = _backward_calls(m, n)
+        for _ in range(3):
+            run_plain()
+            run_inputs()
+        torch.cuda.synchronize()
+
+
+def _backward_calls(m, n):
+    """(fg_mlp_bwd, fg_mlp_bwd_inputs) as callables on the activations of one training forward of ``m`` over n rows."""
+    import ctypes
+
+    from freegaussian_amd import _lib, ops
+
+    g = torch.Generator().manual_seed(n)
+    x = (torch.rand(n, 3, generator=g) * 2 - 1).cuda()
+    aux = torch.randn(1, m.input_ch - 63, generator=g).cuda()
+    heads = (m.branch_w, m.branch_v, m.gaussian_rotation, m.gaussian_scaling)
+    d, _, rows, keep = ops._mlp_desc("bench", x, aux, m.linear, heads, _lib.MLP_PLAIN)
+    lib = _lib.load()
+    raw = torch.empty(n, sum(rows), device="cuda")
+    enc = torch.empty(n, _lib.mlp_enc_width(d.aux_width), device="cuda")
+    H, G = torch.empty(8, n, 256, device="cuda"), torch.empty(8, n, 256, device="cuda")
+    g_enc, g_heads = torch.empty_like(enc), torch.randn(n, sum(rows), generator=g).cuda()
+    ws = torch.empty(int(lib.fg_mlp_bwd_inputs_workspace_bytes(n)), dtype=torch.uint8, device="cuda")
+    small = int(lib.fg_mlp_train_workspace_bytes(n))
+    ptr, st = ctypes.addressof(d), ops._stream()
+    ops._call("fg_mlp_train_fwd", n, ptr, raw.data_ptr(), enc.data_ptr(), H.data_ptr(), ws.data_ptr(), small, st)
+    torch.cuda.synchronize()
+    hold = (d, keep, raw, enc, H, G, g_enc, g_heads, ws)
+
+    def run_plain(hold=hold):
+        ops._call("fg_mlp_bwd", n, ptr, g_heads.data_ptr(), H.data_ptr(), G.data_ptr(), ws.data_ptr(), small, st)
+
+    def run_inputs(hold=hold):
+        ops._call("fg_mlp_bwd_inputs", n, ptr, g_heads.data_ptr(), H.data_ptr(), G.data_ptr(), g_enc.data_ptr(), ws.data_ptr(),
+                  ws.numel(), st)  # fmt: skip
+
+    return run_plain, run_inputs
+
+
+def step_kernel(out):
+    m = _module().cuda()
+    n = 240_000
+    run_plain, run_inputs = _backward_calls(m, n)
+    f, p = _timed_pair(run_inputs, run_plain)
+    qf, qp = _quantiles(f), _quantiles(p)
+    res = {"n": n, "aux_width": m.input_ch - 63, "inputs_ms": qf, "plain_ms": qp, "ratio": qf["median"] / qp["median"]}
+    print(res, flush=True)
+    json.dump(res, open(os.path.join(out, "kernel.json"), "w"), indent=1)
 
 
 def _ms(q):
     return f"{q['median']:.3f} ({q['p10']:.3f} .. {q['p90']:.3f})"
 
 
+def step_report_inputs(out, md, parity):
+    """profiles/mlp_train_inputs.md (--blender)."""
+    from freegaussian_amd.deform import FUSED_MIN_ROWS
+
+    tm = json.load(open(os.path.join(out, "time.json")))
+    L = ["# Fused fp32 MLP training call with input-row gradients (`FG_FUSED_MLP_TRAIN=2`) against the torch path", "",
+         "Written by `scripts/mlp_train_bench.py --blender` on an MI355X.  Blender deformation net (D = 8, W = 256, multires 10, a",
+         "30-wide learned time code from `timenet`, one time for all rows), forward + backward to the 28 parameter gradients from",
+         f"fixed output cotangents; {tm['flops_per_row']} FLOP per row from the layer shapes (forward, weight gradients, the data",
+         f"gradients of the hidden activations and of the input row).  `{KNOB}=2` against the variable unset, alternating call by",
+         f"call in one process, {WARM} warm-up and {TIMED} timed calls each between device events.  TFLOP/s: that count over the",
+         f"call's time, a whole-call rate (of the {PEAK_TF:.0f} TFLOP/s fp32 matrix peak), not a kernel's.", "",
+         "| N | fused ms median (p10 .. p90) | torch ms median (p10 .. p90) | fused / torch | fused TFLOP/s | torch TFLOP/s | peak allocated GB |",
+         "|---|---|---|---|---|---|---|"]  # fmt: skip
+    for n, r in tm["sizes"].items():
+        L.append(f"| {int(n):,} | {_ms(r['fused_ms'])} | {_ms(r['torch_ms'])} | {r['ratio']:.2f} | {r['fused_tflops']:.1f} | "
+                 f"{r['torch_tflops']:.1f} | {r['peak_alloc_gb']:.1f} |")  # fmt: skip
+    L += ["", f"The knob is off unless set; dispatch from `deform.FUSED_MIN_ROWS` = {FUSED_MIN_ROWS:,} rows.  (Peak allocated: of the",
+          "process up to that size, both paths.)"]
+    stats = sorted(glob.glob(os.path.join(out, "trace", "**", "*kernel_stats.csv"), recursive=True))
+    rows = list(csv.DictReader(open(stats[0]))) if stats else []
+    if os.path.exists(os.path.join(out, "kernel.json")):
+        kr = json.load(open(os.path.join(out, "kernel.json")))
+        L += ["", f"## The backward with input-row gradients against the one without (N = {kr['n']:,}, aux {kr['aux_width']} wide, the same "
+              "activations and cotangents)", "",
+              "`fg_mlp_bwd`'s kernel is the previous commit's, instruction for instruction (its disassembly was compared), so this is",
+              "the new kernel against that one.  By matrix-instruction count the new kernel does 8/7 = 1.14 of the old one's products.", "",
+              "| | `fg_mlp_bwd_inputs` | `fg_mlp_bwd` | ratio |", "|---|---|---|---|",
+              f"| whole call, ms median (p10 .. p90), device events, alternating | {_ms(kr['inputs_ms'])} | {_ms(kr['plain_ms'])} | "
+              f"{kr['ratio']:.2f} |"]  # fmt: skip
+        avg = {}
+        for r in rows:
+            if "mlp_bwd_kernel" in r["Name"]:
+                avg["inputs" if ("true" in r["Name"] or "Lb1" in r["Name"]) else "plain"] = float(r["AverageNs"]) / 1e6
+        if len(avg) == 2:
+            L.append(f"| the kernel alone, average ms (`rocprofv3`, the table below) | {avg['inputs']:.3f} | {avg['plain']:.3f} | "
+                     f"{avg['inputs'] / avg['plain']:.2f} |")  # fmt: skip
+    if os.path.exists(os.path.join(out, "model.json")):
+        fr = json.load(open(os.path.join(out, "model.json")))
+        L += ["", f"## Model training step (`get_outputs` + `get_loss_dict` + backward; the default `FreeGaussianModel` -- the blender net "
+              f"-- {fr['n']:,} random Gaussians behind `warm_up`, {fr['width']} x {fr['height']})", "",
+              "| knob | ms per step median (p10 .. p90) |", "|---|---|",
+              f"| unset (the torch path) | {_ms(fr['torch_ms'])} |", f"| `{KNOB}=2` | {_ms(fr['fused_ms'])} |"]  # fmt: skip
+    if rows:
+        L += ["", "## Kernels of three fused calls, then three calls of each backward entry point, at N = 240 000 "
+              "(`rocprofv3 --kernel-trace --stats`, a run of its own)", "",
+              "| kernel | calls | average us | share % |", "|---|---|---|---|"]  # fmt: skip
+        for r in rows[:14]:
+            L.append(f"| `{r['Name'][:80]}` | {r['Calls']} | {float(r['AverageNs']) / 1e3:.1f} | {float(r['Percentage']):.1f} |")
+    if parity and os.path.exists(parity):
+        worst = {}
+        for line in open(parity):
+            r = json.loads(line)
+            if "test_mlp_inputs_gpu.py" in r["test"] and r["kind"] == "rel_err":
+                name = r["test"].split("::")[1].split("[")[0]
+                worst[name] = max(worst.get(name, 0.0), r["value"])
+        L += ["", "## Margins of tests/test_mlp_inputs_gpu.py (`FG_PARITY_REPORT`: the largest `rel_err` each test saw; the bar is 1e-4)", "",
+              "| test | largest rel_err |", "|---|---|"]  # fmt: skip
+        L += [f"| `{k}` | {v:.2e} |" for k, v in sorted(worst.items())]
+    if os.path.exists(md) and "\n## Notes" in open(md).read():
+        L += ["", "## Notes" + open(md).read().split("\n## Notes", 1)[1].rstrip()]
+    open(md, "w").write("\n".join(L) + "\n")
+    print("\n".join(L))
+
+
 def step_report(out, md, parity):
     from freegaussian_amd.deform import FUSED_MIN_ROWS
 
+    if BLENDER:
+        return step_report_inputs(out, md, parity)
     tm = json.load(open(os.path.join(out, "time.json")))
     L = ["# Fused fp32 MLP training call (`ops.mlp_train`) against the torch path", "",
          "Written by `scripts/mlp_train_bench.py` on an MI355X.  Deformation net (D = 8, W = 256, multires 10, 21-wide time",
@@ -285,19 +416,27 @@ def step_report(out, md, parity):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--step", choices=["time", "error", "model", "trace", "report"])
+    ap.add_argument("--step", choices=["time", "error", "model", "trace", "kernel", "report"])
+    ap.add_argument("--blender", action="store_true", help="the blender net under FG_FUSED_MLP_TRAIN=2 (profiles/mlp_train_inputs.md)")
     ap.add_argument("--trace", action="store_true", help="also one rocprofv3 --kernel-trace --stats run of the fused calls")
-    ap.add_argument("--parity", default=None, help="FG_PARITY_REPORT file of tests/test_mlp_train_gpu.py to quote")
-    ap.add_argument("--out", default=os.path.join(ROOT, "results", "mlp_train"))
-    ap.add_argument("--md", default=os.path.join(ROOT, "profiles", "mlp_train.md"))
+    ap.add_argument("--parity", default=None, help="FG_PARITY_REPORT file to quote: of tests/test_mlp_train_gpu.py, with --blender of tests/test_mlp_inputs_gpu.py")
+    ap.add_argument("--out", default=None, help="default: results/mlp_train, results/mlp_train_inputs with --blender")
+    ap.add_argument("--md", default=None, help="default: profiles/mlp_train.md, profiles/mlp_train_inputs.md with --blender")
     a = ap.parse_args()
+    global BLENDER
+    BLENDER = a.blender
+    name = "mlp_train_inputs" if BLENDER else "mlp_train"
+    a.out = a.out or os.path.join(ROOT, "results", name)
+    a.md = a.md or os.path.join(ROOT, "profiles", name + ".md")
     os.makedirs(a.out, exist_ok=True)
     if a.step:
         if a.step == "report":
             return step_report(a.out, a.md, a.parity)
-        return {"time": step_time, "error": step_error, "model": step_model, "trace": step_trace}[a.step](a.out)
-    me = [sys.executable, os.path.abspath(__file__), "--out", a.out, "--md", a.md, "--step"]
+        return {"time": step_time, "error": step_error, "model": step_model, "trace": step_trace, "kernel": step_kernel}[a.step](a.out)
+    me = [sys.executable, os.path.abspath(__file__), "--out", a.out, "--md", a.md] + (["--blender"] if BLENDER else []) + ["--step"]
     steps = [(300, me + ["time"]), (180, me + ["error"]), (240, me + ["model"])]
+    if BLENDER:
+        steps = [(300, me + ["time"]), (120, me + ["kernel"]), (240, me + ["model"])]
     if a.trace:
         steps.append((180, ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", os.path.join(a.out, "trace"),
                             "-o", "mlp", "--"] + me + ["trace"]))  # fmt: skip
