@@ -110,16 +110,21 @@ SIGNATURES = {
     "fg_mlp_bwd_inputs_workspace_bytes": (c_size_t, [c_int64]),
     # (N, desc, g_heads, acts, g_pre, g_enc, workspace, bytes, stream)
     "fg_mlp_bwd_inputs": (c_int, [c_int64, P, P, P, P, P, P, c_size_t, P]),
+    "fg_mlp_param_grads_workspace_bytes": (c_size_t, [c_int64]),
+    "fg_mlp_param_grads_slab_rows": (c_int, [c_int64]),
+    # (N, desc, enc, acts, g_pre, g_heads, const fg_mlp_grads*, workspace, bytes, stream)
+    "fg_mlp_param_grads": (c_int, [c_int64, P, P, P, P, P, P, P, c_size_t, P]),
 }  # fmt: skip
 
 # test hooks, not declared in the public header
 _EXTRA = {"fg_debug_wave_reduce16": (c_int, [P, P, P]), "fg_debug_knn_grid": (c_int, [c_int64, P, c_int, P, P])}
 
-ABI_VERSION = 13
+ABI_VERSION = 14
 KNN_MAX_K = 8  # FG_KNN_MAX_K
 MLP_ROW_TILE = 64  # FG_MLP_ROW_TILE
 MLP_MAX_HEADS = 4  # FG_MLP_MAX_HEADS
 MLP_SE3, MLP_PLAIN = 0, 1  # FG_MLP_SE3, FG_MLP_PLAIN
+MLP_WGRAD_MAX_SLAB, MLP_WGRAD_MIN_SPLIT = 4096, 512  # FG_MLP_WGRAD_MAX_SLAB, FG_MLP_WGRAD_MIN_SPLIT
 
 
 def mlp_enc_width(aux_width: int) -> int:
@@ -202,6 +207,14 @@ class MlpDesc(ctypes.Structure):
         ("x", ctypes.c_void_p), ("aux", ctypes.c_void_p), ("weight", ctypes.c_void_p * 8), ("bias", ctypes.c_void_p * 8),
         ("head_weight", ctypes.c_void_p * MLP_MAX_HEADS), ("head_bias", ctypes.c_void_p * MLP_MAX_HEADS),
         ("out", ctypes.c_void_p * MLP_MAX_HEADS)]  # fmt: skip
+
+
+class MlpGrads(ctypes.Structure):
+    """``fg_mlp_grads``: where ``fg_mlp_param_grads`` writes; a null pointer = that gradient is not formed."""
+
+    _fields_ = [("size", ctypes.c_int32), ("reserved", ctypes.c_int32), ("weight", ctypes.c_void_p * 8),
+                ("bias", ctypes.c_void_p * 8), ("head_weight", ctypes.c_void_p * MLP_MAX_HEADS),
+                ("head_bias", ctypes.c_void_p * MLP_MAX_HEADS)]  # fmt: skip
 
 
 def load() -> ctypes.CDLL:

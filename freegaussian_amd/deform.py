@@ -4,7 +4,8 @@
 With ``FG_FUSED_MLP_TRAIN=1`` (opt-in; unset = off) a taped forward over as many rows runs as ``ops.mlp_train``: the fused
 forward with saved activations, the fused backward data chain, and the weight gradients as chunked library products
 (``mlp_param_grads``); ``FG_FUSED_MLP_TRAIN=2`` also takes the blender net and inputs that want a gradient
-(``ops.mlp_train(..., input_grads=True)``: the backward that forms the gradient of the input row).  Behaviour and
+(``ops.mlp_train(..., input_grads=True)``: the backward that forms the gradient of the input row); with
+``FG_FUSED_MLP_WGRAD=1`` (opt-in) on top of either, the weight gradients are one fused call too (``ops.mlp_param_grads``).  Behaviour and
 ``state_dict`` key names follow the reference's ``FreeGaussianDeformableModel`` / ``FreeGaussianControllableModel``
 (freegaussian/freegaussian_model.py:1054-1145) so stage-1 checkpoints load unchanged; outputs are
 checked against golden vectors produced by the reference classes (tests/golden/g_mlp.npz)."""
@@ -142,8 +143,15 @@ def fused_train_applies(module: nn.Module, x: torch.Tensor, other: torch.Tensor)
 
 
 def _train_keywords(mode: str) -> dict:
-    """``ops.mlp_train``'s keywords for a ``fused_train_mode``: "2" = the call also returns the gradients of its inputs."""
-    return {"input_grads": True} if mode == "2" else {}
+    """``ops.mlp_train``'s keywords for a ``fused_train_mode``: "2" = the call also returns the gradients of its inputs;
+    ``FG_FUSED_MLP_WGRAD=1`` (opt-in; read here and nowhere else, on the host, on every call; unset = off) = its parameter
+    gradients come from the fused call ``ops.mlp_param_grads`` in place of ``mlp_param_grads`` below.  The knob has no
+    lower row bound of its own: it wins at every size measured (profiles/mlp_wgrad.md: 0.49 against 1.42 ms at 33 000 rows,
+    the smallest, within 1 % of ``FUSED_MIN_ROWS``, the fewest rows a fused training call sees)."""
+    kw = {"input_grads": True} if mode == "2" else {}
+    if os.environ.get("FG_FUSED_MLP_WGRAD", "0") == "1":
+        kw["fused_param_grads"] = True
+    return kw
 
 
 def mlp_param_grads(inp: torch.Tensor, H: torch.Tensor, G: torch.Tensor, g_heads: torch.Tensor, head_rows):

@@ -1368,13 +1368,69 @@ def mlp_input_grads(g_enc: torch.Tensor, enc: torch.Tensor, aux_width: int, want
     return g_x, g_aux
 
 
+def mlp_wgrad_slab_rows(N: int) -> int:
+    """Rows of one slab of ``fg_mlp_param_grads`` over ``N`` rows (a function of ``N`` alone; tests place rows around it)."""
+    return int(_lib.load().fg_mlp_param_grads_slab_rows(int(N)))
+
+
+def mlp_param_grads(enc: torch.Tensor, H: torch.Tensor, G: torch.Tensor, g_heads: torch.Tensor, aux_width: int, head_rows,
+                    want=None):
+    """The parameter gradients of the fused training path in one call (``fg_mlp_param_grads``): from ``enc``
+    [N, padded 63 + aux_width] and ``H`` [8,N,256] as ``fg_mlp_train_fwd`` stores them, ``G`` [8,N,256] as ``fg_mlp_bwd``
+    does and the head cotangents ``g_heads`` [N, sum(head_rows)] ->  ``(gW x 8, gb x 8, gW_head per head, gb_head per
+    head)``, the tuple of ``deform.mlp_param_grads`` in ``nn.Linear``'s layouts.  ``want``: one boolean per gradient in the
+    order of ``_MlpTrain``'s ``params`` (trunk weights, trunk biases, head weights, head biases); an unwanted one is not
+    formed and comes back as ``None``.  Row slabs on the exact-fp32 matrix instructions, partial sums added in slab order:
+    no atomics, two calls on the same arrays are bit for bit equal.  CUDA float32 contiguous tensors; no host
+    synchronisation: capturable."""
+    tensors = (enc, H, G, g_heads)
+    if any(not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() for t in tensors):
+        raise ValueError("mlp_param_grads wants contiguous CUDA float32 tensors")
+    rows = [int(r) for r in head_rows]
+    n = len(rows)
+    if not 1 <= aux_width <= 64 or not 1 <= n <= _lib.MLP_MAX_HEADS or min(rows) < 1 or sum(rows) > 16:
+        raise ValueError(f"mlp_param_grads: aux width {aux_width} / head rows {rows} outside what the kernels take")
+    N, in_ch = enc.shape[0], 63 + aux_width
+    if enc.dim() != 2 or enc.shape[1] != _lib.mlp_enc_width(aux_width):
+        raise ValueError(f"mlp_param_grads wants enc [N, {_lib.mlp_enc_width(aux_width)}], got {tuple(enc.shape)}")
+    if tuple(H.shape) != (8, N, 256) or G.shape != H.shape:
+        raise ValueError(f"mlp_param_grads wants H and G [8, {N}, 256], got {tuple(H.shape)} and {tuple(G.shape)}")
+    if tuple(g_heads.shape) != (N, sum(rows)):
+        raise ValueError(f"mlp_param_grads wants g_heads [{N}, {sum(rows)}], got {tuple(g_heads.shape)}")
+    want = [True] * (16 + 2 * n) if want is None else [bool(w) for w in want]
+    if len(want) != 16 + 2 * n:
+        raise ValueError(f"mlp_param_grads: want has {len(want)} entries for {16 + 2 * n} gradients")
+    shapes = [(256, in_ch if l == 0 else (in_ch + 256 if l == 5 else 256)) for l in range(8)] + [(256,)] * 8
+    shapes += [(r, 256) for r in rows] + [(r,) for r in rows]
+    dev = enc.device
+    # (N = 0: the sums over no rows)
+    outs = [(torch.zeros if N == 0 else torch.empty)(s, dtype=torch.float32, device=dev) if w else None for s, w in zip(shapes, want)]
+    if N > 0 and any(want):
+        d, g = _lib.MlpDesc(), _lib.MlpGrads()
+        d.size, d.mode, d.depth, d.width, d.multires = ctypes.sizeof(_lib.MlpDesc), _lib.MLP_PLAIN, 8, 256, 10
+        d.aux_width, d.n_heads = aux_width, n
+        g.size = ctypes.sizeof(_lib.MlpGrads)
+        for i, r in enumerate(rows):
+            d.head_rows[i] = r
+        for i in range(8):
+            g.weight[i], g.bias[i] = _ptr(outs[i]), _ptr(outs[8 + i])
+        for i in range(n):
+            g.head_weight[i], g.head_bias[i] = _ptr(outs[16 + i]), _ptr(outs[16 + n + i])
+        with torch.cuda.device(dev):
+            ws = torch.empty(int(_lib.load().fg_mlp_param_grads_workspace_bytes(N)), dtype=torch.uint8, device=dev)
+            _call("fg_mlp_param_grads", N, ctypes.addressof(d), _ptr(enc), _ptr(H), _ptr(G), _ptr(g_heads), ctypes.addressof(g),
+                  _ptr(ws), ws.numel(), _stream())  # fmt: skip
+    return tuple(outs[:8]), tuple(outs[8:16]), tuple(outs[16 : 16 + n]), tuple(outs[16 + n :])
+
+
 class _MlpTrain(torch.autograd.Function):
     """``fg_mlp_train_fwd`` / ``fg_mlp_bwd`` around the saved ``enc`` [N, padded in_ch] and ``H`` [8,N,256]; the inputs are
     ``x``, ``aux``, the number of heads, whether ``x`` / ``aux`` may get a gradient (then ``fg_mlp_bwd_inputs`` where one
-    of them wants it), then the 8 trunk weights, the 8 trunk biases, the head weights, the head biases."""
+    of them wants it), whether the parameter gradients come from ``fg_mlp_param_grads``, then the 8 trunk weights, the 8
+    trunk biases, the head weights, the head biases."""
 
     @staticmethod
-    def forward(ctx, x, aux, n_heads, input_grads, *params):
+    def forward(ctx, x, aux, n_heads, input_grads, fused_param_grads, *params):
         trunk, heads = list(zip(params[:8], params[8:16])), list(zip(params[16 : 16 + n_heads], params[16 + n_heads :]))
         d, N, rows, keep = _mlp_desc("mlp_train", x, aux, trunk, heads, _lib.MLP_PLAIN)
         dev = keep[0].device
@@ -1387,12 +1443,13 @@ class _MlpTrain(torch.autograd.Function):
         ctx.save_for_backward(enc, H, *params)
         ctx.aux_width, ctx.head_rows = d.aux_width, rows
         ctx.input_grads, ctx.one_row_aux = bool(input_grads), d.aux_stride == 0
+        ctx.fused_param_grads = bool(fused_param_grads)
         return out
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_heads):
-        from .deform import mlp_param_grads
+        from . import deform
 
         enc, H, *params = ctx.saved_tensors
         n = len(ctx.head_rows)
@@ -1413,12 +1470,16 @@ class _MlpTrain(torch.autograd.Function):
             else:
                 ws = torch.empty(int(_lib.load().fg_mlp_train_workspace_bytes(N)), dtype=torch.uint8, device=G.device)
                 _call("fg_mlp_bwd", N, ctypes.addressof(d), _ptr(g_heads), _ptr(H), _ptr(G), _ptr(ws), ws.numel(), _stream())
-        gW, gb, gWh, gbh = mlp_param_grads(enc[:, : 63 + ctx.aux_width], H, G, g_heads, rows)
+        if ctx.fused_param_grads:
+            gW, gb, gWh, gbh = mlp_param_grads(enc, H, G, g_heads, ctx.aux_width, rows, want=ctx.needs_input_grad[5:])
+            return (g_x, g_aux, None, None, None, *gW, *gb, *gWh, *gbh)
+        gW, gb, gWh, gbh = deform.mlp_param_grads(enc[:, : 63 + ctx.aux_width], H, G, g_heads, rows)
         grads = (*gW, *gb, *gWh, *gbh)
-        return (g_x, g_aux, None, None, *(g if need else None for g, need in zip(grads, ctx.needs_input_grad[4:])))
+        return (g_x, g_aux, None, None, None, *(g if need else None for g, need in zip(grads, ctx.needs_input_grad[5:])))
 
 
-def mlp_train(x: torch.Tensor, aux: torch.Tensor, trunk, heads, input_grads: bool = False) -> torch.Tensor:
+def mlp_train(x: torch.Tensor, aux: torch.Tensor, trunk, heads, input_grads: bool = False,
+              fused_param_grads: bool = False) -> torch.Tensor:
     """The network of ``mlp_forward`` for training (``fg_mlp_train_fwd`` / ``fg_mlp_bwd``): the raw head outputs
     ``[N, rows_total]`` (the heads side by side in the order given, bit for bit ``mlp_forward(mode="plain")``), recorded
     for autograd.  The forward keeps the encoded input row and the eight post-ReLU activations (``[8,N,256]``); the
@@ -1426,7 +1487,9 @@ def mlp_train(x: torch.Tensor, aux: torch.Tensor, trunk, heads, input_grads: boo
     gradients from the two (``deform.mlp_param_grads``: the chunked products of ``_TallLinear``).  ``x`` and ``aux`` get
     no gradient unless ``input_grads``: then, where either wants one, the backward is ``fg_mlp_bwd_inputs`` -- the same
     chain and the gradient of the encoded input row -- and ``mlp_input_grads`` takes that to ``x`` (through the
-    positional encoding, in closed form) and to ``aux`` (a one-row ``aux`` gets the sum over the rows).  CUDA float32
+    positional encoding, in closed form) and to ``aux`` (a one-row ``aux`` gets the sum over the rows).
+    ``fused_param_grads``: the parameter gradients come from one ``fg_mlp_param_grads`` call (``mlp_param_grads`` above:
+    only those that want one are formed) in place of the library products; the rest of the backward is the same.  CUDA float32
     tensors, N >= 1; ``aux`` as for ``mlp_forward``.  No host synchronisation: capturable."""
     trunk = [(m.weight, m.bias) if hasattr(m, "weight") else tuple(m) for m in trunk]
     heads = [(m.weight, m.bias) if hasattr(m, "weight") else tuple(m) for m in heads]
@@ -1440,7 +1503,7 @@ def mlp_train(x: torch.Tensor, aux: torch.Tensor, trunk, heads, input_grads: boo
     if input_grads and aux.requires_grad and aux.dim() == 2 and aux.shape[0] > 1 and aux.stride(0) == 0:
         aux = aux[:1]  # (one row for all: autograd's own expand carries the [1, A] sum back)
     params = [w for w, _ in trunk] + [b for _, b in trunk] + [w for w, _ in heads] + [b for _, b in heads]
-    return _MlpTrain.apply(x, aux, len(heads), bool(input_grads), *params)
+    return _MlpTrain.apply(x, aux, len(heads), bool(input_grads), bool(fused_param_grads), *params)
 
 
 # --------------------------------------------------------------------------------------------

@@ -44,7 +44,7 @@ typedef void* fg_stream_t;
 #define FG_MAX_CHANNELS 8    /* composited feature channels per splat (RGB, depth, flow, ...) */
 #define FG_SPLAT_FLOATS 16   /* one 64-byte record per Gaussian, see fg_pack_splats */
 #define FG_SH_JAC_FLOATS 10  /* per-Gaussian note of the SH colour for the backward, see fg_preprocess_fwd */
-#define FG_ABI_VERSION 13
+#define FG_ABI_VERSION 14
 #define FG_COUNT_OUT_WORDS 16 /* int64 words of a count_out block (fg_stbin_count, fg_step_io): ABI 9 */
 
 int fg_abi_version(void);
@@ -885,6 +885,56 @@ int fg_mlp_bwd(int64_t N, const fg_mlp_desc* desc, const float* g_heads, const f
 size_t fg_mlp_bwd_inputs_workspace_bytes(int64_t N);
 int fg_mlp_bwd_inputs(int64_t N, const fg_mlp_desc* desc, const float* g_heads, const float* acts, float* g_pre, float* g_enc,
                       void* workspace, size_t workspace_bytes, fg_stream_t stream);
+
+/* ---- K10 parameter gradients (ABI 14): the products that fg_mlp_bwd leaves to the caller, in one call of two launches.
+ * From enc and acts as fg_mlp_train_fwd stores them, g_pre (P_l) as fg_mlp_bwd / fg_mlp_bwd_inputs store it and the head
+ * cotangents g_heads [N, rows_total]:
+ *   gW_l    = P_l^T in_l          in_0 = enc[:, :in_ch], in_5 = [enc[:, :in_ch], h_4], in_l = h_{l-1} otherwise (in_ch = 63 + aux_width)
+ *   gb_l    = sum over the rows of P_l
+ *   gW_head = g_heads^T h_7 (split by head_rows),   gb_head = sum over the rows of g_heads
+ * Outputs go to fg_mlp_grads in the layout nn.Linear stores: weight[0] [256, in_ch], weight[5] [256, in_ch + 256] (the input
+ * columns in front), the other weights [256, 256], bias[l] [256], head_weight[h] [head_rows[h], 256], head_bias[h]
+ * [head_rows[h]].  Every pointer in it is nullable: a null entry is not formed and nothing is written for it; all null is
+ * FG_OK and launches nothing.  The descriptor supplies the shape only (size, mode = FG_MLP_PLAIN, depth, width, multires,
+ * aux_width, n_heads, head_rows): its parameter and input pointers are not read and may be null.  An input array may be
+ * null where no gradient asked for reads it (enc: weight[0], weight[5]; acts: weight[1..7], head weights; g_pre: trunk
+ * weights and biases; g_heads: head weights and biases); enc, acts and g_pre are 16-byte aligned.
+ *   Matrix instructions: v_mfma_f32_32x32x2_f32 (exact fp32) for the hidden and input products -- the A lane (i, k) takes
+ *     P[row k][col i], the B lane (k, j) in[row k][col j], so both operands are read along the rows as stored and nothing is
+ *     transposed -- and v_mfma_f32_16x16x4_f32 for the 16-wide head cotangents.  All accumulation is fp32.
+ *   Deterministic, no atomics: the rows are cut into slabs; each slab's partial results go to the workspace with plain
+ *     stores; a second launch of the same call adds the partials in slab order and writes the outputs.  Two runs on the
+ *     same inputs are bit for bit equal.
+ *   The cut depends on N alone, never on the device or its load: fg_mlp_param_grads_slab_rows(N) rows per slab -- a multiple
+ *     of 64, at most FG_MLP_WGRAD_MAX_SLAB = 4096, the slabs as equal as that allows; max(ceil(N / 4096), min(32, ceil(N / 512)))
+ *     slabs at the most, so below 131 072 rows the slabs are shorter and a small N still fills the machine.
+ *   Chain length: an output element of a slab is one fmaf chain over the slab's rows in row order: never more than 4096 terms
+ *     (half the 8192-row chunk of the library path it replaces).
+ *   Bias sums are formed in the pass that reads g_pre / g_heads for the products (from the staged operand tile); a bias
+ *     whose weight is null reads its P_l once.
+ *   Rows >= N are never read (acts[l] is followed directly by acts[l + 1]); the pad columns k >= in_ch of enc never reach
+ *     an output.  The rows of weight[0] / weight[5] have strides in_ch / in_ch + 256, odd for odd aux widths: outputs are
+ *     written with scalar stores, no alignment is assumed.
+ * The workspace: 16-byte aligned, fg_mlp_param_grads_workspace_bytes(N) bytes = 2 121 792 bytes per slab of the bound above
+ * (FG_ERR_WORKSPACE below that; 0 for N <= 0).  N == 0 does nothing.  FG_ERR_INVALID_ARG: negative N, a null desc, a null
+ * input whose product is asked for, a null out, wrong size fields, aux_width outside 1..64, head rows outside 1..16 (or more
+ * than 16 together), mode other than FG_MLP_PLAIN, a null or misaligned workspace; FG_ERR_UNSUPPORTED: depth / width /
+ * multires other than 8 / 256 / 10.  Asynchronous and capturable in a graph. */
+#define FG_MLP_WGRAD_MAX_SLAB 4096 /* rows of the longest slab */
+#define FG_MLP_WGRAD_MIN_SPLIT 512 /* up to 32 slabs of about N / 32 rows, none cut below this */
+typedef struct fg_mlp_grads {
+  int32_t size; /* sizeof(fg_mlp_grads) */
+  int32_t reserved;
+  float* weight[8];
+  float* bias[8];
+  float* head_weight[FG_MLP_MAX_HEADS];
+  float* head_bias[FG_MLP_MAX_HEADS];
+} fg_mlp_grads;
+size_t fg_mlp_param_grads_workspace_bytes(int64_t N);
+int fg_mlp_param_grads_slab_rows(int64_t N);
+int fg_mlp_param_grads(int64_t N, const fg_mlp_desc* desc, const float* enc, const float* acts, const float* g_pre,
+                       const float* g_heads, const fg_mlp_grads* out, void* workspace, size_t workspace_bytes,
+                       fg_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -29,6 +29,19 @@ the non-blender net only, and tests/test_mlp_inputs_gpu.py holds this path to fl
     --step kernel  ``fg_mlp_bwd`` and ``fg_mlp_bwd_inputs`` on the same saved activations and head cotangents at N = 240 000,
                    alternating call by call between device events (each call: its weight re-ordering launches and the
                    kernel); the trace step runs both as well, so that the kernel table holds each kernel's own time
+
+``--wgrad`` measures the fused parameter-gradient call (``fg_mlp_param_grads``; knob ``FG_FUSED_MLP_WGRAD=1`` on top of
+``FG_FUSED_MLP_TRAIN``) against the library products it replaces (``deform.mlp_param_grads``: the knob unset, the same
+build) and writes profiles/mlp_wgrad.md.  Its steps, each a child process as above:
+
+    --step wcall   the call alone against ``deform.mlp_param_grads`` on the same random arrays (the tests' generators) at
+                   N = 33 000, 240 000, 1 000 000 for aux widths 21 and 30, alternating call by call
+    --step werror  both at N = 33 000 against ``deform.mlp_param_grads`` of the same arrays in float64 on the CPU
+    --step wtrain  the whole ``ops.mlp_train`` forward + backward through the module, ``FG_FUSED_MLP_WGRAD`` set and unset,
+                   under ``FG_FUSED_MLP_TRAIN=1`` (and, with --blender, the blender net under ``=2``)
+    --step wmodel  the model training step of --step model, the knob set and unset (with --blender: the default model)
+    --step wtrace  three calls of each side at N = 240 000, both aux widths, for ``rocprofv3 --kernel-trace --stats``
+    --step wreport profiles/mlp_wgrad.md; --parity: a ``FG_PARITY_REPORT`` file of tests/test_mlp_wgrad_gpu.py
 """
 import argparse
 import copy
@@ -291,6 +304,227 @@ def _ms(q):
     return f"{q['median']:.3f} ({q['p10']:.3f} .. {q['p90']:.3f})"
 
 
+# ---- --wgrad: the fused parameter-gradient call ---------------------------------------------------------------------------
+WGRAD_KNOB = "FG_FUSED_MLP_WGRAD"
+WGRAD_ROWS = (3, 3, 4, 3)
+WGRAD_FLOP_PER_ROW = 2 * 256 * (7 * 256 + 16)  # + 2 x 2 x 256 x in_ch for the two input products
+
+
+def _wgrad_arrays(n, A, seed=0):
+    """The generators of tests/test_mlp_wgrad_gpu.py, on the device: (enc, H, G, g_heads)."""
+    from freegaussian_amd import _lib
+
+    g = torch.Generator(device="cuda").manual_seed(1000 * A + seed)
+    enc = torch.rand(n, _lib.mlp_enc_width(A), generator=g, device="cuda") * 2 - 1
+    enc[:, 63 + A :] = 0.0
+    H = torch.randn(8, n, 256, generator=g, device="cuda").relu_()
+    G = torch.randn(8, n, 256, generator=g, device="cuda")
+    for l in range(8):  # (layer by layer: no second [8, N, 256] temporary at a million rows)
+        G[l] *= (torch.rand(n, 256, generator=g, device="cuda") < 0.5) * 1e-3
+    return enc, H, G, torch.randn(n, sum(WGRAD_ROWS), generator=g, device="cuda") * 1e-3
+
+
+def _wgrad_pair(enc, H, G, gh, A):
+    from freegaussian_amd import deform, ops
+
+    def run_fused():
+        return ops.mlp_param_grads(enc, H, G, gh, A, WGRAD_ROWS)
+
+    def run_lib():  # what _MlpTrain.backward does with the knob unset, the column copy of enc included
+        return deform.mlp_param_grads(enc[:, : 63 + A], H, G, gh, WGRAD_ROWS)
+
+    return run_fused, run_lib
+
+
+def wstep_call(out):
+    from freegaussian_amd import _lib, ops
+
+    res = {}
+    for A in (21, 30):
+        for n in SIZES:
+            arrays = _wgrad_arrays(n, A)
+            run_fused, run_lib = _wgrad_pair(*arrays, A)
+            f, p = _timed_pair(run_fused, run_lib)
+            qf, qp = _quantiles(f), _quantiles(p)
+            fl = (WGRAD_FLOP_PER_ROW + 4 * 256 * (63 + A)) * n
+            res[f"{A},{n}"] = {"aux_width": A, "n": n, "fused_ms": qf, "lib_ms": qp, "ratio": qf["median"] / qp["median"],
+                               "fused_tflops": fl / qf["median"] / 1e9, "lib_tflops": fl / qp["median"] / 1e9,
+                               "slab_rows": ops.mlp_wgrad_slab_rows(n), "slabs": -(-n // ops.mlp_wgrad_slab_rows(n)),
+                               "workspace_mb": int(_lib.load().fg_mlp_param_grads_workspace_bytes(n)) / 1e6}  # fmt: skip
+            print(res[f"{A},{n}"], flush=True)
+            del arrays, run_fused, run_lib
+            torch.cuda.empty_cache()
+    json.dump(res, open(os.path.join(out, "wcall.json"), "w"), indent=1)
+
+
+def wstep_error(out):
+    from freegaussian_amd import deform
+
+    n, res = 33_000, {}
+
+    def rel(a, b):
+        return float((a.double().cpu() - b).abs().max() / b.abs().max())
+
+    for A in (21, 30):
+        enc, H, G, gh = _wgrad_arrays(n, A)
+        run_fused, run_lib = _wgrad_pair(enc, H, G, gh, A)
+        want = deform.mlp_param_grads(enc[:, : 63 + A].double().cpu(), H.double().cpu(), G.double().cpu(), gh.double().cpu(), WGRAD_ROWS)
+        for name, got in (("fused", run_fused()), ("library", run_lib())):
+            for kind, gs, ws in zip(("trunk weights", "trunk biases", "head weights", "head biases"), got, want):
+                res.setdefault(f"{kind}, aux width {A}", {})[name] = max(rel(g, w) for g, w in zip(gs, ws))
+    print(res, flush=True)
+    json.dump(res, open(os.path.join(out, "werror.json"), "w"), indent=1)
+
+
+def _wgrad_knob(on):
+    if on:
+        os.environ[WGRAD_KNOB] = "1"
+    else:
+        os.environ.pop(WGRAD_KNOB, None)
+
+
+def _count_wgrad_calls():
+    from freegaussian_amd import ops
+
+    calls = []
+    real = ops.mlp_param_grads
+    ops.mlp_param_grads = lambda *a, **k: calls.append(1) or real(*a, **k)
+    return calls
+
+
+def wstep_train(out):
+    m = _module().cuda()
+    _knob(True)
+    calls, res = _count_wgrad_calls(), {}
+    for n in SIZES:
+        g = torch.Generator().manual_seed(n)
+        x = (torch.rand(n, 3, generator=g) * 2 - 1).cuda()
+        t = torch.full((1, 1), 0.4, device="cuda").expand(n, -1)
+        cots = [torch.randn(n, *s, generator=g).cuda() for s in ((4, 4), (4,), (3,))]
+
+        def run(on):
+            def go():
+                _wgrad_knob(on)
+                _train_call(m, x, t, cots)
+            return go
+
+        before = len(calls)
+        f, p = _timed_pair(run(True), run(False))
+        assert len(calls) - before == WARM + TIMED  # the knob's side made the fused call, the other never
+        qf, qp = _quantiles(f), _quantiles(p)
+        res[str(n)] = {"on_ms": qf, "off_ms": qp, "ratio": qf["median"] / qp["median"]}
+        print(n, res[str(n)], flush=True)
+    json.dump(res, open(os.path.join(out, "wtrain_blender.json" if BLENDER else "wtrain.json"), "w"), indent=1)
+
+
+def wstep_model(out):
+    from freegaussian_amd.model import Camera, FreeGaussianModel, FreeGaussianModelConfig
+    from freegaussian_amd.scenes import look_at_viewmat
+
+    torch.manual_seed(0)
+    n, W, H = 240_000, 960, 540
+    cfg = FreeGaussianModelConfig(background_color="white", num_downscales=0, warm_up=3000)
+    model = FreeGaussianModel(cfg, seed_points=(torch.rand(n, 3) - 0.5) * 2.0, init_scales=-4.5, is_blender=BLENDER)
+    with torch.no_grad():
+        for q in model.deform.parameters():
+            q.mul_(0.3)
+    model.step = 4000
+    model = model.cuda().train()
+    c2w = torch.linalg.inv(look_at_viewmat(torch.tensor([0.3, -0.2, -3.0]), torch.zeros(3)))
+    c2w[:3, 1:3] *= -1
+    cam = Camera(c2w[None, :3], 750.0, 750.0, W / 2, H / 2, W, H, times=torch.tensor([[0.4]]))
+    gt = torch.rand(H, W, 3, device="cuda")
+    _knob(True)
+    calls = _count_wgrad_calls()
+
+    def step(on):
+        def run():
+            _wgrad_knob(on)
+            model.zero_grad(set_to_none=True)
+            model.get_loss_dict(model.get_outputs(cam), {"image": gt})["main_loss"].backward()
+        return run
+
+    warm, timed = 5, 30
+    f, p = _timed_pair(step(True), step(False), warm=warm, timed=timed)
+    assert len(calls) == warm + timed
+    res = {"n": n, "width": W, "height": H, "on_ms": _quantiles(f), "off_ms": _quantiles(p)}
+    print(res, flush=True)
+    json.dump(res, open(os.path.join(out, "wmodel_blender.json" if BLENDER else "wmodel.json"), "w"), indent=1)
+
+
+def wstep_trace(out):
+    for A in (21, 30):
+        arrays = _wgrad_arrays(240_000, A)
+        run_fused, run_lib = _wgrad_pair(*arrays, A)
+        for _ in range(3):
+            run_fused()
+            run_lib()
+        torch.cuda.synchronize()
+
+
+def wstep_report(out, md, parity):
+    from freegaussian_amd.deform import FUSED_MIN_ROWS
+
+    call = json.load(open(os.path.join(out, "wcall.json")))
+    L = ["# Fused parameter-gradient call (`fg_mlp_param_grads`, `FG_FUSED_MLP_WGRAD=1`) against the library products", "",
+         "Written by `scripts/mlp_train_bench.py --wgrad` on an MI355X.  The baseline of every table is the knob-unset path of the",
+         "same build (`deform.mlp_param_grads`: the chunked library products and their reductions), never an earlier figure.",
+         f"One process per table, {WARM} warm-up and {TIMED} timed calls each between device events, the two sides alternating call by call.", "",
+         "## (a) The call alone, on the same arrays (the generators of tests/test_mlp_wgrad_gpu.py; head rows (3, 3, 4, 3))", "",
+         "TFLOP/s: the products' 2 x 256 x (7 x 256 + 2 x in_ch + 16) FLOP per row over the call's time (of the "
+         f"{PEAK_TF:.0f} TFLOP/s fp32 matrix peak).", "",
+         "| aux width | N | slabs x rows | workspace MB | fused ms median (p10 .. p90) | library ms median (p10 .. p90) | fused / library | "
+         "fused TFLOP/s | library TFLOP/s |", "|---|---|---|---|---|---|---|---|---|"]  # fmt: skip
+    for r in call.values():
+        L.append(f"| {r['aux_width']} | {r['n']:,} | {r['slabs']} x {r['slab_rows']} | {r['workspace_mb']:.0f} | {_ms(r['fused_ms'])} | "
+                 f"{_ms(r['lib_ms'])} | {r['ratio']:.2f} | {r['fused_tflops']:.1f} | {r['lib_tflops']:.1f} |")  # fmt: skip
+    at = [r for r in call.values() if r["n"] == 240_000]
+    gain = all(r["fused_ms"]["median"] < r["lib_ms"]["median"] and r["fused_ms"]["p90"] < r["lib_ms"]["p10"] for r in at)
+    wins = sorted({r["n"] for r in call.values()
+                   if all(q["fused_ms"]["p90"] < q["lib_ms"]["p10"] for q in call.values() if q["n"] == r["n"])})
+    L += ["", "**Outcome by the rule set for this call** (at 240 000 rows: the fused median below the library's with non-overlapping p10 .. p90, both "
+          "aux widths): " + ("a gain." if gain else "NO gain is claimed; the call stays (it is correct and deterministic).")
+          + f"  Sizes at which the fused call wins by that rule for both widths: {', '.join(f'{n:,}' for n in wins) or 'none'}."
+          + f"  The knob stays opt-in either way; a fused training call sees at least `deform.FUSED_MIN_ROWS` = {FUSED_MIN_ROWS:,} rows."]  # fmt: skip
+    for name, title in (("wtrain.json", "deformation net, `FG_FUSED_MLP_TRAIN=1`"), ("wtrain_blender.json", "blender net, `FG_FUSED_MLP_TRAIN=2`")):
+        if os.path.exists(os.path.join(out, name)):
+            tr = json.load(open(os.path.join(out, name)))
+            L += ["", f"## (b) The whole `ops.mlp_train` forward + backward through the module ({title})", "",
+                  f"| N | `{WGRAD_KNOB}=1` ms median (p10 .. p90) | unset ms median (p10 .. p90) | set / unset |", "|---|---|---|---|"]
+            L += [f"| {int(n):,} | {_ms(r['on_ms'])} | {_ms(r['off_ms'])} | {r['ratio']:.2f} |" for n, r in tr.items()]
+    for name, title in (("wmodel.json", "non-blender net, `FG_FUSED_MLP_TRAIN=1`"), ("wmodel_blender.json", "the default model -- the blender net -- `FG_FUSED_MLP_TRAIN=2`")):
+        if os.path.exists(os.path.join(out, name)):
+            fr = json.load(open(os.path.join(out, name)))
+            L += ["", f"## (c) Model training step (`get_outputs` + `get_loss_dict` + backward; {fr['n']:,} random Gaussians behind `warm_up`, "
+                  f"{fr['width']} x {fr['height']}; {title})", "", "| knob | ms per step median (p10 .. p90) |", "|---|---|",
+                  f"| `{WGRAD_KNOB}` unset | {_ms(fr['off_ms'])} |", f"| `{WGRAD_KNOB}=1` | {_ms(fr['on_ms'])} |"]  # fmt: skip
+    stats = sorted(glob.glob(os.path.join(out, "wtrace", "**", "*kernel_stats.csv"), recursive=True))
+    if stats:
+        L += ["", "## (d) Kernels of three calls of each side at N = 240 000, aux widths 21 and 30 (`rocprofv3 --kernel-trace --stats`, a run "
+              "of its own; no counters)", "", "| kernel | calls | average us | share % |", "|---|---|---|---|"]  # fmt: skip
+        for r in list(csv.DictReader(open(stats[0])))[:14]:
+            L.append(f"| `{r['Name'][:80]}` | {r['Calls']} | {float(r['AverageNs']) / 1e3:.1f} | {float(r['Percentage']):.1f} |")
+    if os.path.exists(os.path.join(out, "werror.json")):
+        er = json.load(open(os.path.join(out, "werror.json")))
+        L += ["", "## (e) Error against float64 at N = 33 000 (`deform.mlp_param_grads` of the same arrays in float64 on the CPU; "
+              "max |a - b| / max |b|, worst array; the bar is 1e-4)", "", "| | fused call | library products (fp32) |", "|---|---|---|"]  # fmt: skip
+        L += [f"| {k} | {v['fused']:.2e} | {v['library']:.2e} |" for k, v in er.items()]
+    if parity and os.path.exists(parity):
+        worst = {}
+        for line in open(parity):
+            r = json.loads(line)
+            if "test_mlp_wgrad_gpu.py" in r["test"] and r["kind"] == "rel_err":
+                name = r["test"].split("::")[1].split("[")[0]
+                worst[name] = max(worst.get(name, 0.0), r["value"])
+        L += ["", "## Margins of tests/test_mlp_wgrad_gpu.py (`FG_PARITY_REPORT`: the largest `rel_err` each test saw; the bar is 1e-4)", "",
+              "| test | largest rel_err |", "|---|---|"]  # fmt: skip
+        L += [f"| `{k}` | {v:.2e} |" for k, v in sorted(worst.items())]
+    if os.path.exists(md) and "\n## Notes" in open(md).read():
+        L += ["", "## Notes" + open(md).read().split("\n## Notes", 1)[1].rstrip()]
+    open(md, "w").write("\n".join(L) + "\n")
+    print("\n".join(L))
+
+
 def step_report_inputs(out, md, parity):
     """profiles/mlp_train_inputs.md (--blender)."""
     from freegaussian_amd.deform import FUSED_MIN_ROWS
@@ -416,7 +650,9 @@ def step_report(out, md, parity):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--step", choices=["time", "error", "model", "trace", "kernel", "report"])
+    ap.add_argument("--step", choices=["time", "error", "model", "trace", "kernel", "report", "wcall", "werror", "wtrain", "wmodel",
+                                       "wtrace", "wreport"])  # fmt: skip
+    ap.add_argument("--wgrad", action="store_true", help="the fused parameter-gradient call, FG_FUSED_MLP_WGRAD (profiles/mlp_wgrad.md)")
     ap.add_argument("--blender", action="store_true", help="the blender net under FG_FUSED_MLP_TRAIN=2 (profiles/mlp_train_inputs.md)")
     ap.add_argument("--trace", action="store_true", help="also one rocprofv3 --kernel-trace --stats run of the fused calls")
     ap.add_argument("--parity", default=None, help="FG_PARITY_REPORT file to quote: of tests/test_mlp_train_gpu.py, with --blender of tests/test_mlp_inputs_gpu.py")
@@ -426,21 +662,36 @@ def main():
     global BLENDER
     BLENDER = a.blender
     name = "mlp_train_inputs" if BLENDER else "mlp_train"
+    if a.wgrad or (a.step or "").startswith("w"):
+        name = "mlp_wgrad"
     a.out = a.out or os.path.join(ROOT, "results", name)
     a.md = a.md or os.path.join(ROOT, "profiles", name + ".md")
     os.makedirs(a.out, exist_ok=True)
     if a.step:
         if a.step == "report":
             return step_report(a.out, a.md, a.parity)
+        if a.step == "wreport":
+            return wstep_report(a.out, a.md, a.parity)
+        if a.step.startswith("w"):
+            return {"wcall": wstep_call, "werror": wstep_error, "wtrain": wstep_train, "wmodel": wstep_model, "wtrace": wstep_trace}[a.step](a.out)
         return {"time": step_time, "error": step_error, "model": step_model, "trace": step_trace, "kernel": step_kernel}[a.step](a.out)
     me = [sys.executable, os.path.abspath(__file__), "--out", a.out, "--md", a.md] + (["--blender"] if BLENDER else []) + ["--step"]
     steps = [(300, me + ["time"]), (180, me + ["error"]), (240, me + ["model"])]
     if BLENDER:
         steps = [(300, me + ["time"]), (120, me + ["kernel"]), (240, me + ["model"])]
-    if a.trace:
+    if a.wgrad:
+        me = [sys.executable, os.path.abspath(__file__), "--out", a.out, "--md", a.md, "--step"]
+        steps = [(240, me + ["wcall"]), (120, me + ["werror"]), (180, me + ["wtrain"]), (180, me + ["wtrain", "--blender"]),
+                 (240, me + ["wmodel"]), (240, me + ["wmodel", "--blender"])]  # fmt: skip
+        if a.trace:
+            steps.append((180, ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", os.path.join(a.out, "wtrace"),
+                                "-o", "mlp", "--"] + me + ["wtrace"]))  # fmt: skip
+        steps.append((60, me + ["wreport"] + (["--parity", a.parity] if a.parity else [])))
+    elif a.trace:
         steps.append((180, ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", os.path.join(a.out, "trace"),
                             "-o", "mlp", "--"] + me + ["trace"]))  # fmt: skip
-    steps.append((60, me + ["report"] + (["--parity", a.parity] if a.parity else [])))
+    if not a.wgrad:
+        steps.append((60, me + ["report"] + (["--parity", a.parity] if a.parity else [])))
     for limit, cmd in steps:  # chained like &&: the first failure ends the job
         rc = subprocess.call(["timeout", "-k", "10", str(limit)] + cmd)
         if rc != 0:
