@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_void_p
+from ctypes import c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libfgraster.so")
@@ -17,6 +17,7 @@ P = c_void_p
 # name -> (restype, argtypes); must list every symbol of include/fgraster.h
 SIGNATURES = {
     "fg_abi_version": (c_int, []),
+    "fg_abi_minor": (c_int, []),
     "fg_error_string": (c_char_p, [c_int]),
     "fg_project_fwd": (c_int, [c_int, P, P, P, P, P, c_int, c_int, c_float, c_float, c_float, c_float, c_int,
                                P, P, P, P, P, P, P]),
@@ -114,17 +115,23 @@ SIGNATURES = {
     "fg_mlp_param_grads_slab_rows": (c_int, [c_int64]),
     # (N, desc, enc, acts, g_pre, g_heads, const fg_mlp_grads*, workspace, bytes, stream)
     "fg_mlp_param_grads": (c_int, [c_int64, P, P, P, P, P, P, P, c_size_t, P]),
+    "fg_mlp_train_bwd_chunk_rows": (c_int64, [c_int64, c_int32]),  # (N, chunk_slabs)
+    "fg_mlp_train_bwd_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32]),  # (N, chunk_slabs, want_g_enc)
+    # (N, desc, g_heads, enc, acts, g_enc, const fg_mlp_grads*, chunk_slabs, workspace, bytes, stream)
+    "fg_mlp_train_bwd": (c_int, [c_int64, P, P, P, P, P, P, c_int32, P, c_size_t, P]),
 }  # fmt: skip
 
 # test hooks, not declared in the public header
 _EXTRA = {"fg_debug_wave_reduce16": (c_int, [P, P, P]), "fg_debug_knn_grid": (c_int, [c_int64, P, c_int, P, P])}
 
 ABI_VERSION = 14
+ABI_MINOR = 1  # FG_ABI_MINOR: the least the binding needs (symbols added without raising FG_ABI_VERSION)
 KNN_MAX_K = 8  # FG_KNN_MAX_K
 MLP_ROW_TILE = 64  # FG_MLP_ROW_TILE
 MLP_MAX_HEADS = 4  # FG_MLP_MAX_HEADS
 MLP_SE3, MLP_PLAIN = 0, 1  # FG_MLP_SE3, FG_MLP_PLAIN
 MLP_WGRAD_MAX_SLAB, MLP_WGRAD_MIN_SPLIT = 4096, 512  # FG_MLP_WGRAD_MAX_SLAB, FG_MLP_WGRAD_MIN_SPLIT
+MLP_TRAIN_BWD_CHUNK_SLABS = 16  # FG_MLP_TRAIN_BWD_CHUNK_SLABS
 
 
 def mlp_enc_width(aux_width: int) -> int:
@@ -235,6 +242,8 @@ def load() -> ctypes.CDLL:
         fn.argtypes = args
     if lib.fg_abi_version() != ABI_VERSION:
         raise FgRasterError(f"ABI mismatch: library {lib.fg_abi_version()} vs binding {ABI_VERSION}")
+    if ABI_MINOR and lib.fg_abi_minor() < ABI_MINOR:
+        raise FgRasterError(f"ABI mismatch: library minor {lib.fg_abi_minor()} below the binding's {ABI_MINOR}")
     _lib = lib
     return lib
 

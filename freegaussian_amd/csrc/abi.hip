@@ -2,6 +2,7 @@
 #include "fg_common.h"
 
 extern "C" int fg_abi_version(void) { return FG_ABI_VERSION; }
+extern "C" int fg_abi_minor(void) { return FG_ABI_MINOR; }
 
 extern "C" const char* fg_error_string(int code) {
   switch (code) {

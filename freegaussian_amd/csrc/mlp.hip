@@ -41,6 +41,7 @@
 #include <cmath>
 
 #include "fg_common.h"
+#include "mlp_internal.h"
 
 namespace {
 
@@ -399,17 +400,21 @@ mlp_fwd_kernel(int64_t N, MlpArgs p, MlpLayout L, const float* __restrict__ ws, 
   }
 }
 
-// INPUTS: also g_enc [N, enc_w] = P_5 W_5[:, :in_ch] + P_0 W_0 from `tin` (fg_mlp_bwd_inputs); false: neither is looked at, and
-// the code is the backward kernel's of before, instruction for instruction
+// INPUTS: also g_enc [N, enc_w] = P_5 W_5[:, :in_ch] + P_0 W_0 from `tin` (fg_mlp_bwd_inputs); false: neither is looked at.
+// A launch takes the rows from tile tile_begin up to row N (the END of its rows, not of the arrays; acts_rows = the rows of a
+// layer of acts): g_heads, acts and g_enc are addressed by the row itself, g_pre by the row less the launch's first with
+// pre_rows rows to a layer -- fg_mlp_train_bwd's chunk array; the whole-array calls pass tile_begin = 0 and acts_rows =
+// pre_rows = N.  (The first tile as a 32-bit argument: the kernel sits at the scalar-register limit, and a 64-bit first row
+// cost <true> two vector registers over its 224 -- profiles/mlp_chunked_bwd.md.)
 template <bool INPUTS>
 __global__ void __launch_bounds__(MLP_BLOCK) __attribute__((amdgpu_waves_per_eu(INPUTS ? 2 : 1)))
-mlp_bwd_kernel(int64_t N, int rows_total, const float* __restrict__ g_heads, const float* __restrict__ acts,
-               float* __restrict__ g_pre, const float* __restrict__ ws, const float* __restrict__ tin,
-               float* __restrict__ g_enc, int in_ch, int enc_w) {
+mlp_bwd_kernel(int64_t N, int tile_begin, int64_t acts_rows, int64_t pre_rows, int rows_total, const float* __restrict__ g_heads,
+               const float* __restrict__ acts, float* __restrict__ g_pre, const float* __restrict__ ws,
+               const float* __restrict__ tin, float* __restrict__ g_enc, int in_ch, int enc_w) {
   __shared__ __attribute__((aligned(16))) float grad[MLP_M * MLP_ACT_STRIDE];
   __shared__ __attribute__((aligned(16))) float gh[MLP_M * MLP_GH_STRIDE];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int64_t row0 = (int64_t)blockIdx.x * MLP_M;
+  const int64_t row_begin = (int64_t)tile_begin * MLP_M, row0 = row_begin + (int64_t)blockIdx.x * MLP_M;
 
   // ---- the head cotangents: [64][16], zero beyond rows_total and beyond N
   for (int i = tid; i < MLP_M * 16; i += MLP_BLOCK) {
@@ -431,8 +436,9 @@ mlp_bwd_kernel(int64_t N, int rows_total, const float* __restrict__ g_heads, con
   mlp_gemm_part(acc, gh + li * MLP_GH_STRIDE + 4 * lh, MLP_GH_STRIDE, 2, ws + MLP_T_HEAD + b_lane);  // g(h_7)
   for (int l = MLP_D - 1; l >= 0; --l) {
     // P_l = g(h_l) where h_l > 0: to g_pre and, for the next product, in place of the previous tile
-    const float* h = acts + (int64_t)l * N * MLP_W;
-    float* out = g_pre + (int64_t)l * N * MLP_W;
+    const float* h = acts + (int64_t)l * acts_rows * MLP_W;
+    // (row_begin taken off the layer's base, a scalar: the row offsets below are the ones acts is read with)
+    float* out = g_pre + ((int64_t)l * pre_rows - row_begin) * MLP_W;
     for (int rb = 0; rb < 2; ++rb)
       for (int cb = 0; cb < 2; ++cb)
 #pragma unroll
@@ -571,32 +577,51 @@ extern "C" int fg_mlp_train_fwd(int64_t N, const fg_mlp_desc* d, float* heads, f
   return mlp_launch_fwd<true>(N, mlp_args(d), sv, workspace, stream);
 }
 
-namespace {
+// ---- what fg_mlp_train_bwd (mlp_wgrad.hip) shares with the two calls below: mlp_internal.h
+int fg_mlp_detail::bwd_check(int64_t N, const fg_mlp_desc* d, const void* workspace, size_t workspace_bytes, size_t need) {
+  if (int rc = mlp_check_desc(d, false)) return rc;
+  if (d->mode != FG_MLP_PLAIN) return FG_ERR_INVALID_ARG;
+  return need ? mlp_check_launch(N, workspace, workspace_bytes, need) : FG_OK;
+}
 
-// the launches of fg_mlp_bwd (g_enc null) and fg_mlp_bwd_inputs: the packed weights, then the chain
-int mlp_launch_bwd(int64_t N, const fg_mlp_desc* d, const float* g_heads, const float* acts, float* g_pre, float* g_enc,
-                   void* workspace, fg_stream_t stream) {
+int fg_mlp_detail::bwd_launch_pack(const fg_mlp_desc* d, bool inputs, void* workspace, fg_stream_t stream) {
   const MlpArgs p = mlp_args(d);
+  hipStream_t s = fg_hip_stream(stream);
+  float* ws = static_cast<float*>(workspace);
+  hipLaunchKernelGGL(mlp_pack_t_kernel, dim3((unsigned)((MLP_T_TOTAL + MLP_BLOCK - 1) / MLP_BLOCK)), dim3(MLP_BLOCK), 0, s, p, ws);
+  FG_RETURN_IF_LAUNCH_FAILED();
+  if (!inputs) return FG_OK;
+  hipLaunchKernelGGL(mlp_pack_tin_kernel, dim3((unsigned)((MLP_TIN_TOTAL + MLP_BLOCK - 1) / MLP_BLOCK)), dim3(MLP_BLOCK), 0, s, p,
+                     ws + MLP_T_TOTAL);
+  FG_RETURN_IF_LAUNCH_FAILED();
+  return FG_OK;
+}
+
+int fg_mlp_detail::bwd_launch_rows(int64_t N, const fg_mlp_desc* d, int64_t row_begin, int64_t row_end, const float* g_heads,
+                                   const float* acts, float* g_pre, int64_t pre_rows, float* g_enc, const void* workspace,
+                                   fg_stream_t stream) {
   int rows_total = 0;
   for (int h = 0; h < d->n_heads; ++h) rows_total += d->head_rows[h];
   hipStream_t s = fg_hip_stream(stream);
-  float* ws = static_cast<float*>(workspace);
-  const dim3 tiles((unsigned)((N + MLP_M - 1) / MLP_M));
-  hipLaunchKernelGGL(mlp_pack_t_kernel, dim3((unsigned)((MLP_T_TOTAL + MLP_BLOCK - 1) / MLP_BLOCK)), dim3(MLP_BLOCK), 0, s, p, ws);
-  FG_RETURN_IF_LAUNCH_FAILED();
-  if (!g_enc) {
-    hipLaunchKernelGGL(mlp_bwd_kernel<false>, tiles, dim3(MLP_BLOCK), 0, s, N, rows_total, g_heads, acts, g_pre, ws, nullptr, nullptr,
-                       0, 0);
-    FG_RETURN_IF_LAUNCH_FAILED();
-    return FG_OK;
-  }
-  float* tin = ws + MLP_T_TOTAL;
-  hipLaunchKernelGGL(mlp_pack_tin_kernel, dim3((unsigned)((MLP_TIN_TOTAL + MLP_BLOCK - 1) / MLP_BLOCK)), dim3(MLP_BLOCK), 0, s, p, tin);
-  FG_RETURN_IF_LAUNCH_FAILED();
-  hipLaunchKernelGGL(mlp_bwd_kernel<true>, tiles, dim3(MLP_BLOCK), 0, s, N, rows_total, g_heads, acts, g_pre, ws, tin, g_enc,
-                     MLP_XCH + p.A, FG_MLP_ENC_WIDTH(p.A));
+  const float* ws = static_cast<const float*>(workspace);
+  const dim3 tiles((unsigned)((row_end - row_begin + MLP_M - 1) / MLP_M));
+  if (!g_enc)
+    hipLaunchKernelGGL(mlp_bwd_kernel<false>, tiles, dim3(MLP_BLOCK), 0, s, row_end, (int)(row_begin / MLP_M), N, pre_rows, rows_total, g_heads, acts,
+                       g_pre, ws, nullptr, nullptr, 0, 0);
+  else
+    hipLaunchKernelGGL(mlp_bwd_kernel<true>, tiles, dim3(MLP_BLOCK), 0, s, row_end, (int)(row_begin / MLP_M), N, pre_rows, rows_total, g_heads, acts,
+                       g_pre, ws, ws + MLP_T_TOTAL, g_enc, MLP_XCH + d->aux_width, FG_MLP_ENC_WIDTH(d->aux_width));
   FG_RETURN_IF_LAUNCH_FAILED();
   return FG_OK;
+}
+
+namespace {
+
+// the launches of fg_mlp_bwd (g_enc null) and fg_mlp_bwd_inputs: the packed weights, then the chain over all the rows
+int mlp_launch_bwd(int64_t N, const fg_mlp_desc* d, const float* g_heads, const float* acts, float* g_pre, float* g_enc,
+                   void* workspace, fg_stream_t stream) {
+  if (int rc = fg_mlp_detail::bwd_launch_pack(d, g_enc != nullptr, workspace, stream)) return rc;
+  return fg_mlp_detail::bwd_launch_rows(N, d, 0, N, g_heads, acts, g_pre, N, g_enc, workspace, stream);
 }
 
 }  // namespace

@@ -32,6 +32,7 @@
 // Rows beyond a slab's end (so beyond N) are never read: both operand tiles hold zeros there.  Columns k >= in_ch of enc
 // are replaced by zeros as they are read.  Two runs on the same inputs are bit for bit equal, whatever else the device does.
 #include "fg_common.h"
+#include "mlp_internal.h"
 
 namespace {
 
@@ -80,7 +81,9 @@ struct WgArgs {
   const float* g_pre;
   const float* g_heads;
   float* ws;
-  int64_t N, n_slabs;
+  // the launch takes n_slabs slabs from slab0 on (the partial blocks sit at the slabs' own indices); g_pre has pre_rows rows
+  // to a layer and starts at row pre_row0 of the other arrays (fg_mlp_param_grads: 0, n_slabs = all, pre_rows = N)
+  int64_t N, n_slabs, slab0, pre_rows, pre_row0;
   int slab_rows, n_jobs;
   int in_ch, enc_w, rows_total;
   uint32_t jobs[WG_MAX_JOBS];
@@ -131,7 +134,8 @@ __device__ __forceinline__ void wg_tile_job(const WgArgs& p, uint32_t job, int64
   const uint32_t flags = job >> 16;
   const bool gemm = flags & WG_F_GEMM, bias = flags & WG_F_BIAS, from_enc = flags & WG_F_ENC;
 
-  const float* a_src = p.g_pre + (int64_t)l * p.N * WG_W;
+  const float* a_src = p.g_pre + (int64_t)l * p.pre_rows * WG_W;
+  const int64_t a_r0 = r0 - p.pre_row0, a_r1 = r1 - p.pre_row0;  // the slab's rows as g_pre counts them
   const float* b_src = from_enc ? p.enc : p.acts + (int64_t)(l > 0 ? l - 1 : 0) * p.N * WG_W;
   const int64_t b_ld = from_enc ? p.enc_w : WG_W;
   const int b_col0 = from_enc ? 0 : jt * WG_T;
@@ -149,14 +153,14 @@ __device__ __forceinline__ void wg_tile_job(const WgArgs& p, uint32_t job, int64
   const float* s_rd = As + (tid >> 7) * 16 * WG_STRIDE + (tid & 127);
 
   f32x4 va[4], vb[4];
-  wg_fetch(va, a_src, WG_W, r0, r1, it * WG_T, WG_T, tid);
+  wg_fetch(va, a_src, WG_W, a_r0, a_r1, it * WG_T, WG_T, tid);
   if (gemm) wg_fetch(vb, b_src, b_ld, r0, r1, b_col0, b_cols_ld, tid);
   for (int64_t row = r0; row < r1; row += WG_K) {
     wg_stage(As, va, WG_T, tid);
     if (gemm) wg_stage(Bs, vb, b_cols, tid);
     __syncthreads();
     if (row + WG_K < r1) {
-      wg_fetch(va, a_src, WG_W, row + WG_K, r1, it * WG_T, WG_T, tid);
+      wg_fetch(va, a_src, WG_W, row + WG_K - p.pre_row0, a_r1, it * WG_T, WG_T, tid);
       if (gemm) wg_fetch(vb, b_src, b_ld, row + WG_K, r1, b_col0, b_cols_ld, tid);
     }
     if (bias) {
@@ -250,7 +254,7 @@ __global__ void __launch_bounds__(WG_BLOCK) mlp_wgrad_kernel(WgArgs p) {
   const int64_t total = p.n_slabs * p.n_jobs, run = (total + 7) / 8;
   const int64_t id = (int64_t)(blockIdx.x & 7) * run + (blockIdx.x >> 3);
   if (id >= total) return;
-  const int64_t slab = id / p.n_jobs;
+  const int64_t slab = p.slab0 + id / p.n_jobs;
   const uint32_t job = p.jobs[id % p.n_jobs];
   const int64_t r0 = slab * p.slab_rows;
   const int64_t r1 = r0 + p.slab_rows < p.N ? r0 + p.slab_rows : p.N;
@@ -309,11 +313,12 @@ extern "C" int fg_mlp_param_grads_slab_rows(int64_t N) {
   return rows;
 }
 
-extern "C" int fg_mlp_param_grads(int64_t N, const fg_mlp_desc* d, const float* enc, const float* acts, const float* g_pre,
-                                  const float* g_heads, const fg_mlp_grads* out, void* workspace, size_t workspace_bytes,
-                                  fg_stream_t stream) {
-  if (N < 0) return FG_ERR_INVALID_ARG;
-  if (N == 0) return FG_OK;
+namespace {
+
+// The shape checks of the descriptor and `out`, then the jobs of one slab into p and the outputs into o; which inputs the
+// jobs read comes back in need_* (need_pre: g_pre).  p.n_jobs == 0: nothing is asked for.
+int wg_plan(const fg_mlp_desc* d, const fg_mlp_grads* out, WgArgs& p, WgOut& o, bool& need_enc, bool& need_acts, bool& need_pre,
+            bool& need_heads) {
   if (!d || d->size != (int32_t)sizeof(fg_mlp_desc)) return FG_ERR_INVALID_ARG;
   if (d->aux_width < 1 || d->aux_width > 64 || d->mode != FG_MLP_PLAIN) return FG_ERR_INVALID_ARG;
   if (d->n_heads < 1 || d->n_heads > FG_MLP_MAX_HEADS) return FG_ERR_INVALID_ARG;
@@ -326,10 +331,7 @@ extern "C" int fg_mlp_param_grads(int64_t N, const fg_mlp_desc* d, const float* 
   if (d->depth != WG_D || d->width != WG_W || d->multires != 10) return FG_ERR_UNSUPPORTED;
   if (!out || out->size != (int32_t)sizeof(fg_mlp_grads)) return FG_ERR_INVALID_ARG;
 
-  // the jobs of one slab, and which inputs they read
-  WgArgs p = {};
-  WgOut o = {};
-  bool need_enc = false, need_acts = false, need_pre = false, need_heads = false;
+  need_enc = need_acts = need_pre = need_heads = false;
   auto push = [&](uint32_t type, int l, int it, int jt, uint32_t flags) {
     p.jobs[p.n_jobs++] = type | (uint32_t)l << 4 | (uint32_t)it << 8 | (uint32_t)jt << 12 | flags << 16;
   };
@@ -361,6 +363,38 @@ extern "C" int fg_mlp_param_grads(int64_t N, const fg_mlp_desc* d, const float* 
   else if (head_b)
     push(WG_JOB_HEAD, 0, 0, 0, WG_F_BIAS);
   need_heads = head_w || head_b, need_acts |= head_w;
+  p.in_ch = WG_XCH + d->aux_width, p.enc_w = FG_MLP_ENC_WIDTH(d->aux_width), p.rows_total = rows_total;
+  o.n_heads = d->n_heads, o.in_ch = p.in_ch;
+  return FG_OK;
+}
+
+// the jobs of p over the slabs [slab0, slab0 + n_slabs), g_pre as p describes it
+int wg_launch_slabs(WgArgs p, int64_t slab0, int64_t n_slabs, fg_stream_t stream) {
+  p.slab0 = slab0, p.n_slabs = n_slabs;
+  hipLaunchKernelGGL(mlp_wgrad_kernel, dim3((unsigned)((n_slabs * p.n_jobs + 7) / 8 * 8)), dim3(WG_BLOCK), 0, fg_hip_stream(stream), p);
+  FG_RETURN_IF_LAUNCH_FAILED();
+  return FG_OK;
+}
+
+// the partial blocks of all n_slabs slabs, added in slab order, to the outputs
+int wg_launch_reduce(const float* ws, int64_t n_slabs, const WgOut& o, fg_stream_t stream) {
+  hipLaunchKernelGGL(mlp_wgrad_reduce_kernel, dim3((unsigned)((WG_SLAB_FLOATS + WG_BLOCK - 1) / WG_BLOCK)), dim3(WG_BLOCK), 0,
+                     fg_hip_stream(stream), ws, n_slabs, o);
+  FG_RETURN_IF_LAUNCH_FAILED();
+  return FG_OK;
+}
+
+}  // namespace
+
+extern "C" int fg_mlp_param_grads(int64_t N, const fg_mlp_desc* d, const float* enc, const float* acts, const float* g_pre,
+                                  const float* g_heads, const fg_mlp_grads* out, void* workspace, size_t workspace_bytes,
+                                  fg_stream_t stream) {
+  if (N < 0) return FG_ERR_INVALID_ARG;
+  if (N == 0) return FG_OK;
+  WgArgs p = {};
+  WgOut o = {};
+  bool need_enc, need_acts, need_pre, need_heads;
+  if (int rc = wg_plan(d, out, p, o, need_enc, need_acts, need_pre, need_heads)) return rc;
   if (p.n_jobs == 0) return FG_OK;
   if ((need_enc && !enc) || (need_acts && !acts) || (need_pre && !g_pre) || (need_heads && !g_heads)) return FG_ERR_INVALID_ARG;
   // (the operand tiles are fetched 16 bytes at a time)
@@ -375,14 +409,81 @@ extern "C" int fg_mlp_param_grads(int64_t N, const fg_mlp_desc* d, const float* 
   if (reinterpret_cast<uintptr_t>(workspace) % 16) return FG_ERR_INVALID_ARG;
 
   p.enc = enc, p.acts = acts, p.g_pre = g_pre, p.g_heads = g_heads, p.ws = static_cast<float*>(workspace);
-  p.N = N, p.n_slabs = n_slabs, p.slab_rows = slab_rows;
-  p.in_ch = WG_XCH + d->aux_width, p.enc_w = FG_MLP_ENC_WIDTH(d->aux_width), p.rows_total = rows_total;
-  o.n_heads = d->n_heads, o.in_ch = p.in_ch;
-  hipStream_t s = fg_hip_stream(stream);
-  hipLaunchKernelGGL(mlp_wgrad_kernel, dim3((unsigned)((n_slabs * p.n_jobs + 7) / 8 * 8)), dim3(WG_BLOCK), 0, s, p);
-  FG_RETURN_IF_LAUNCH_FAILED();
-  hipLaunchKernelGGL(mlp_wgrad_reduce_kernel, dim3((unsigned)((WG_SLAB_FLOATS + WG_BLOCK - 1) / WG_BLOCK)), dim3(WG_BLOCK), 0, s,
-                     p.ws, n_slabs, o);
-  FG_RETURN_IF_LAUNCH_FAILED();
-  return FG_OK;
+  p.N = N, p.slab_rows = slab_rows, p.pre_rows = N, p.pre_row0 = 0;
+  if (int rc = wg_launch_slabs(p, 0, n_slabs, stream)) return rc;
+  return wg_launch_reduce(p.ws, n_slabs, o, stream);
+}
+
+// ---- fg_mlp_train_bwd: the chain (mlp.hip) and the slab jobs above, one chunk of slabs at a time, so that g_pre is a
+// chunk-sized array of the workspace.  Workspace: [the chain's packed weights, padded to 4 KB][g_pre chunk: 8 x chunk_rows x 256]
+// [one partial block per slab of the bound].
+namespace {
+
+inline int64_t tb_chunk_slabs(int64_t n_slabs, int32_t chunk_slabs) {
+  const int64_t want = chunk_slabs > 0 ? chunk_slabs : FG_MLP_TRAIN_BWD_CHUNK_SLABS;
+  return want < n_slabs ? want : n_slabs;
+}
+
+// the chain's packed weights, rounded up so that the chunk array behind them starts on a 4 KB boundary of the workspace: its
+// rows are read and written 128 bytes a wave at a time, and at the 64-byte offset the bare size leaves every such access
+// straddles two cache lines (measured: 3 % of the call, profiles/mlp_chunked_bwd.md)
+inline size_t tb_pack_bytes(int64_t N, bool inputs) {
+  const size_t b = inputs ? fg_mlp_bwd_inputs_workspace_bytes(N) : fg_mlp_train_workspace_bytes(N);
+  return (b + FG_MLP_TRAIN_BWD_ALIGN - 1) / FG_MLP_TRAIN_BWD_ALIGN * FG_MLP_TRAIN_BWD_ALIGN;
+}
+
+}  // namespace
+
+extern "C" int64_t fg_mlp_train_bwd_chunk_rows(int64_t N, int32_t chunk_slabs) {
+  if (N <= 0 || chunk_slabs < 0) return 0;
+  int rows;
+  int64_t slabs;
+  wg_cut(N, &rows, &slabs);
+  return tb_chunk_slabs(slabs, chunk_slabs) * rows;
+}
+
+extern "C" size_t fg_mlp_train_bwd_workspace_bytes(int64_t N, int32_t chunk_slabs, int32_t want_g_enc) {
+  if (N <= 0 || chunk_slabs < 0) return 0;
+  return tb_pack_bytes(N, want_g_enc != 0) + (size_t)WG_D * (size_t)fg_mlp_train_bwd_chunk_rows(N, chunk_slabs) * WG_W * sizeof(float) +
+         fg_mlp_param_grads_workspace_bytes(N);
+}
+
+extern "C" int fg_mlp_train_bwd(int64_t N, const fg_mlp_desc* d, const float* g_heads, const float* enc, const float* acts,
+                                float* g_enc, const fg_mlp_grads* out, int32_t chunk_slabs, void* workspace, size_t workspace_bytes,
+                                fg_stream_t stream) {
+  if (N < 0) return FG_ERR_INVALID_ARG;
+  if (N == 0) return FG_OK;
+  if (chunk_slabs < 0) return FG_ERR_INVALID_ARG;
+  if (int rc = fg_mlp_detail::bwd_check(N, d, nullptr, 0, 0)) return rc;
+  WgArgs p = {};
+  WgOut o = {};
+  bool need_enc, need_acts, need_pre, need_heads;
+  if (int rc = wg_plan(d, out, p, o, need_enc, need_acts, need_pre, need_heads)) return rc;
+  if (p.n_jobs == 0 && !g_enc) return FG_OK;
+  // (the chain reads g_heads and acts whatever is asked for; the operand tiles are fetched 16 bytes at a time)
+  if (!g_heads || !acts || (need_enc && !enc)) return FG_ERR_INVALID_ARG;
+  if (reinterpret_cast<uintptr_t>(enc) % 16 || reinterpret_cast<uintptr_t>(acts) % 16) return FG_ERR_INVALID_ARG;
+
+  int slab_rows;
+  int64_t n_slabs;
+  wg_cut(N, &slab_rows, &n_slabs);
+  if (n_slabs * (p.n_jobs > 0 ? p.n_jobs : 1) >= ((int64_t)1 << 31)) return FG_ERR_INVALID_ARG;
+  const bool inputs = g_enc != nullptr;
+  if (int rc = fg_mlp_detail::bwd_check(N, d, workspace, workspace_bytes, fg_mlp_train_bwd_workspace_bytes(N, chunk_slabs, inputs)))
+    return rc;
+
+  const int64_t per_chunk = tb_chunk_slabs(n_slabs, chunk_slabs), chunk_rows = per_chunk * slab_rows;
+  float* g_pre = reinterpret_cast<float*>(static_cast<char*>(workspace) + tb_pack_bytes(N, inputs));
+  p.enc = enc, p.acts = acts, p.g_pre = g_pre, p.g_heads = g_heads, p.ws = g_pre + (size_t)WG_D * chunk_rows * WG_W;
+  p.N = N, p.slab_rows = slab_rows, p.pre_rows = chunk_rows;
+  if (int rc = fg_mlp_detail::bwd_launch_pack(d, inputs, workspace, stream)) return rc;
+  for (int64_t s0 = 0; s0 < n_slabs; s0 += per_chunk) {
+    const int64_t s1 = s0 + per_chunk < n_slabs ? s0 + per_chunk : n_slabs;
+    const int64_t r0 = s0 * slab_rows, r1 = s1 * slab_rows < N ? s1 * slab_rows : N;
+    if (int rc = fg_mlp_detail::bwd_launch_rows(N, d, r0, r1, g_heads, acts, g_pre, chunk_rows, g_enc, workspace, stream)) return rc;
+    p.pre_row0 = r0;
+    if (p.n_jobs > 0)
+      if (int rc = wg_launch_slabs(p, s0, s1 - s0, stream)) return rc;
+  }
+  return p.n_jobs > 0 ? wg_launch_reduce(p.ws, n_slabs, o, stream) : FG_OK;
 }

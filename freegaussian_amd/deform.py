@@ -5,7 +5,9 @@ With ``FG_FUSED_MLP_TRAIN=1`` (opt-in; unset = off) a taped forward over as many
 forward with saved activations, the fused backward data chain, and the weight gradients as chunked library products
 (``mlp_param_grads``); ``FG_FUSED_MLP_TRAIN=2`` also takes the blender net and inputs that want a gradient
 (``ops.mlp_train(..., input_grads=True)``: the backward that forms the gradient of the input row); with
-``FG_FUSED_MLP_WGRAD=1`` (opt-in) on top of either, the weight gradients are one fused call too (``ops.mlp_param_grads``).  Behaviour and
+``FG_FUSED_MLP_WGRAD=1`` (opt-in) on top of either, the weight gradients are one fused call too (``ops.mlp_param_grads``); with
+``FG_FUSED_MLP_CHUNKED=1`` (opt-in) on top of both, the backward is one call that works through the rows in chunks and keeps no
+``[8,N,256]`` gradient array (``ops.mlp_train_backward``).  Behaviour and
 ``state_dict`` key names follow the reference's ``FreeGaussianDeformableModel`` / ``FreeGaussianControllableModel``
 (freegaussian/freegaussian_model.py:1054-1145) so stage-1 checkpoints load unchanged; outputs are
 checked against golden vectors produced by the reference classes (tests/golden/g_mlp.npz)."""
@@ -147,10 +149,15 @@ def _train_keywords(mode: str) -> dict:
     ``FG_FUSED_MLP_WGRAD=1`` (opt-in; read here and nowhere else, on the host, on every call; unset = off) = its parameter
     gradients come from the fused call ``ops.mlp_param_grads`` in place of ``mlp_param_grads`` below.  The knob has no
     lower row bound of its own: it wins at every size measured (profiles/mlp_wgrad.md: 0.49 against 1.42 ms at 33 000 rows,
-    the smallest, within 1 % of ``FUSED_MIN_ROWS``, the fewest rows a fused training call sees)."""
+    the smallest, within 1 % of ``FUSED_MIN_ROWS``, the fewest rows a fused training call sees).
+    ``FG_FUSED_MLP_CHUNKED=1`` (opt-in; read here and nowhere else, on the host, on every call; unset = off) on top of that
+    knob -- without it it does nothing -- = the backward is one ``fg_mlp_train_bwd`` call over row chunks: the same gradients
+    bit for bit, 8 KB per row less memory (profiles/mlp_chunked_bwd.md)."""
     kw = {"input_grads": True} if mode == "2" else {}
     if os.environ.get("FG_FUSED_MLP_WGRAD", "0") == "1":
         kw["fused_param_grads"] = True
+        if os.environ.get("FG_FUSED_MLP_CHUNKED", "0") == "1":
+            kw["chunked_backward"] = True
     return kw
 
 

@@ -1423,14 +1423,76 @@ def mlp_param_grads(enc: torch.Tensor, H: torch.Tensor, G: torch.Tensor, g_heads
     return tuple(outs[:8]), tuple(outs[8:16]), tuple(outs[16 : 16 + n]), tuple(outs[16 + n :])
 
 
+def mlp_train_chunk_rows(N: int, chunk_slabs: int = 0) -> int:
+    """Rows of the chunk array of ``fg_mlp_train_bwd`` over ``N`` rows: ``chunk_slabs`` slabs of ``mlp_wgrad_slab_rows(N)``
+    rows (0 = the library's constant), capped at all the slabs."""
+    return int(_lib.load().fg_mlp_train_bwd_chunk_rows(int(N), int(chunk_slabs)))
+
+
+def mlp_train_backward(enc: torch.Tensor, H: torch.Tensor, g_heads: torch.Tensor, trunk, heads, aux_width: int, head_rows,
+                       want=None, want_g_enc: bool = False, chunk_slabs: int = 0):
+    """The whole backward of the fused training path in one call that never holds ``G`` [8,N,256] (``fg_mlp_train_bwd``;
+    DESIGN.md §6 A): from ``enc`` [N, padded 63 + aux_width] and ``H`` [8,N,256] as ``fg_mlp_train_fwd`` stores them, the
+    head cotangents ``g_heads`` [N, sum(head_rows)] and the network's parameters (``trunk`` / ``heads`` as for
+    ``mlp_train``) ->  ``(gW x 8, gb x 8, gW_head per head, gb_head per head, g_enc or None)``.  The rows go through the
+    data chain and the slab products ``chunk_slabs`` slabs of ``mlp_wgrad_slab_rows(N)`` rows at a time (0 = the library's
+    constant; capped at all the slabs), the chain's gradients in a chunk-sized array of the workspace; the partial sums are
+    added once, in slab order.  Every result is bit for bit what ``fg_mlp_bwd`` / ``fg_mlp_bwd_inputs`` followed by
+    ``mlp_param_grads`` gives, for every ``chunk_slabs``.  ``want`` as for ``mlp_param_grads``; ``want_g_enc``: also the
+    gradient of the encoded input row [N, padded 63 + aux_width] (``mlp_input_grads`` takes it to ``x`` / ``aux``).  CUDA
+    float32 contiguous tensors; no host synchronisation: capturable."""
+    tensors = (enc, H, g_heads)
+    if any(not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() for t in tensors):
+        raise ValueError("mlp_train_backward wants contiguous CUDA float32 tensors")
+    rows = [int(r) for r in head_rows]
+    n = len(rows)
+    if not 1 <= aux_width <= 64 or not 1 <= n <= _lib.MLP_MAX_HEADS or min(rows) < 1 or sum(rows) > 16:
+        raise ValueError(f"mlp_train_backward: aux width {aux_width} / head rows {rows} outside what the kernels take")
+    if not isinstance(chunk_slabs, int) or isinstance(chunk_slabs, bool) or chunk_slabs < 0:
+        raise ValueError(f"mlp_train_backward: chunk_slabs wants an int >= 0, got {chunk_slabs!r}")
+    N, in_ch = enc.shape[0], 63 + aux_width
+    if enc.dim() != 2 or enc.shape[1] != _lib.mlp_enc_width(aux_width):
+        raise ValueError(f"mlp_train_backward wants enc [N, {_lib.mlp_enc_width(aux_width)}], got {tuple(enc.shape)}")
+    if tuple(H.shape) != (8, N, 256):
+        raise ValueError(f"mlp_train_backward wants H [8, {N}, 256], got {tuple(H.shape)}")
+    if tuple(g_heads.shape) != (N, sum(rows)):
+        raise ValueError(f"mlp_train_backward wants g_heads [{N}, {sum(rows)}], got {tuple(g_heads.shape)}")
+    want = [True] * (16 + 2 * n) if want is None else [bool(w) for w in want]
+    if len(want) != 16 + 2 * n:
+        raise ValueError(f"mlp_train_backward: want has {len(want)} entries for {16 + 2 * n} gradients")
+    d, _, desc_rows, keep = _mlp_desc("mlp_train_backward", None, aux_width, trunk, heads, _lib.MLP_PLAIN)
+    if desc_rows != rows:
+        raise ValueError(f"mlp_train_backward: head rows {rows} are not the heads' {desc_rows}")
+    shapes = [(256, in_ch if l == 0 else (in_ch + 256 if l == 5 else 256)) for l in range(8)] + [(256,)] * 8
+    shapes += [(r, 256) for r in rows] + [(r,) for r in rows]
+    dev = enc.device
+    # (N = 0: the sums over no rows)
+    outs = [(torch.zeros if N == 0 else torch.empty)(s, dtype=torch.float32, device=dev) if w else None for s, w in zip(shapes, want)]
+    g_enc = torch.empty_like(enc) if want_g_enc else None
+    if N > 0 and (any(want) or want_g_enc):
+        g = _lib.MlpGrads()
+        g.size = ctypes.sizeof(_lib.MlpGrads)
+        for i in range(8):
+            g.weight[i], g.bias[i] = _ptr(outs[i]), _ptr(outs[8 + i])
+        for i in range(n):
+            g.head_weight[i], g.head_bias[i] = _ptr(outs[16 + i]), _ptr(outs[16 + n + i])
+        with torch.cuda.device(dev):
+            need = int(_lib.load().fg_mlp_train_bwd_workspace_bytes(N, chunk_slabs, int(bool(want_g_enc))))
+            ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            _call("fg_mlp_train_bwd", N, ctypes.addressof(d), _ptr(g_heads), _ptr(enc), _ptr(H), _ptr(g_enc), ctypes.addressof(g),
+                  chunk_slabs, _ptr(ws), ws.numel(), _stream())  # fmt: skip
+    return tuple(outs[:8]), tuple(outs[8:16]), tuple(outs[16 : 16 + n]), tuple(outs[16 + n :]), g_enc
+
+
 class _MlpTrain(torch.autograd.Function):
     """``fg_mlp_train_fwd`` / ``fg_mlp_bwd`` around the saved ``enc`` [N, padded in_ch] and ``H`` [8,N,256]; the inputs are
     ``x``, ``aux``, the number of heads, whether ``x`` / ``aux`` may get a gradient (then ``fg_mlp_bwd_inputs`` where one
-    of them wants it), whether the parameter gradients come from ``fg_mlp_param_grads``, then the 8 trunk weights, the 8
-    trunk biases, the head weights, the head biases."""
+    of them wants it), whether the parameter gradients come from ``fg_mlp_param_grads``, the chunked backward (None = off;
+    an int = the whole backward is one ``fg_mlp_train_bwd`` call with that ``chunk_slabs``, 0 being the library's constant),
+    then the 8 trunk weights, the 8 trunk biases, the head weights, the head biases."""
 
     @staticmethod
-    def forward(ctx, x, aux, n_heads, input_grads, fused_param_grads, *params):
+    def forward(ctx, x, aux, n_heads, input_grads, fused_param_grads, chunk_slabs, *params):
         trunk, heads = list(zip(params[:8], params[8:16])), list(zip(params[16 : 16 + n_heads], params[16 + n_heads :]))
         d, N, rows, keep = _mlp_desc("mlp_train", x, aux, trunk, heads, _lib.MLP_PLAIN)
         dev = keep[0].device
@@ -1444,6 +1506,7 @@ class _MlpTrain(torch.autograd.Function):
         ctx.aux_width, ctx.head_rows = d.aux_width, rows
         ctx.input_grads, ctx.one_row_aux = bool(input_grads), d.aux_stride == 0
         ctx.fused_param_grads = bool(fused_param_grads)
+        ctx.chunk_slabs = chunk_slabs
         return out
 
     @staticmethod
@@ -1457,9 +1520,15 @@ class _MlpTrain(torch.autograd.Function):
         d, _, rows, keep = _mlp_desc("mlp_train", None, ctx.aux_width, trunk, heads, _lib.MLP_PLAIN)
         g_heads = _f32(g_heads, "g_heads")
         N = g_heads.shape[0]
-        G = torch.empty_like(H)
         want_x, want_aux = (ctx.input_grads and need for need in ctx.needs_input_grad[:2])
         g_x = g_aux = None
+        if ctx.chunk_slabs is not None:  # no G: the chain and the products chunk by chunk, in one call
+            gW, gb, gWh, gbh, g_enc = mlp_train_backward(enc, H, g_heads, trunk, heads, ctx.aux_width, rows, want=ctx.needs_input_grad[6:],
+                                                         want_g_enc=want_x or want_aux, chunk_slabs=ctx.chunk_slabs)  # fmt: skip
+            if g_enc is not None:
+                g_x, g_aux = mlp_input_grads(g_enc, enc, ctx.aux_width, want_x, want_aux, ctx.one_row_aux)
+            return (g_x, g_aux, None, None, None, None, *gW, *gb, *gWh, *gbh)
+        G = torch.empty_like(H)
         with torch.cuda.device(G.device):
             if want_x or want_aux:
                 g_enc = torch.empty_like(enc)
@@ -1471,15 +1540,15 @@ class _MlpTrain(torch.autograd.Function):
                 ws = torch.empty(int(_lib.load().fg_mlp_train_workspace_bytes(N)), dtype=torch.uint8, device=G.device)
                 _call("fg_mlp_bwd", N, ctypes.addressof(d), _ptr(g_heads), _ptr(H), _ptr(G), _ptr(ws), ws.numel(), _stream())
         if ctx.fused_param_grads:
-            gW, gb, gWh, gbh = mlp_param_grads(enc, H, G, g_heads, ctx.aux_width, rows, want=ctx.needs_input_grad[5:])
-            return (g_x, g_aux, None, None, None, *gW, *gb, *gWh, *gbh)
+            gW, gb, gWh, gbh = mlp_param_grads(enc, H, G, g_heads, ctx.aux_width, rows, want=ctx.needs_input_grad[6:])
+            return (g_x, g_aux, None, None, None, None, *gW, *gb, *gWh, *gbh)
         gW, gb, gWh, gbh = deform.mlp_param_grads(enc[:, : 63 + ctx.aux_width], H, G, g_heads, rows)
         grads = (*gW, *gb, *gWh, *gbh)
-        return (g_x, g_aux, None, None, None, *(g if need else None for g, need in zip(grads, ctx.needs_input_grad[5:])))
+        return (g_x, g_aux, None, None, None, None, *(g if need else None for g, need in zip(grads, ctx.needs_input_grad[6:])))
 
 
 def mlp_train(x: torch.Tensor, aux: torch.Tensor, trunk, heads, input_grads: bool = False,
-              fused_param_grads: bool = False) -> torch.Tensor:
+              fused_param_grads: bool = False, chunked_backward=False) -> torch.Tensor:
     """The network of ``mlp_forward`` for training (``fg_mlp_train_fwd`` / ``fg_mlp_bwd``): the raw head outputs
     ``[N, rows_total]`` (the heads side by side in the order given, bit for bit ``mlp_forward(mode="plain")``), recorded
     for autograd.  The forward keeps the encoded input row and the eight post-ReLU activations (``[8,N,256]``); the
@@ -1489,8 +1558,22 @@ def mlp_train(x: torch.Tensor, aux: torch.Tensor, trunk, heads, input_grads: boo
     chain and the gradient of the encoded input row -- and ``mlp_input_grads`` takes that to ``x`` (through the
     positional encoding, in closed form) and to ``aux`` (a one-row ``aux`` gets the sum over the rows).
     ``fused_param_grads``: the parameter gradients come from one ``fg_mlp_param_grads`` call (``mlp_param_grads`` above:
-    only those that want one are formed) in place of the library products; the rest of the backward is the same.  CUDA float32
+    only those that want one are formed) in place of the library products; the rest of the backward is the same.
+    ``chunked_backward``: ``True`` or a positive int -- the backward allocates no second ``[8,N,256]`` array: the chain and
+    the fused parameter gradients run chunk by chunk in one ``fg_mlp_train_bwd`` call (``mlp_train_backward`` above; the int
+    is its ``chunk_slabs``, ``True`` the library's constant), bit for bit the gradients of ``fused_param_grads=True``.  It
+    implies the fused parameter gradients: with ``fused_param_grads=False`` it is a ``ValueError``.  CUDA float32
     tensors, N >= 1; ``aux`` as for ``mlp_forward``.  No host synchronisation: capturable."""
+    chunk_slabs = None
+    if chunked_backward is not False and chunked_backward is not None:
+        if chunked_backward is True:
+            chunk_slabs = 0
+        elif isinstance(chunked_backward, int) and chunked_backward > 0:
+            chunk_slabs = int(chunked_backward)
+        else:
+            raise ValueError(f"mlp_train: chunked_backward wants True or a positive int, got {chunked_backward!r}")
+        if not fused_param_grads:
+            raise ValueError("mlp_train: chunked_backward forms the fused parameter gradients; pass fused_param_grads=True")
     trunk = [(m.weight, m.bias) if hasattr(m, "weight") else tuple(m) for m in trunk]
     heads = [(m.weight, m.bias) if hasattr(m, "weight") else tuple(m) for m in heads]
     if len(trunk) != 8 or not 1 <= len(heads) <= _lib.MLP_MAX_HEADS:
@@ -1503,7 +1586,7 @@ def mlp_train(x: torch.Tensor, aux: torch.Tensor, trunk, heads, input_grads: boo
     if input_grads and aux.requires_grad and aux.dim() == 2 and aux.shape[0] > 1 and aux.stride(0) == 0:
         aux = aux[:1]  # (one row for all: autograd's own expand carries the [1, A] sum back)
     params = [w for w, _ in trunk] + [b for _, b in trunk] + [w for w, _ in heads] + [b for _, b in heads]
-    return _MlpTrain.apply(x, aux, len(heads), bool(input_grads), bool(fused_param_grads), *params)
+    return _MlpTrain.apply(x, aux, len(heads), bool(input_grads), bool(fused_param_grads), chunk_slabs, *params)
 
 
 # --------------------------------------------------------------------------------------------

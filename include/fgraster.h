@@ -45,6 +45,7 @@ typedef void* fg_stream_t;
 #define FG_SPLAT_FLOATS 16   /* one 64-byte record per Gaussian, see fg_pack_splats */
 #define FG_SH_JAC_FLOATS 10  /* per-Gaussian note of the SH colour for the backward, see fg_preprocess_fwd */
 #define FG_ABI_VERSION 14
+#define FG_ABI_MINOR 1 /* symbols added since FG_ABI_VERSION was last raised: 1 = fg_abi_minor, fg_mlp_train_bwd* */
 #define FG_COUNT_OUT_WORDS 16 /* int64 words of a count_out block (fg_stbin_count, fg_step_io): ABI 9 */
 
 int fg_abi_version(void);
@@ -935,6 +936,50 @@ int fg_mlp_param_grads_slab_rows(int64_t N);
 int fg_mlp_param_grads(int64_t N, const fg_mlp_desc* desc, const float* enc, const float* acts, const float* g_pre,
                        const float* g_heads, const fg_mlp_grads* out, void* workspace, size_t workspace_bytes,
                        fg_stream_t stream);
+
+/* ---- K10 backward in row chunks (ABI 14, minor 1): fg_mlp_bwd / fg_mlp_bwd_inputs and fg_mlp_param_grads as ONE call that
+ * never holds g_pre [8, N, 256] whole.  The rows are cut into the slabs of fg_mlp_param_grads (fg_mlp_param_grads_slab_rows(N)
+ * rows, a function of N alone, a multiple of 64); a chunk is chunk_slabs consecutive slabs, the last chunk may be shorter.
+ * On the caller's stream, in row order:
+ *   once       the chain's weight re-ordering launches (Tp; Tin too where g_enc is wanted)
+ *   per chunk  the data-chain kernel of fg_mlp_bwd (of fg_mlp_bwd_inputs where g_enc is non-null) over the chunk's rows:
+ *              g_heads, acts (layer stride N * 256) and g_enc at the rows themselves, P_l into a workspace array
+ *              [8, chunk_rows, 256] at the row less the chunk's first; then the slab kernel of fg_mlp_param_grads over the
+ *              chunk's slabs, P_l from that array, each slab's partial block at the slab's own index
+ *   once       the reduction of fg_mlp_param_grads over all the slabs
+ * so 1 (2 with g_enc) + 2 ceil(slabs / chunk_slabs) + 1 launches: a function of N, chunk_slabs and what is asked for.  Same
+ * slabs, same chain inside a slab, same slab-order sum: every output of fg_mlp_grads, and g_enc, is bit for bit what
+ * fg_mlp_bwd[_inputs] followed by fg_mlp_param_grads writes from the same inputs, for every chunk_slabs.  No atomics, nothing kept
+ * between calls, no host synchronisation; asynchronous and capturable in a graph.
+ *   chunk_slabs  0 = FG_MLP_TRAIN_BWD_CHUNK_SLABS; a positive value is taken as given, capped at the number of slabs (all
+ *                the slabs = one chunk: what the two calls do); negative: FG_ERR_INVALID_ARG
+ *   g_enc        [N, FG_MLP_ENC_WIDTH(aux_width)] or null (not formed)
+ *   out          as for fg_mlp_param_grads: every entry nullable.  No trunk gradient asked for: the chunks still run where
+ *                g_enc is wanted; nothing asked for and g_enc null: FG_OK, nothing is launched
+ *   desc         as for fg_mlp_bwd: the chain reads its weight pointers; x / aux / out are not read
+ *   fg_mlp_train_bwd_chunk_rows(N, chunk_slabs) = min(chunk_slabs, slabs) * slab rows: the rows of the workspace array
+ * The workspace: 16-byte aligned, fg_mlp_train_bwd_workspace_bytes(N, chunk_slabs, want_g_enc) bytes =
+ *   fg_mlp_train_workspace_bytes(N) (want_g_enc: fg_mlp_bwd_inputs_workspace_bytes(N)) rounded up to a multiple of
+ *   FG_MLP_TRAIN_BWD_ALIGN = 4096 (the chunk array's rows then start on cache-line boundaries of an allocator's block: at
+ *   the 64-byte offset of the bare size the call was 3 % slower) + 8 * chunk_rows * 256 * 4
+ *   + fg_mlp_param_grads_workspace_bytes(N);  0 for N <= 0.  Next to acts (8 KB per row) the call needs nothing that grows
+ * with N but the partial blocks (0.5 KB per row): at 1M rows 1.07 GB for the default chunk, against the 8.2 GB of g_pre.  (The
+ * slab length is not monotone in N, so neither is this size in general: ask per call.)
+ * FG_MLP_TRAIN_BWD_CHUNK_SLABS = 16: chosen among 16 / 21 / 32 / 42 by the median backward at 240 000 rows (profiles/mlp_chunked_bwd.md,
+ * table (a), MI355X: 6.98 / 7.45 / 7.36 / 7.43 ms, p10 .. p90 of 16 apart from the others; the two calls 6.65 ms, one chunk 6.77 ms).
+ * 16 slabs are 1024 tiles of the chain, two full rounds of its 512 workgroup places.  The call is slower than the two calls it
+ * combines: 1.05 x at 33 000 and 240 000 rows, 1.03 x at 1 000 000; what it saves is the 8 KB per row of g_pre.
+ * Error codes as the two calls: N == 0 does nothing; FG_ERR_INVALID_ARG: negative N or chunk_slabs, a null desc or out, wrong
+ * size fields, a null weight pointer, aux_width / head rows out of range, a mode other than FG_MLP_PLAIN, null g_heads / acts
+ * (always read) or enc (where weight[0] / weight[5] is asked for), a null or misaligned workspace; FG_ERR_WORKSPACE: a
+ * workspace too small; FG_ERR_UNSUPPORTED: depth / width / multires other than 8 / 256 / 10. */
+#define FG_MLP_TRAIN_BWD_CHUNK_SLABS 16
+#define FG_MLP_TRAIN_BWD_ALIGN 4096 /* bytes: where the chunk array starts in the workspace */
+int fg_abi_minor(void);
+int64_t fg_mlp_train_bwd_chunk_rows(int64_t N, int32_t chunk_slabs);
+size_t fg_mlp_train_bwd_workspace_bytes(int64_t N, int32_t chunk_slabs, int32_t want_g_enc);
+int fg_mlp_train_bwd(int64_t N, const fg_mlp_desc* desc, const float* g_heads, const float* enc, const float* acts, float* g_enc,
+                     const fg_mlp_grads* out, int32_t chunk_slabs, void* workspace, size_t workspace_bytes, fg_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -42,6 +42,24 @@ build) and writes profiles/mlp_wgrad.md.  Its steps, each a child process as abo
     --step wmodel  the model training step of --step model, the knob set and unset (with --blender: the default model)
     --step wtrace  three calls of each side at N = 240 000, both aux widths, for ``rocprofv3 --kernel-trace --stats``
     --step wreport profiles/mlp_wgrad.md; --parity: a ``FG_PARITY_REPORT`` file of tests/test_mlp_wgrad_gpu.py
+
+``--chunked`` measures the backward in row chunks (``fg_mlp_train_bwd``; knob ``FG_FUSED_MLP_CHUNKED=1`` on top of the two
+above) against the two calls it combines, ``fg_mlp_bwd_inputs`` + ``fg_mlp_param_grads`` of the same build, and writes
+profiles/mlp_chunked_bwd.md.  Its steps, each a child process as above:
+
+    --step ccall   the backward alone on one real forward's activations at N = 33 000, 240 000, 1 000 000 for aux widths 21
+                   and 30: ``chunk_slabs`` 16, 21, 32, 42 and all the slabs (one chunk), each alternating call by call with
+                   the two calls; launches per call; the candidate the rule of the report picks
+    --step ctrain  the whole ``ops.mlp_train`` forward + backward through the module, the knob set and unset (with --blender:
+                   the blender net under ``FG_FUSED_MLP_TRAIN=2``)
+    --step cmodel  the model training step of --step model for the default (blender) model, the knob set and unset
+    --step cmem    peak allocated bytes per row of one forward + backward of the blender net above the level before it: the
+                   torch path, the fused path with a whole ``G`` and the chunked path, at 240 000 and 1 000 000 rows
+    --step ctrace  three calls of each side at N = 240 000, both aux widths, for ``rocprofv3 --kernel-trace --stats``
+    --step creport profiles/mlp_chunked_bwd.md; --parity: a ``FG_PARITY_REPORT`` file of tests/test_mlp_chunked_gpu.py
+With ``--parent-lib FILE`` (the library built from the parent commit) it also runs ``--step wcall`` and ``--step kernel
+--blender`` once on each build (``--lib``: the library a step loads), for the table that shows what the kernels' new
+arguments cost the existing entry points.
 """
 import argparse
 import copy
@@ -525,6 +543,306 @@ def wstep_report(out, md, parity):
     print("\n".join(L))
 
 
+# ---- --chunked: the backward in row chunks ----------------------------------------------------------------------------------
+CHUNK_KNOB = "FG_FUSED_MLP_CHUNKED"
+CHUNK_CANDIDATES = (16, 21, 32, 42)
+
+
+def _use_library(path):
+    """Load another build of the library (the parent commit's): the symbols it lacks are not bound."""
+    import ctypes
+
+    from freegaussian_amd import _lib
+
+    os.environ["FG_RASTER_LIB"] = path
+    lib = ctypes.CDLL(path)
+    for name in [n for n in _lib.SIGNATURES if not hasattr(lib, n)]:
+        del _lib.SIGNATURES[name]
+    if "fg_abi_minor" not in _lib.SIGNATURES:
+        _lib.ABI_MINOR = 0
+
+
+def _chunk_knob(on):
+    if on:
+        os.environ[CHUNK_KNOB] = "1"
+    else:
+        os.environ.pop(CHUNK_KNOB, None)
+
+
+def _count_chunked_calls():
+    from freegaussian_amd import ops
+
+    calls = []
+    real = ops.mlp_train_backward
+    ops.mlp_train_backward = lambda *a, **k: calls.append(1) or real(*a, **k)
+    return calls
+
+
+def _chunked_pair(n, A):
+    """(run_chunked(chunk_slabs), run_two_calls) on the activations of one training forward over n rows of the net with an
+    aux of width A (21: the deformation net, 30: the blender net)."""
+    import ctypes
+
+    from freegaussian_amd import _lib, ops
+    from freegaussian_amd.deform import FreeGaussianDeformableModel
+
+    torch.manual_seed(0)
+    m = FreeGaussianDeformableModel(is_blender=A == 30).cuda()
+    assert m.input_ch - 63 == A
+    g = torch.Generator().manual_seed(n)
+    x = (torch.rand(n, 3, generator=g) * 2 - 1).cuda()
+    aux = torch.randn(1, A, generator=g).cuda()
+    heads = (m.branch_w, m.branch_v, m.gaussian_rotation, m.gaussian_scaling)
+    d, _, rows, keep = ops._mlp_desc("bench", x, aux, m.linear, heads, _lib.MLP_PLAIN)
+    lib = _lib.load()
+    raw = torch.empty(n, sum(rows), device="cuda")
+    enc = torch.empty(n, _lib.mlp_enc_width(A), device="cuda")
+    H = torch.empty(8, n, 256, device="cuda")
+    g_heads = (torch.randn(n, sum(rows), generator=g) * 1e-3).cuda()
+    ws = torch.empty(int(lib.fg_mlp_bwd_inputs_workspace_bytes(n)), dtype=torch.uint8, device="cuda")
+    ptr, st = ctypes.addressof(d), ops._stream()
+    ops._call("fg_mlp_train_fwd", n, ptr, raw.data_ptr(), enc.data_ptr(), H.data_ptr(), ws.data_ptr(), int(lib.fg_mlp_train_workspace_bytes(n)), st)
+    torch.cuda.synchronize()
+    hold = (m, d, keep, raw, x, aux)
+
+    def run_two(hold=hold):  # what _MlpTrain.backward does with the knob unset: G and g_enc from the allocator, the two calls
+        G, g_enc = torch.empty_like(H), torch.empty_like(enc)
+        ops._call("fg_mlp_bwd_inputs", n, ptr, g_heads.data_ptr(), H.data_ptr(), G.data_ptr(), g_enc.data_ptr(), ws.data_ptr(), ws.numel(), st)
+        return ops.mlp_param_grads(enc, H, G, g_heads, A, rows), g_enc
+
+    def run_chunked(c, hold=hold):
+        return ops.mlp_train_backward(enc, H, g_heads, m.linear, heads, A, rows, want_g_enc=True, chunk_slabs=c)
+
+    return run_chunked, run_two
+
+
+def cstep_call(out):
+    from freegaussian_amd import _lib, ops
+
+    res = {}
+    for A in (21, 30):
+        for n in SIZES:
+            run_chunked, run_two = _chunked_pair(n, A)
+            slabs = -(-n // ops.mlp_wgrad_slab_rows(n))
+            a, b = run_chunked(3), run_two()  # the same bits, whatever the chunks
+            torch.cuda.synchronize()
+            same = all(torch.equal(p, q) for ga, gb in zip(a[:4], b[0]) for p, q in zip(ga, gb)) and torch.equal(a[4], b[1])
+            assert same
+            del a, b
+            for c in CHUNK_CANDIDATES + (slabs,):
+                f, p = _timed_pair(lambda: run_chunked(c), run_two)
+                qf, qp = _quantiles(f), _quantiles(p)
+                chunks = -(-slabs // min(c, slabs))
+                res[f"{A},{n},{c}"] = {"aux_width": A, "n": n, "chunk_slabs": c, "one_chunk": c >= slabs, "slabs": slabs, "chunks": chunks,
+                                       "launches": 2 + 2 * chunks + 1, "two_call_launches": 3 + 2, "chunked_ms": qf, "two_ms": qp,
+                                       "ratio": qf["median"] / qp["median"],
+                                       "workspace_mb": int(_lib.load().fg_mlp_train_bwd_workspace_bytes(n, c, 1)) / 1e6}  # fmt: skip
+                print(res[f"{A},{n},{c}"], flush=True)
+            del run_chunked, run_two
+            torch.cuda.empty_cache()
+    json.dump(res, open(os.path.join(out, "ccall.json"), "w"), indent=1)
+
+
+def _pick_chunk_slabs(call, A=30, n=240_000):
+    """The rule: the candidate with the lowest median at 240 000 rows (the default model's net); where its p10 .. p90 overlaps a
+    smaller candidate's, the smaller."""
+    rows = sorted((r for r in call.values() if r["aux_width"] == A and r["n"] == n and r["chunk_slabs"] in CHUNK_CANDIDATES),
+                  key=lambda r: r["chunk_slabs"])  # fmt: skip
+    best = min(rows, key=lambda r: r["chunked_ms"]["median"])
+    for r in rows:
+        if r["chunk_slabs"] < best["chunk_slabs"] and r["chunked_ms"]["p10"] <= best["chunked_ms"]["p90"] and best["chunked_ms"]["p10"] <= r["chunked_ms"]["p90"]:
+            return r["chunk_slabs"], best["chunk_slabs"]
+    return best["chunk_slabs"], best["chunk_slabs"]
+
+
+def cstep_train(out):
+    m = _module().cuda()
+    _knob(True)
+    _wgrad_knob(True)
+    calls, res = _count_chunked_calls(), {}
+    for n in SIZES:
+        g = torch.Generator().manual_seed(n)
+        x = (torch.rand(n, 3, generator=g) * 2 - 1).cuda()
+        t = torch.full((1, 1), 0.4, device="cuda").expand(n, -1)
+        cots = [torch.randn(n, *s, generator=g).cuda() for s in ((4, 4), (4,), (3,))]
+
+        def run(on):
+            def go():
+                _chunk_knob(on)
+                _train_call(m, x, t, cots)
+            return go
+
+        before = len(calls)
+        f, p = _timed_pair(run(True), run(False))
+        assert len(calls) - before == WARM + TIMED  # the knob's side made the chunked call, the other never
+        qf, qp = _quantiles(f), _quantiles(p)
+        res[str(n)] = {"on_ms": qf, "off_ms": qp, "ratio": qf["median"] / qp["median"]}
+        print(n, res[str(n)], flush=True)
+    json.dump(res, open(os.path.join(out, "ctrain_blender.json" if BLENDER else "ctrain.json"), "w"), indent=1)
+
+
+def cstep_model(out):
+    from freegaussian_amd.model import Camera, FreeGaussianModel, FreeGaussianModelConfig
+    from freegaussian_amd.scenes import look_at_viewmat
+
+    torch.manual_seed(0)
+    n, W, H = 240_000, 960, 540
+    cfg = FreeGaussianModelConfig(background_color="white", num_downscales=0, warm_up=3000)
+    model = FreeGaussianModel(cfg, seed_points=(torch.rand(n, 3) - 0.5) * 2.0, init_scales=-4.5, is_blender=True)
+    with torch.no_grad():
+        for q in model.deform.parameters():
+            q.mul_(0.3)
+    model.step = 4000
+    model = model.cuda().train()
+    c2w = torch.linalg.inv(look_at_viewmat(torch.tensor([0.3, -0.2, -3.0]), torch.zeros(3)))
+    c2w[:3, 1:3] *= -1
+    cam = Camera(c2w[None, :3], 750.0, 750.0, W / 2, H / 2, W, H, times=torch.tensor([[0.4]]))
+    gt = torch.rand(H, W, 3, device="cuda")
+    os.environ[KNOB] = "2"
+    _wgrad_knob(True)
+    calls = _count_chunked_calls()
+
+    def step(on):
+        def run():
+            _chunk_knob(on)
+            model.zero_grad(set_to_none=True)
+            model.get_loss_dict(model.get_outputs(cam), {"image": gt})["main_loss"].backward()
+        return run
+
+    warm, timed = 5, 30
+    f, p = _timed_pair(step(True), step(False), warm=warm, timed=timed)
+    assert len(calls) == warm + timed
+    res = {"n": n, "width": W, "height": H, "on_ms": _quantiles(f), "off_ms": _quantiles(p)}
+    print(res, flush=True)
+    json.dump(res, open(os.path.join(out, "cmodel.json"), "w"), indent=1)
+
+
+def cstep_mem(out):
+    from freegaussian_amd.deform import FreeGaussianDeformableModel
+
+    torch.manual_seed(0)
+    m = FreeGaussianDeformableModel(is_blender=True).cuda()
+    res = {}
+    paths = (("torch path (no knob)", {}), ("fused, whole G (`FG_FUSED_MLP_TRAIN=2`, `FG_FUSED_MLP_WGRAD=1`)", {KNOB: "2", WGRAD_KNOB: "1"}),
+             ("chunked (`FG_FUSED_MLP_CHUNKED=1` on top)", {KNOB: "2", WGRAD_KNOB: "1", CHUNK_KNOB: "1"}))  # fmt: skip
+    for n in (240_000, 1_000_000):
+        g = torch.Generator().manual_seed(n)
+        x = (torch.rand(n, 3, generator=g) * 2 - 1).cuda()
+        t = torch.full((1, 1), 0.4, device="cuda").expand(n, -1)
+        cots = [torch.randn(n, *s, generator=g).cuda() for s in ((4, 4), (4,), (3,))]
+        for name, env in paths:
+            for k in (KNOB, WGRAD_KNOB, CHUNK_KNOB):
+                os.environ.pop(k, None)
+            os.environ.update(env)
+            for _ in range(2):  # (the second call: the library loaded, nothing of the first alive)
+                m.zero_grad(set_to_none=True)
+                torch.cuda.synchronize()
+                torch.cuda.empty_cache()
+                torch.cuda.reset_peak_memory_stats()
+                before = torch.cuda.memory_allocated()
+                outs = m(x, t)
+                torch.cuda.synchronize()
+                after_fwd = torch.cuda.memory_allocated() - before
+                torch.autograd.backward(outs, cots)
+                torch.cuda.synchronize()
+                peak = torch.cuda.max_memory_allocated() - before
+                del outs
+            res[f"{name}|{n}"] = {"path": name, "n": n, "kept_after_forward_per_row": after_fwd / n, "peak_per_row": peak / n, "peak_gb": peak / 1e9}
+            print(res[f"{name}|{n}"], flush=True)
+    json.dump(res, open(os.path.join(out, "cmem.json"), "w"), indent=1)
+
+
+def cstep_trace(out):
+    for A in (21, 30):
+        run_chunked, run_two = _chunked_pair(240_000, A)
+        for _ in range(3):
+            run_chunked(0)
+            run_two()
+        torch.cuda.synchronize()
+
+
+def cstep_report(out, md, parity):
+    from freegaussian_amd import _lib
+    from freegaussian_amd.deform import FUSED_MIN_ROWS
+
+    call = json.load(open(os.path.join(out, "ccall.json")))
+    pick, fastest = _pick_chunk_slabs(call)
+    const = _lib.MLP_TRAIN_BWD_CHUNK_SLABS
+    L = ["# Fused MLP backward in row chunks (`fg_mlp_train_bwd`, `FG_FUSED_MLP_CHUNKED=1`) against the two calls it combines", "",
+         "Written by `scripts/mlp_train_bench.py --chunked` on an MI355X.  The baseline of every table is the knob-unset path of the same",
+         "build (`fg_mlp_bwd_inputs` into a whole `G` [8, N, 256], then `fg_mlp_param_grads`), never an earlier figure.  One process per",
+         f"table, {WARM} warm-up and {TIMED} timed calls each between device events, the two sides alternating call by call.  The results of",
+         "the two sides are the same bits (checked at the start of every case of table (a), and by tests/test_mlp_chunked_gpu.py).", "",
+         "## (a) The backward alone, on one real forward's activations (head rows (3, 3, 4, 3), `g_enc` wanted)", "",
+         "Launches per call: the weight re-ordering (2), the chain and the slab kernel per chunk, the reduction; the two calls make 5.", "",
+         "| aux width | N | slabs | chunk_slabs | chunks | launches | workspace MB | chunked ms median (p10 .. p90) | two calls ms median (p10 .. p90) | "
+         "chunked / two calls |", "|---|---|---|---|---|---|---|---|---|---|"]  # fmt: skip
+    for r in call.values():
+        c = f"{r['chunk_slabs']} (all: one chunk)" if r["chunk_slabs"] == r["slabs"] else (f"{r['chunk_slabs']} (capped: one chunk)" if r["one_chunk"] else str(r["chunk_slabs"]))
+        L.append(f"| {r['aux_width']} | {r['n']:,} | {r['slabs']} | {c} | {r['chunks']} | {r['launches']} | {r['workspace_mb']:.0f} | "
+                 f"{_ms(r['chunked_ms'])} | {_ms(r['two_ms'])} | {r['ratio']:.3f} |")  # fmt: skip
+    L += ["", f"**The library's constant.**  Rule: the candidate of {CHUNK_CANDIDATES} with the lowest median at 240 000 rows (aux width 30, the default "
+          f"model's net); where its p10 .. p90 overlaps a smaller candidate's, the smaller.  Lowest median: {fastest}; by the rule: **{pick}**.  "
+          f"`FG_MLP_TRAIN_BWD_CHUNK_SLABS` of the build that ran tables (b) to (e): {const}" + ("." if const == pick else " -- NOT the rule's pick.")]  # fmt: skip
+    L += ["", "Chunked / two calls with the library's constant, as measured (above 1: the chunked call is slower by that factor):", ""]
+    for r in call.values():
+        if r["chunk_slabs"] == const:
+            L.append(f"- aux width {r['aux_width']}, N = {r['n']:,}: {r['ratio']:.3f}")
+    for name, title in (("ctrain.json", "deformation net, `FG_FUSED_MLP_TRAIN=1`"), ("ctrain_blender.json", "blender net, `FG_FUSED_MLP_TRAIN=2`")):
+        if os.path.exists(os.path.join(out, name)):
+            tr = json.load(open(os.path.join(out, name)))
+            L += ["", f"## (b) The whole `ops.mlp_train` forward + backward through the module ({title}, `{WGRAD_KNOB}=1`)", "",
+                  f"| N | `{CHUNK_KNOB}=1` ms median (p10 .. p90) | unset ms median (p10 .. p90) | set / unset |", "|---|---|---|---|"]
+            L += [f"| {int(n):,} | {_ms(r['on_ms'])} | {_ms(r['off_ms'])} | {r['ratio']:.3f} |" for n, r in tr.items()]
+    if os.path.exists(os.path.join(out, "cmodel.json")):
+        fr = json.load(open(os.path.join(out, "cmodel.json")))
+        L += ["", f"## (c) Model training step (`get_outputs` + `get_loss_dict` + backward; the default model -- the blender net -- {fr['n']:,} random "
+              f"Gaussians behind `warm_up`, {fr['width']} x {fr['height']}; `FG_FUSED_MLP_TRAIN=2`, `{WGRAD_KNOB}=1`)", "",
+              "| knob | ms per step median (p10 .. p90) |", "|---|---|",
+              f"| `{CHUNK_KNOB}` unset | {_ms(fr['off_ms'])} |", f"| `{CHUNK_KNOB}=1` | {_ms(fr['on_ms'])} |"]  # fmt: skip
+    if os.path.exists(os.path.join(out, "cmem.json")):
+        mem = json.load(open(os.path.join(out, "cmem.json")))
+        L += ["", "## (d) Peak allocated bytes per row (`torch.cuda.max_memory_allocated` over one forward + backward of the blender net through the "
+              "module, above the level before the call: inputs, cotangents and parameters are not counted)", "",
+              "| path | N | kept after the forward, bytes per row | peak, bytes per row | peak GB |", "|---|---|---|---|---|"]  # fmt: skip
+        L += [f"| {r['path']} | {r['n']:,} | {r['kept_after_forward_per_row']:,.0f} | {r['peak_per_row']:,.0f} | {r['peak_gb']:.2f} |" for r in mem.values()]
+    stats = sorted(glob.glob(os.path.join(out, "ctrace", "**", "*kernel_stats.csv"), recursive=True))
+    if stats:
+        L += ["", "## (e) Kernels of three calls of each side at N = 240 000, aux widths 21 and 30 (`rocprofv3 --kernel-trace --stats`, a run "
+              "of its own; no counters)", "", "| kernel | calls | average us | share % |", "|---|---|---|---|"]  # fmt: skip
+        for r in list(csv.DictReader(open(stats[0])))[:12]:
+            L.append(f"| `{r['Name'][:80]}` | {r['Calls']} | {float(r['AverageNs']) / 1e3:.1f} | {float(r['Percentage']):.1f} |")
+    base = {tag: os.path.join(out, f"base_{tag}") for tag in ("this", "parent")}
+    if all(os.path.exists(os.path.join(d, "wcall.json")) and os.path.exists(os.path.join(d, "kernel.json")) for d in base.values()):
+        w = {tag: json.load(open(os.path.join(d, "wcall.json"))) for tag, d in base.items()}
+        k = {tag: json.load(open(os.path.join(d, "kernel.json"))) for tag, d in base.items()}
+        L += ["", "## (f) The existing entry points on this build and on the parent commit's (the same GPU visit, a process each): what the "
+              "kernels' new arguments cost them", "", "| call | N | aux width | this build ms median (p10 .. p90) | parent build ms median (p10 .. p90) | "
+              "this / parent |", "|---|---|---|---|---|---|"]  # fmt: skip
+        for key, r in w["this"].items():
+            q = w["parent"][key]
+            L.append(f"| `fg_mlp_param_grads` | {r['n']:,} | {r['aux_width']} | {_ms(r['fused_ms'])} | {_ms(q['fused_ms'])} | "
+                     f"{r['fused_ms']['median'] / q['fused_ms']['median']:.3f} |")  # fmt: skip
+        for name, field in (("fg_mlp_bwd_inputs", "inputs_ms"), ("fg_mlp_bwd", "plain_ms")):
+            r, q = k["this"], k["parent"]
+            L.append(f"| `{name}` | {r['n']:,} | {r['aux_width']} | {_ms(r[field])} | {_ms(q[field])} | {r[field]['median'] / q[field]['median']:.3f} |")
+    if parity and os.path.exists(parity):
+        worst = {}
+        for line in open(parity):
+            r = json.loads(line)
+            if "test_mlp_chunked_gpu.py" in r["test"] and r["kind"] == "rel_err":
+                name = r["test"].split("::")[1].split("[")[0]
+                worst[name] = max(worst.get(name, 0.0), r["value"])
+        L += ["", "## Margins of tests/test_mlp_chunked_gpu.py (`FG_PARITY_REPORT`: the largest `rel_err` each test saw; the bar is 1e-4; every other "
+              "comparison of that file is bit for bit)", "", "| test | largest rel_err |", "|---|---|"]  # fmt: skip
+        L += [f"| `{k_}` | {v:.2e} |" for k_, v in sorted(worst.items())]
+    L += ["", f"The knob is off unless set; a fused training call sees at least `deform.FUSED_MIN_ROWS` = {FUSED_MIN_ROWS:,} rows."]
+    if os.path.exists(md) and "\n## Notes" in open(md).read():
+        L += ["", "## Notes" + open(md).read().split("\n## Notes", 1)[1].rstrip()]
+    open(md, "w").write("\n".join(L) + "\n")
+    print("\n".join(L))
+
+
 def step_report_inputs(out, md, parity):
     """profiles/mlp_train_inputs.md (--blender)."""
     from freegaussian_amd.deform import FUSED_MIN_ROWS
@@ -651,7 +969,11 @@ def step_report(out, md, parity):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--step", choices=["time", "error", "model", "trace", "kernel", "report", "wcall", "werror", "wtrain", "wmodel",
-                                       "wtrace", "wreport"])  # fmt: skip
+                                       "wtrace", "wreport", "ccall", "ctrain", "cmodel", "cmem", "ctrace", "creport"])  # fmt: skip
+    ap.add_argument("--chunked", action="store_true", help="the backward in row chunks, FG_FUSED_MLP_CHUNKED (profiles/mlp_chunked_bwd.md)")
+    ap.add_argument("--only", default=None, help="with --chunked: a comma-separated subset of its steps (ccall,base,ctrain,cmodel,cmem,ctrace,creport)")
+    ap.add_argument("--parent-lib", default=None, help="with --chunked: the parent commit's build of the library, for the side-by-side table")
+    ap.add_argument("--lib", default=None, help="with --step: load this build of the library in place of the package's")
     ap.add_argument("--wgrad", action="store_true", help="the fused parameter-gradient call, FG_FUSED_MLP_WGRAD (profiles/mlp_wgrad.md)")
     ap.add_argument("--blender", action="store_true", help="the blender net under FG_FUSED_MLP_TRAIN=2 (profiles/mlp_train_inputs.md)")
     ap.add_argument("--trace", action="store_true", help="also one rocprofv3 --kernel-trace --stats run of the fused calls")
@@ -664,6 +986,10 @@ def main():
     name = "mlp_train_inputs" if BLENDER else "mlp_train"
     if a.wgrad or (a.step or "").startswith("w"):
         name = "mlp_wgrad"
+    if a.chunked or (a.step or "").startswith("c"):
+        name = "mlp_chunked_bwd"
+    if a.lib:
+        _use_library(a.lib)
     a.out = a.out or os.path.join(ROOT, "results", name)
     a.md = a.md or os.path.join(ROOT, "profiles", name + ".md")
     os.makedirs(a.out, exist_ok=True)
@@ -672,6 +998,10 @@ def main():
             return step_report(a.out, a.md, a.parity)
         if a.step == "wreport":
             return wstep_report(a.out, a.md, a.parity)
+        if a.step == "creport":
+            return cstep_report(a.out, a.md, a.parity)
+        if a.step.startswith("c"):
+            return {"ccall": cstep_call, "ctrain": cstep_train, "cmodel": cstep_model, "cmem": cstep_mem, "ctrace": cstep_trace}[a.step](a.out)
         if a.step.startswith("w"):
             return {"wcall": wstep_call, "werror": wstep_error, "wtrain": wstep_train, "wmodel": wstep_model, "wtrace": wstep_trace}[a.step](a.out)
         return {"time": step_time, "error": step_error, "model": step_model, "trace": step_trace, "kernel": step_kernel}[a.step](a.out)
@@ -690,7 +1020,25 @@ def main():
     elif a.trace:
         steps.append((180, ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", os.path.join(a.out, "trace"),
                             "-o", "mlp", "--"] + me + ["trace"]))  # fmt: skip
-    if not a.wgrad:
+    if a.chunked:
+        me = [sys.executable, os.path.abspath(__file__), "--md", a.md]
+        here = me + ["--out", a.out, "--step"]
+        groups = {"ccall": [(300, here + ["ccall"])], "ctrain": [(180, here + ["ctrain"]), (180, here + ["ctrain", "--blender"])],
+                  "cmodel": [(240, here + ["cmodel"])], "cmem": [(180, here + ["cmem"])], "base": [], "ctrace": [],
+                  "creport": [(60, here + ["creport"] + (["--parity", a.parity] if a.parity else []))]}  # fmt: skip
+        if a.parent_lib:
+            from freegaussian_amd import _lib
+
+            for tag, lib in (("this", _lib.LIB_PATH), ("parent", os.path.abspath(a.parent_lib))):
+                base = me + ["--out", os.path.join(a.out, f"base_{tag}"), "--lib", lib, "--step"]
+                os.makedirs(os.path.join(a.out, f"base_{tag}"), exist_ok=True)
+                groups["base"] += [(300, base + ["wcall"]), (120, base + ["kernel", "--blender"])]
+        if a.trace:
+            groups["ctrace"] = [(180, ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", os.path.join(a.out, "ctrace"),
+                                       "-o", "mlp", "--"] + here + ["ctrace"])]  # fmt: skip
+        order = ("ccall", "base", "ctrain", "cmodel", "cmem", "ctrace", "creport")
+        steps = [s for name in order if not a.only or name in a.only.split(",") for s in groups[name]]
+    elif not a.wgrad:
         steps.append((60, me + ["report"] + (["--parity", a.parity] if a.parity else [])))
     for limit, cmd in steps:  # chained like &&: the first failure ends the job
         rc = subprocess.call(["timeout", "-k", "10", str(limit)] + cmd)
