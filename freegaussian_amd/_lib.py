@@ -103,6 +103,7 @@ SIGNATURES = {
     "fg_flow_bwd": (c_int, [c_int, P, P, P, P, P, P, P, P, P, P, P, P, P]),
     "fg_knn_workspace_bytes": (c_size_t, [c_int64]),
     "fg_knn": (c_int, [c_int64, P, c_int, P, P, P, c_size_t, P]),
+    "fg_mlp_precision_supported": (c_int, [c_int32]),  # (FG_MLP_FP32 / FG_MLP_BF16X3 / ...) -> 1 or 0
     "fg_mlp_workspace_bytes": (c_size_t, [c_int64]),
     "fg_mlp_fwd": (c_int, [c_int64, P, P, c_size_t, P]),  # (N, const fg_mlp_desc*, workspace, bytes, stream)
     "fg_mlp_train_workspace_bytes": (c_size_t, [c_int64]),
@@ -130,6 +131,7 @@ KNN_MAX_K = 8  # FG_KNN_MAX_K
 MLP_ROW_TILE = 64  # FG_MLP_ROW_TILE
 MLP_MAX_HEADS = 4  # FG_MLP_MAX_HEADS
 MLP_SE3, MLP_PLAIN = 0, 1  # FG_MLP_SE3, FG_MLP_PLAIN
+MLP_FP32, MLP_BF16X3 = 0, 1  # FG_MLP_FP32, FG_MLP_BF16X3: fg_mlp_desc::precision
 MLP_WGRAD_MAX_SLAB, MLP_WGRAD_MIN_SPLIT = 4096, 512  # FG_MLP_WGRAD_MAX_SLAB, FG_MLP_WGRAD_MIN_SPLIT
 MLP_TRAIN_BWD_CHUNK_SLABS = 16  # FG_MLP_TRAIN_BWD_CHUNK_SLABS
 
@@ -210,7 +212,7 @@ class MlpDesc(ctypes.Structure):
     """``fg_mlp_desc``: field order = the header's; device pointers as integers."""
 
     _fields_ = [(n, ctypes.c_int32) for n in ("size", "mode", "depth", "width", "multires", "aux_width", "n_heads")] + [
-        ("head_rows", ctypes.c_int32 * MLP_MAX_HEADS), ("reserved", ctypes.c_int32), ("aux_stride", ctypes.c_int64),
+        ("head_rows", ctypes.c_int32 * MLP_MAX_HEADS), ("precision", ctypes.c_int32), ("aux_stride", ctypes.c_int64),
         ("x", ctypes.c_void_p), ("aux", ctypes.c_void_p), ("weight", ctypes.c_void_p * 8), ("bias", ctypes.c_void_p * 8),
         ("head_weight", ctypes.c_void_p * MLP_MAX_HEADS), ("head_bias", ctypes.c_void_p * MLP_MAX_HEADS),
         ("out", ctypes.c_void_p * MLP_MAX_HEADS)]  # fmt: skip

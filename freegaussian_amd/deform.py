@@ -7,7 +7,8 @@ forward with saved activations, the fused backward data chain, and the weight gr
 (``ops.mlp_train(..., input_grads=True)``: the backward that forms the gradient of the input row); with
 ``FG_FUSED_MLP_WGRAD=1`` (opt-in) on top of either, the weight gradients are one fused call too (``ops.mlp_param_grads``); with
 ``FG_FUSED_MLP_CHUNKED=1`` (opt-in) on top of both, the backward is one call that works through the rows in chunks and keeps no
-``[8,N,256]`` gradient array (``ops.mlp_train_backward``).  Behaviour and
+``[8,N,256]`` gradient array (``ops.mlp_train_backward``); with ``FG_FUSED_MLP_PRECISION=bf16x3`` (opt-in) whichever of these
+fused calls takes a call forms its trunk and data-chain products as split-bf16 products (``fused_precision``).  Behaviour and
 ``state_dict`` key names follow the reference's ``FreeGaussianDeformableModel`` / ``FreeGaussianControllableModel``
 (freegaussian/freegaussian_model.py:1054-1145) so stage-1 checkpoints load unchanged; outputs are
 checked against golden vectors produced by the reference classes (tests/golden/g_mlp.npz)."""
@@ -139,6 +140,24 @@ def fused_train_mode(module: nn.Module, x: torch.Tensor, other: torch.Tensor) ->
     return knob if ok else ""
 
 
+def fused_precision() -> str:
+    """The ``precision`` of the fused calls: ``FG_FUSED_MLP_PRECISION`` (opt-in; read here and nowhere else, on the host, on
+    every call) -- unset or "fp32": the exact-fp32 kernels; "bf16x3": the split-bf16 product of include/fgraster.h in the
+    forward's trunk and the backward's data chain (the weight gradients stay fp32; profiles/mlp_split_bf16.md).  Anything
+    else is a ``ValueError``: a typo must not train silently in fp32.  It has effect only where a fused path already takes
+    the call (``fused_applies``, ``fused_train_mode``): no dispatch of its own."""
+    knob = os.environ.get("FG_FUSED_MLP_PRECISION", "fp32")
+    if knob not in ("fp32", "bf16x3"):
+        raise ValueError(f"FG_FUSED_MLP_PRECISION wants fp32 or bf16x3, got {knob!r}")
+    return knob
+
+
+def _precision_keywords() -> dict:
+    """``precision=`` for a fused call, only where the knob asks for something other than the default."""
+    knob = fused_precision()
+    return {} if knob == "fp32" else {"precision": knob}
+
+
 def fused_train_applies(module: nn.Module, x: torch.Tensor, other: torch.Tensor) -> bool:
     """Whether a taped ``module(x, other)`` runs as one ``ops.mlp_train`` call (``fused_train_mode``)."""
     return fused_train_mode(module, x, other) != ""
@@ -154,6 +173,7 @@ def _train_keywords(mode: str) -> dict:
     knob -- without it it does nothing -- = the backward is one ``fg_mlp_train_bwd`` call over row chunks: the same gradients
     bit for bit, 8 KB per row less memory (profiles/mlp_chunked_bwd.md)."""
     kw = {"input_grads": True} if mode == "2" else {}
+    kw.update(_precision_keywords())  # (FG_FUSED_MLP_PRECISION: fused_precision above)
     if os.environ.get("FG_FUSED_MLP_WGRAD", "0") == "1":
         kw["fused_param_grads"] = True
         if os.environ.get("FG_FUSED_MLP_CHUNKED", "0") == "1":
@@ -217,7 +237,7 @@ class FreeGaussianDeformableModel(nn.Module):
             if self.is_blender:
                 aux = self.timenet(aux)
             heads = (self.branch_w, self.branch_v, self.gaussian_rotation, self.gaussian_scaling)
-            return ops.mlp_forward(x, aux, self.linear, heads, mode="se3", outs=outs)
+            return ops.mlp_forward(x, aux, self.linear, heads, mode="se3", outs=outs, **_precision_keywords())
 
     def deformed_points(self, x: torch.Tensor, t: torch.Tensor):
         """(transform_points(d_xyz, x) [N,3], d_rotation, d_scaling) without the [N,4,4] transforms: what a render that
@@ -274,7 +294,8 @@ class FreeGaussianControllableModel(nn.Module):
 
             with torch.no_grad():
                 aux = positional_encoding(_one_row_if_broadcast(value), self.multires)
-                return tuple(ops.mlp_forward(x, aux, self.linear, (self.d_xyz, self.d_rot, self.d_scale), mode="plain"))
+                heads = (self.d_xyz, self.d_rot, self.d_scale)
+                return tuple(ops.mlp_forward(x, aux, self.linear, heads, mode="plain", **_precision_keywords()))
         mode = fused_train_mode(self, x, value)
         if mode:
             from . import ops

@@ -1261,6 +1261,15 @@ def knn(x: torch.Tensor, k: int = 3, squared: bool = False) -> Tuple[torch.Tenso
 
 MLP_ROW_TILE = _lib.MLP_ROW_TILE  # rows of one workgroup of fg_mlp_fwd (tests place their sizes around it)
 _MLP_OUT_COLS = {"se3": ((4, 4), (4,), (3,), (3,)), "plain": None}
+_MLP_PRECISIONS = {"fp32": _lib.MLP_FP32, "bf16x3": _lib.MLP_BF16X3}
+
+
+def _mlp_precision(who: str, precision) -> int:
+    """``fg_mlp_desc::precision`` of a ``precision=`` argument ("fp32": the exact-fp32 matrix instructions; "bf16x3": the
+    split-bf16 product of include/fgraster.h, three bf16 products for one fp32 one)."""
+    if not isinstance(precision, str) or precision not in _MLP_PRECISIONS:
+        raise ValueError(f"{who}: precision wants one of {sorted(_MLP_PRECISIONS)}, got {precision!r}")
+    return _MLP_PRECISIONS[precision]
 
 
 def _mlp_desc(who: str, x, aux, trunk, heads, mode: int):
@@ -1310,7 +1319,7 @@ def _mlp_desc(who: str, x, aux, trunk, heads, mode: int):
 
 
 @torch.no_grad()
-def mlp_forward(x: torch.Tensor, aux: torch.Tensor, trunk, heads, mode: str = "se3", outs=None):
+def mlp_forward(x: torch.Tensor, aux: torch.Tensor, trunk, heads, mode: str = "se3", outs=None, precision: str = "fp32"):
     """Fused fp32 forward of the deformation / control MLP (``fg_mlp_fwd``): per row
     ``[posenc(x, 10), aux]`` -> 8 linears of 256 with ReLU and the skip after layer 4 -> the head linears in one call of two launches (the weights
     re-ordered into scratch, then the whole network), no activation in global memory.  Inference only: nothing here is recorded for autograd.
@@ -1320,10 +1329,14 @@ def mlp_forward(x: torch.Tensor, aux: torch.Tensor, trunk, heads, mode: str = "s
     ``mode="se3"``: heads (w, v, rotation, scaling) -> ``[d_xyz [N,4,4], d_rot [N,4], d_scale [N,3], pts [N,3]]``
     (``pts`` = the transform applied to ``x``); ``mode="plain"``: one ``[N, rows]`` array per head.
     ``outs``: one entry per output -- ``None`` allocates it, a tensor is written in place, ``False`` leaves it out (the
-    returned list holds ``None`` there)."""
+    returned list holds ``None`` there).  ``precision``: "fp32" (the default: exact-fp32 products) or "bf16x3" (opt-in: the
+    trunk's products as three bf16 products of split operands, within 1e-4 of float64 -- the contract is in
+    include/fgraster.h); anything else is a ``ValueError``."""
     if mode not in _MLP_OUT_COLS:
         raise ValueError(f"mlp_forward: unknown mode {mode!r}")
+    prec = _mlp_precision("mlp_forward", precision)
     d, N, rows, keep = _mlp_desc("mlp_forward", x, aux, trunk, heads, _lib.MLP_SE3 if mode == "se3" else _lib.MLP_PLAIN)
+    d.precision = prec
     dev = keep[0].device
     shapes = _MLP_OUT_COLS[mode] or tuple((r,) for r in rows)
     outs = [None] * len(shapes) if outs is None else list(outs)
@@ -1430,7 +1443,7 @@ def mlp_train_chunk_rows(N: int, chunk_slabs: int = 0) -> int:
 
 
 def mlp_train_backward(enc: torch.Tensor, H: torch.Tensor, g_heads: torch.Tensor, trunk, heads, aux_width: int, head_rows,
-                       want=None, want_g_enc: bool = False, chunk_slabs: int = 0):
+                       want=None, want_g_enc: bool = False, chunk_slabs: int = 0, precision: str = "fp32"):
     """The whole backward of the fused training path in one call that never holds ``G`` [8,N,256] (``fg_mlp_train_bwd``;
     DESIGN.md §6 A): from ``enc`` [N, padded 63 + aux_width] and ``H`` [8,N,256] as ``fg_mlp_train_fwd`` stores them, the
     head cotangents ``g_heads`` [N, sum(head_rows)] and the network's parameters (``trunk`` / ``heads`` as for
@@ -1439,8 +1452,11 @@ def mlp_train_backward(enc: torch.Tensor, H: torch.Tensor, g_heads: torch.Tensor
     constant; capped at all the slabs), the chain's gradients in a chunk-sized array of the workspace; the partial sums are
     added once, in slab order.  Every result is bit for bit what ``fg_mlp_bwd`` / ``fg_mlp_bwd_inputs`` followed by
     ``mlp_param_grads`` gives, for every ``chunk_slabs``.  ``want`` as for ``mlp_param_grads``; ``want_g_enc``: also the
-    gradient of the encoded input row [N, padded 63 + aux_width] (``mlp_input_grads`` takes it to ``x`` / ``aux``).  CUDA
+    gradient of the encoded input row [N, padded 63 + aux_width] (``mlp_input_grads`` takes it to ``x`` / ``aux``).
+    ``precision``: as for ``mlp_forward`` -- "bf16x3" splits the data chain's products (and ``g_enc``'s); the parameter
+    gradients stay exact-fp32 products of the arrays the chain leaves.  CUDA
     float32 contiguous tensors; no host synchronisation: capturable."""
+    prec = _mlp_precision("mlp_train_backward", precision)
     tensors = (enc, H, g_heads)
     if any(not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() for t in tensors):
         raise ValueError("mlp_train_backward wants contiguous CUDA float32 tensors")
@@ -1461,6 +1477,7 @@ def mlp_train_backward(enc: torch.Tensor, H: torch.Tensor, g_heads: torch.Tensor
     if len(want) != 16 + 2 * n:
         raise ValueError(f"mlp_train_backward: want has {len(want)} entries for {16 + 2 * n} gradients")
     d, _, desc_rows, keep = _mlp_desc("mlp_train_backward", None, aux_width, trunk, heads, _lib.MLP_PLAIN)
+    d.precision = prec
     if desc_rows != rows:
         raise ValueError(f"mlp_train_backward: head rows {rows} are not the heads' {desc_rows}")
     shapes = [(256, in_ch if l == 0 else (in_ch + 256 if l == 5 else 256)) for l in range(8)] + [(256,)] * 8
@@ -1489,12 +1506,14 @@ class _MlpTrain(torch.autograd.Function):
     ``x``, ``aux``, the number of heads, whether ``x`` / ``aux`` may get a gradient (then ``fg_mlp_bwd_inputs`` where one
     of them wants it), whether the parameter gradients come from ``fg_mlp_param_grads``, the chunked backward (None = off;
     an int = the whole backward is one ``fg_mlp_train_bwd`` call with that ``chunk_slabs``, 0 being the library's constant),
+    the precision ("fp32" / "bf16x3": kept in the context, so every form of the backward runs in the forward's),
     then the 8 trunk weights, the 8 trunk biases, the head weights, the head biases."""
 
     @staticmethod
-    def forward(ctx, x, aux, n_heads, input_grads, fused_param_grads, chunk_slabs, *params):
+    def forward(ctx, x, aux, n_heads, input_grads, fused_param_grads, chunk_slabs, precision, *params):
         trunk, heads = list(zip(params[:8], params[8:16])), list(zip(params[16 : 16 + n_heads], params[16 + n_heads :]))
         d, N, rows, keep = _mlp_desc("mlp_train", x, aux, trunk, heads, _lib.MLP_PLAIN)
+        d.precision = _mlp_precision("mlp_train", precision)
         dev = keep[0].device
         out = torch.empty(N, sum(rows), dtype=torch.float32, device=dev)
         enc = torch.empty(N, _lib.mlp_enc_width(d.aux_width), dtype=torch.float32, device=dev)
@@ -1506,7 +1525,7 @@ class _MlpTrain(torch.autograd.Function):
         ctx.aux_width, ctx.head_rows = d.aux_width, rows
         ctx.input_grads, ctx.one_row_aux = bool(input_grads), d.aux_stride == 0
         ctx.fused_param_grads = bool(fused_param_grads)
-        ctx.chunk_slabs = chunk_slabs
+        ctx.chunk_slabs, ctx.precision = chunk_slabs, precision
         return out
 
     @staticmethod
@@ -1518,16 +1537,17 @@ class _MlpTrain(torch.autograd.Function):
         n = len(ctx.head_rows)
         trunk, heads = list(zip(params[:8], params[8:16])), list(zip(params[16 : 16 + n], params[16 + n :]))
         d, _, rows, keep = _mlp_desc("mlp_train", None, ctx.aux_width, trunk, heads, _lib.MLP_PLAIN)
+        d.precision = _mlp_precision("mlp_train", ctx.precision)
         g_heads = _f32(g_heads, "g_heads")
         N = g_heads.shape[0]
         want_x, want_aux = (ctx.input_grads and need for need in ctx.needs_input_grad[:2])
         g_x = g_aux = None
         if ctx.chunk_slabs is not None:  # no G: the chain and the products chunk by chunk, in one call
-            gW, gb, gWh, gbh, g_enc = mlp_train_backward(enc, H, g_heads, trunk, heads, ctx.aux_width, rows, want=ctx.needs_input_grad[6:],
-                                                         want_g_enc=want_x or want_aux, chunk_slabs=ctx.chunk_slabs)  # fmt: skip
+            gW, gb, gWh, gbh, g_enc = mlp_train_backward(enc, H, g_heads, trunk, heads, ctx.aux_width, rows, want=ctx.needs_input_grad[7:],
+                                                         want_g_enc=want_x or want_aux, chunk_slabs=ctx.chunk_slabs, precision=ctx.precision)  # fmt: skip
             if g_enc is not None:
                 g_x, g_aux = mlp_input_grads(g_enc, enc, ctx.aux_width, want_x, want_aux, ctx.one_row_aux)
-            return (g_x, g_aux, None, None, None, None, *gW, *gb, *gWh, *gbh)
+            return (g_x, g_aux, None, None, None, None, None, *gW, *gb, *gWh, *gbh)
         G = torch.empty_like(H)
         with torch.cuda.device(G.device):
             if want_x or want_aux:
@@ -1540,15 +1560,15 @@ class _MlpTrain(torch.autograd.Function):
                 ws = torch.empty(int(_lib.load().fg_mlp_train_workspace_bytes(N)), dtype=torch.uint8, device=G.device)
                 _call("fg_mlp_bwd", N, ctypes.addressof(d), _ptr(g_heads), _ptr(H), _ptr(G), _ptr(ws), ws.numel(), _stream())
         if ctx.fused_param_grads:
-            gW, gb, gWh, gbh = mlp_param_grads(enc, H, G, g_heads, ctx.aux_width, rows, want=ctx.needs_input_grad[6:])
-            return (g_x, g_aux, None, None, None, None, *gW, *gb, *gWh, *gbh)
+            gW, gb, gWh, gbh = mlp_param_grads(enc, H, G, g_heads, ctx.aux_width, rows, want=ctx.needs_input_grad[7:])
+            return (g_x, g_aux, None, None, None, None, None, *gW, *gb, *gWh, *gbh)
         gW, gb, gWh, gbh = deform.mlp_param_grads(enc[:, : 63 + ctx.aux_width], H, G, g_heads, rows)
         grads = (*gW, *gb, *gWh, *gbh)
-        return (g_x, g_aux, None, None, None, None, *(g if need else None for g, need in zip(grads, ctx.needs_input_grad[6:])))
+        return (g_x, g_aux, None, None, None, None, None, *(g if need else None for g, need in zip(grads, ctx.needs_input_grad[7:])))
 
 
 def mlp_train(x: torch.Tensor, aux: torch.Tensor, trunk, heads, input_grads: bool = False,
-              fused_param_grads: bool = False, chunked_backward=False) -> torch.Tensor:
+              fused_param_grads: bool = False, chunked_backward=False, precision: str = "fp32") -> torch.Tensor:
     """The network of ``mlp_forward`` for training (``fg_mlp_train_fwd`` / ``fg_mlp_bwd``): the raw head outputs
     ``[N, rows_total]`` (the heads side by side in the order given, bit for bit ``mlp_forward(mode="plain")``), recorded
     for autograd.  The forward keeps the encoded input row and the eight post-ReLU activations (``[8,N,256]``); the
@@ -1562,8 +1582,12 @@ def mlp_train(x: torch.Tensor, aux: torch.Tensor, trunk, heads, input_grads: boo
     ``chunked_backward``: ``True`` or a positive int -- the backward allocates no second ``[8,N,256]`` array: the chain and
     the fused parameter gradients run chunk by chunk in one ``fg_mlp_train_bwd`` call (``mlp_train_backward`` above; the int
     is its ``chunk_slabs``, ``True`` the library's constant), bit for bit the gradients of ``fused_param_grads=True``.  It
-    implies the fused parameter gradients: with ``fused_param_grads=False`` it is a ``ValueError``.  CUDA float32
+    implies the fused parameter gradients: with ``fused_param_grads=False`` it is a ``ValueError``.
+    ``precision``: as for ``mlp_forward``; "bf16x3" runs the forward's trunk and the backward's data chain (in every form
+    above: two calls, with input gradients, chunked) on split-bf16 products.  What is stored stays fp32, and the parameter
+    gradients -- fused or not -- stay exact-fp32 products of it.  CUDA float32
     tensors, N >= 1; ``aux`` as for ``mlp_forward``.  No host synchronisation: capturable."""
+    _mlp_precision("mlp_train", precision)
     chunk_slabs = None
     if chunked_backward is not False and chunked_backward is not None:
         if chunked_backward is True:
@@ -1586,7 +1610,7 @@ def mlp_train(x: torch.Tensor, aux: torch.Tensor, trunk, heads, input_grads: boo
     if input_grads and aux.requires_grad and aux.dim() == 2 and aux.shape[0] > 1 and aux.stride(0) == 0:
         aux = aux[:1]  # (one row for all: autograd's own expand carries the [1, A] sum back)
     params = [w for w, _ in trunk] + [b for _, b in trunk] + [w for w, _ in heads] + [b for _, b in heads]
-    return _MlpTrain.apply(x, aux, len(heads), bool(input_grads), bool(fused_param_grads), chunk_slabs, *params)
+    return _MlpTrain.apply(x, aux, len(heads), bool(input_grads), bool(fused_param_grads), chunk_slabs, precision, *params)
 
 
 # --------------------------------------------------------------------------------------------

@@ -46,6 +46,9 @@ typedef void* fg_stream_t;
 #define FG_SH_JAC_FLOATS 10  /* per-Gaussian note of the SH colour for the backward, see fg_preprocess_fwd */
 #define FG_ABI_VERSION 14
 #define FG_ABI_MINOR 1 /* symbols added since FG_ABI_VERSION was last raised: 1 = fg_abi_minor, fg_mlp_train_bwd* */
+/* (fg_mlp_precision_supported, added later still, is discovered BY NAME -- dlsym, or ctypes' hasattr -- not by the minor
+ * number, which stays 1: a library without the symbol takes fg_mlp_desc::precision as the reserved word it was and
+ * computes in fp32.) */
 #define FG_COUNT_OUT_WORDS 16 /* int64 words of a count_out block (fg_stbin_count, fg_step_io): ABI 9 */
 
 int fg_abi_version(void);
@@ -798,7 +801,8 @@ int fg_knn(int64_t n, const float* xyz, int k, float* dist2_out, int32_t* idx_ou
  * Per row: [posenc(x, 10) (63 wide, computed in the kernel with the accurate sin / cos), aux (aux_width wide)] -> 8 linears
  * of 256 with ReLU, the input row re-injected IN FRONT of h after layer 4 (layer 5's weight is [256, in_ch + 256]) -> up
  * to FG_MLP_MAX_HEADS head linears of together <= 16 rows over the final h.  Weights and biases as nn.Linear stores them
- * ([out, in] row-major).  aux[N, aux_width] has a row stride in floats; stride 0 = one row for all.  Products run on the
+ * ([out, in] row-major).  aux[N, aux_width] has a row stride in floats; stride 0 = one row for all.  Products run (under
+ * precision = FG_MLP_FP32, the default; FG_MLP_BF16X3 is described at the constants below) on the
  * exact-fp32 matrix instructions: every output element is one fmaf chain over its own row in a fixed order, so a row's
  * result does not depend on the other rows or on its place; no atomics.
  *   FG_MLP_SE3   heads (3, 3, 4, 3) = (w, v, rotation, scaling): theta = |w|, screw = (w / theta + 1e-5, v / theta + 1e-5),
@@ -814,6 +818,33 @@ int fg_knn(int64_t n, const float* xyz, int k, float* dist2_out, int32_t* idx_ou
 #define FG_MLP_MAX_HEADS 4
 #define FG_MLP_SE3 0
 #define FG_MLP_PLAIN 1
+/* fg_mlp_desc::precision -- how the products of the trunk and of the backward's data chain are formed.  The word was
+ * `reserved` (same type, same offset, sizeof unchanged): every earlier caller passes 0.
+ *   FG_MLP_FP32    the exact-fp32 matrix instructions, as described above and below.  The default.
+ *   FG_MLP_BF16X3  opt-in: the split-bf16 product on the bf16 matrix instructions.  The contract, which a caller can restate:
+ *     split(v):  hi = bf16(v), round to nearest even (v_cvt_pk_bf16_f32); lo = bf16(v - float(hi)), the subtraction exact in fp32.
+ *     A.B     =  A_hi.B_hi + A_hi.B_lo + A_lo.B_hi, accumulated in fp32 by v_mfma_f32_32x32x16_bf16; A_lo.B_lo is dropped.  The
+ *                accumulator starts from the bias where the fp32 chain does (from 0 in the backward).  Order per output
+ *                element: K in steps of 16, ascending; inside a step the three terms in the order written, each the
+ *                instruction's own sum over k = 16 s + 8 h + j (lane half h, j = 0..7).  Nothing but the element's own row enters.
+ *     where   :  forward -- trunk layers 0..7, both halves of layer 5; backward -- g(h_7) = g_heads W_h, g(h_{l-1}) = P_l W_l,
+ *                and under fg_mlp_bwd_inputs / a non-null g_enc the two g_enc products.  Values are split once: the weights by
+ *                the pack launch of the same call, an activation / gradient tile by the lane that holds its accumulator.
+ *     fp32 as before: the positional encoding, biases, ReLU, the SE(3) epilogue, the mask h_l > 0 (read from acts), and the
+ *                forward's 16-row head product (v_mfma_f32_16x16x4_f32 over the fp32 h_7: 0.6 % of the FLOP).
+ *     stored  :  acts, enc, heads, g_pre, g_enc and the outputs are the fp32 accumulator values, never re-rounded ones, so
+ *                fg_mlp_param_grads runs unchanged, in exact fp32, on them: the WEIGHT-GRADIENT products are not split.
+ *     Against float64 the results stay within 1e-4 of each array's largest magnitude (measured: about 1e-5, an order above
+ *     fp32's 1e-6); a pre-activation moves by about 5e-6 of its layer's scale, so a row within that of a ReLU kink may take the
+ *     other branch.  Two runs are bit for bit equal, rows are independent of one another and of their tile, no atomics;
+ *     non-finite inputs give non-finite outputs (|v| beyond bf16's largest finite value, 3.39e38, splits to infinity).
+ *     Workspace sizes, arguments and error codes are those of FG_MLP_FP32.
+ * Honoured by fg_mlp_fwd, fg_mlp_train_fwd, fg_mlp_bwd, fg_mlp_bwd_inputs and fg_mlp_train_bwd (whose chunks run the same
+ * chain kernel); IGNORED by fg_mlp_param_grads (always fp32).  Any other value: FG_ERR_INVALID_ARG from the five calls.
+ * fg_mlp_precision_supported(precision) = 1 where this library takes the value, else 0: ask before the call. */
+#define FG_MLP_FP32 0
+#define FG_MLP_BF16X3 1
+int fg_mlp_precision_supported(int32_t precision);
 typedef struct fg_mlp_desc {
   int32_t size; /* sizeof(fg_mlp_desc) */
   int32_t mode;
@@ -821,7 +852,7 @@ typedef struct fg_mlp_desc {
   int32_t aux_width;
   int32_t n_heads;
   int32_t head_rows[FG_MLP_MAX_HEADS];
-  int32_t reserved;
+  int32_t precision; /* FG_MLP_FP32 (0) or FG_MLP_BF16X3 */
   int64_t aux_stride;
   const float* x;   /* [N,3] */
   const float* aux; /* [N or 1, aux_width] */

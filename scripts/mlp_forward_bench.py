@@ -17,6 +17,16 @@ fault or a time limit in one step starts nothing more on the GPU):
                    trained:auto``), else 240 000 random Gaussians at 1920 x 1080 -- the table says which
     --step trace   three fused calls at N = 240 000 for ``rocprofv3 --kernel-trace --stats`` (with --trace; a run of its own)
     --step report  profiles/mlp_forward.md from these
+
+    python scripts/mlp_forward_bench.py --precision [--trace] [--out results/mlp_split]
+
+compares the opt-in split-bf16 mode (``precision="bf16x3"`` / ``FG_FUSED_MLP_PRECISION``) with the fp32 path OF THE SAME BUILD,
+same protocol (the two sides alternate call by call); ``scripts/mlp_train_bench.py --precision`` adds the training side and
+writes profiles/mlp_split_bf16.md from both:
+
+    --step ptime   ``ops.mlp_forward`` (``fg_mlp_fwd`` alone: points, rotations, scalings) at the three sizes
+    --step pframe  ``get_outputs_for_camera`` per frame, ``FG_FUSED_MLP_PRECISION`` set and unset alternating
+    --step ptrace  three calls of either precision at N = 240 000 for ``rocprofv3 --kernel-trace --stats`` (with --trace)
 """
 import argparse
 import copy
@@ -141,10 +151,58 @@ def step_error(out):
     json.dump(res, open(os.path.join(out, "error.json"), "w"), indent=1)
 
 
+def _precision_knob(value):
+    if value == "fp32":
+        os.environ.pop("FG_FUSED_MLP_PRECISION", None)
+    else:
+        os.environ["FG_FUSED_MLP_PRECISION"] = value
+
+
+def _forward_pair(m, n):
+    """(run(precision), flops per row) of ``ops.mlp_forward`` over n rows into buffers made once: one time for all rows."""
+    from freegaussian_amd import ops
+    from freegaussian_amd.utils import positional_encoding
+
+    x = (torch.rand(n, 3, generator=torch.Generator().manual_seed(n)) * 2 - 1).cuda()
+    aux = positional_encoding(torch.full((1, 1), 0.4, device="cuda"), m.t_multires)
+    heads = (m.branch_w, m.branch_v, m.gaussian_rotation, m.gaussian_scaling)
+    outs = [False] + [torch.empty(n, c, device="cuda") for c in (4, 3, 3)]
+
+    def run(precision):
+        def go():
+            return ops.mlp_forward(x, aux, m.linear, heads, mode="se3", outs=outs, precision=precision)
+        return go
+
+    return run
+
+
+def pstep_time(out):
+    m = _module().cuda().requires_grad_(False)
+    fl = flops_per_row(m)
+    res = {"flops_per_row": fl, "sizes": {}}
+    for n in SIZES:
+        run = _forward_pair(m, n)
+        s, f = _timed_pair(run("bf16x3"), run("fp32"))
+        qs, qf = _quantiles(s), _quantiles(f)
+        res["sizes"][str(n)] = {"split_ms": qs, "fp32_ms": qf, "ratio": qs["median"] / qf["median"],
+                                "split_tflops": fl * n / qs["median"] / 1e9, "fp32_tflops": fl * n / qf["median"] / 1e9}  # fmt: skip
+        print(n, res["sizes"][str(n)], flush=True)
+    json.dump(res, open(os.path.join(out, "ptime.json"), "w"), indent=1)
+
+
+def pstep_trace(out):
+    m = _module().cuda().requires_grad_(False)
+    run = _forward_pair(m, 240_000)
+    for precision in ("bf16x3", "fp32"):
+        for _ in range(3):
+            run(precision)()
+    torch.cuda.synchronize()
+
+
 TRAINED = os.path.join(ROOT, "data", "trained_scene_r06.npz")  # (what bench.py --layout trained:auto takes; not in the history)
 
 
-def step_frame(out):
+def step_frame(out, precision=False):
     from freegaussian_amd.model import Camera, FreeGaussianModel, FreeGaussianModelConfig
     from freegaussian_amd.scenes import load_trained_scene, look_at_viewmat
 
@@ -185,6 +243,19 @@ def step_frame(out):
             return model.get_outputs_for_camera(cam)["rgb"]
         return run
 
+    if precision:  # the fused forward on both sides, FG_FUSED_MLP_PRECISION set and unset
+        _knob("1")
+
+        def frame_at(value):
+            def run():
+                _precision_knob(value)
+                return model.get_outputs_for_camera(cam)["rgb"]
+            return run
+
+        s, f = _timed_pair(frame_at("bf16x3"), frame_at("fp32"), warm=5, timed=30)
+        res = {"n": n, "width": W, "height": H, "source": source, "split_ms": _quantiles(s), "fp32_ms": _quantiles(f)}
+        print(res, flush=True)
+        return json.dump(res, open(os.path.join(out, "pframe.json"), "w"), indent=1)
     f, p = _timed_pair(frame("1"), frame("0"), warm=5, timed=30)
     res = {"n": n, "width": W, "height": H, "source": source, "fused_ms": _quantiles(f), "torch_ms": _quantiles(p)}
     print(res, flush=True)
@@ -248,15 +319,19 @@ def step_report(out, md):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--step", choices=["time", "error", "frame", "trace", "report"])
+    ap.add_argument("--step", choices=["time", "error", "frame", "trace", "report", "ptime", "pframe", "ptrace"])
+    ap.add_argument("--precision", action="store_true", help="the split-bf16 mode against fp32, the forward's share of profiles/mlp_split_bf16.md")
     ap.add_argument("--trace", action="store_true", help="also one rocprofv3 --kernel-trace --stats run of the fused calls")
-    ap.add_argument("--out", default=os.path.join(ROOT, "results", "mlp_forward"))
+    ap.add_argument("--out", default=None, help="default: results/mlp_forward, results/mlp_split with --precision")
     ap.add_argument("--md", default=os.path.join(ROOT, "profiles", "mlp_forward.md"))
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, "results", "mlp_split" if a.precision or (a.step or "").startswith("p") else "mlp_forward")
     os.makedirs(a.out, exist_ok=True)
     if a.step:
         if a.step == "report":
             return step_report(a.out, a.md)
+        if a.step.startswith("p"):
+            return {"ptime": pstep_time, "pframe": lambda out: step_frame(out, precision=True), "ptrace": pstep_trace}[a.step](a.out)
         return {"time": step_time, "error": step_error, "frame": step_frame, "trace": step_trace}[a.step](a.out)
     me = [sys.executable, os.path.abspath(__file__), "--out", a.out, "--md", a.md, "--step"]
     steps = [(240, me + ["time"]), (180, me + ["error"]), (240, me + ["frame"])]
@@ -264,6 +339,11 @@ def main():
         steps.append((180, ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", os.path.join(a.out, "trace"),
                             "-o", "mlp", "--"] + me + ["trace"]))  # fmt: skip
     steps.append((60, me + ["report"]))
+    if a.precision:
+        steps = [(240, me + ["ptime"]), (240, me + ["pframe"])]
+        if a.trace:
+            steps.append((180, ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", os.path.join(a.out, "ptrace_fwd"),
+                                "-o", "mlp", "--"] + me + ["ptrace"]))  # fmt: skip
     for limit, cmd in steps:  # chained like &&: the first failure ends the job
         rc = subprocess.call(["timeout", "-k", "10", str(limit)] + cmd)
         if rc != 0:

@@ -60,6 +60,19 @@ profiles/mlp_chunked_bwd.md.  Its steps, each a child process as above:
 With ``--parent-lib FILE`` (the library built from the parent commit) it also runs ``--step wcall`` and ``--step kernel
 --blender`` once on each build (``--lib``: the library a step loads), for the table that shows what the kernels' new
 arguments cost the existing entry points.
+
+With ``--precision`` it compares the opt-in split-bf16 mode (``FG_FUSED_MLP_PRECISION=bf16x3``; include/fgraster.h has the
+contract) with the fp32 path OF THE SAME BUILD, the two sides alternating call by call, and writes
+profiles/mlp_split_bf16.md from these and from what ``scripts/mlp_forward_bench.py --precision`` left in the same directory
+(results/mlp_split):
+
+    --step ptrain  the whole fused training call (``ops.mlp_train`` forward + backward through the module,
+                   ``FG_FUSED_MLP_WGRAD=1``), the deformation net and with --blender the blender net, at the three sizes
+    --step pmodel  one model training step at 240 000 Gaussians, 960 x 540 (with --blender: the blender model)
+    --step perror  every stored array and the gradients at N = 33 000 against float64 on the CPU, split beside fp32, over
+                   all rows and over the rows clear of the ReLU's kink by 1e-4
+    --step ptrace  three training calls of either precision at N = 240 000 for ``rocprofv3`` (with --trace)
+    --step preport profiles/mlp_split_bf16.md
 """
 import argparse
 import copy
@@ -965,11 +978,241 @@ def step_report(out, md, parity):
     open(md, "w").write("\n".join(L) + "\n")
     print("\n".join(L))
 
+# ---- --precision: the split-bf16 mode against fp32 (profiles/mlp_split_bf16.md) -------------------------------------------
+PRECISION_KNOB = "FG_FUSED_MLP_PRECISION"
+
+
+def _precision_knob(value):
+    if value == "fp32":
+        os.environ.pop(PRECISION_KNOB, None)
+    else:
+        os.environ[PRECISION_KNOB] = value
+
+
+def _count_precisions():
+    from freegaussian_amd import ops
+
+    seen = []
+    real = ops.mlp_train
+    ops.mlp_train = lambda *a, **k: seen.append(k.get("precision", "fp32")) or real(*a, **k)
+    return seen
+
+
+def pstep_train(out):
+    m = _module().cuda()
+    _knob(True)
+    _wgrad_knob(True)
+    seen, res = _count_precisions(), {"flops_per_row": flops_per_row(m)}
+    for n in SIZES:
+        g = torch.Generator().manual_seed(n)
+        x = (torch.rand(n, 3, generator=g) * 2 - 1).cuda()
+        t = torch.full((1, 1), 0.4, device="cuda").expand(n, -1)
+        cots = [torch.randn(n, *s, generator=g).cuda() for s in ((4, 4), (4,), (3,))]
+
+        def run(value):
+            def go():
+                _precision_knob(value)
+                _train_call(m, x, t, cots)
+            return go
+
+        before = len(seen)
+        s_, f = _timed_pair(run("bf16x3"), run("fp32"))
+        assert seen[before:] == ["bf16x3", "fp32"] * (WARM + TIMED)  # both sides took the fused call, each in its own mode
+        qs, qf = _quantiles(s_), _quantiles(f)
+        res[str(n)] = {"split_ms": qs, "fp32_ms": qf, "ratio": qs["median"] / qf["median"]}
+        print(n, res[str(n)], flush=True)
+    json.dump(res, open(os.path.join(out, "ptrain_blender.json" if BLENDER else "ptrain.json"), "w"), indent=1)
+
+
+def pstep_model(out):
+    from freegaussian_amd.model import Camera, FreeGaussianModel, FreeGaussianModelConfig
+    from freegaussian_amd.scenes import look_at_viewmat
+
+    torch.manual_seed(0)
+    n, W, H = 240_000, 960, 540
+    cfg = FreeGaussianModelConfig(background_color="white", num_downscales=0, warm_up=3000)
+    model = FreeGaussianModel(cfg, seed_points=(torch.rand(n, 3) - 0.5) * 2.0, init_scales=-4.5, is_blender=BLENDER)
+    with torch.no_grad():
+        for q in model.deform.parameters():
+            q.mul_(0.3)
+    model.step = 4000
+    model = model.cuda().train()
+    c2w = torch.linalg.inv(look_at_viewmat(torch.tensor([0.3, -0.2, -3.0]), torch.zeros(3)))
+    c2w[:3, 1:3] *= -1
+    cam = Camera(c2w[None, :3], 750.0, 750.0, W / 2, H / 2, W, H, times=torch.tensor([[0.4]]))
+    gt = torch.rand(H, W, 3, device="cuda")
+    _knob(True)
+    _wgrad_knob(True)
+    seen = _count_precisions()
+
+    def step(value):
+        def run():
+            _precision_knob(value)
+            model.zero_grad(set_to_none=True)
+            model.get_loss_dict(model.get_outputs(cam), {"image": gt})["main_loss"].backward()
+        return run
+
+    warm, timed = 5, 30
+    s_, f = _timed_pair(step("bf16x3"), step("fp32"), warm=warm, timed=timed)
+    assert seen == ["bf16x3", "fp32"] * (warm + timed)
+    res = {"n": n, "width": W, "height": H, "split_ms": _quantiles(s_), "fp32_ms": _quantiles(f)}
+    print(res, flush=True)
+    json.dump(res, open(os.path.join(out, "pmodel_blender.json" if BLENDER else "pmodel.json"), "w"), indent=1)
+
+
+def pstep_error(out):
+    import ctypes
+
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from mlp_inputs_common import float64_with_input_row, rows_clear_of_the_kink_aux  # (the references of the tests)
+    from mlp_split_common import MARGIN, float64_acts
+    from mlp_train_common import head_rows, heads_of
+
+    from freegaussian_amd import _lib, ops
+    from freegaussian_amd.utils import positional_encoding
+
+    n = 33_000
+    m = _module()
+    g = torch.Generator().manual_seed(1)
+    x, t = torch.rand(n, 3, generator=g) * 2 - 1, torch.rand(n, 1, generator=g)
+    with torch.no_grad():
+        aux = positional_encoding(t, m.t_multires)
+        aux = m.timenet(aux) if BLENDER else aux
+    gh = torch.randn(n, sum(head_rows(m)), generator=g)
+    clear = rows_clear_of_the_kink_aux(m, x, aux, margin=MARGIN)
+    ref = float64_with_input_row(m, x, aux, gh)
+    ref["H"] = float64_acts(m, x, aux)
+    md = copy.deepcopy(m).cuda().requires_grad_(False)
+    xd, ad, gd = x.cuda(), aux.cuda(), gh.cuda()
+    A, in_ch, lib = aux.shape[1], 63 + aux.shape[1], _lib.load()
+
+    def arrays(precision):
+        d, _, rows, keep = ops._mlp_desc("bench", xd, ad, md.linear, heads_of(md), _lib.MLP_PLAIN)
+        d.precision = precision
+        raw, enc, H = torch.empty(n, sum(rows), device="cuda"), torch.empty(n, _lib.mlp_enc_width(A), device="cuda"), torch.empty(8, n, 256, device="cuda")
+        G, ge = torch.empty_like(H), torch.empty_like(enc)
+        ws = torch.empty(int(lib.fg_mlp_bwd_inputs_workspace_bytes(n)), dtype=torch.uint8, device="cuda")
+        ops._call("fg_mlp_train_fwd", n, ctypes.addressof(d), raw.data_ptr(), enc.data_ptr(), H.data_ptr(), ws.data_ptr(), ws.numel(), ops._stream())
+        ops._call("fg_mlp_bwd_inputs", n, ctypes.addressof(d), gd.data_ptr(), H.data_ptr(), G.data_ptr(), ge.data_ptr(), ws.data_ptr(),
+                  ws.numel(), ops._stream())  # fmt: skip
+        torch.cuda.synchronize()
+        return {"heads": raw, "acts": H.transpose(0, 1), "g_pre": G.transpose(0, 1), "g_enc": ge[:, :in_ch]}
+
+    def rel(a, b):
+        return float((a.detach().double().cpu() - b).abs().max() / b.abs().max())
+
+    want = {"heads": ref["raw"], "acts": ref["H"].transpose(0, 1), "g_pre": ref["G"].transpose(0, 1), "g_enc": ref["g_enc"]}
+    got = {"split": arrays(_lib.MLP_BF16X3), "fp32": arrays(_lib.MLP_FP32)}
+    res = {"rows": {"all rows": n, "rows clear of the ReLU kink": int(clear.sum())}, "margin": MARGIN, "arrays": {}}
+    for label, rows in (("all rows", torch.ones(n, dtype=torch.bool)), ("rows clear of the ReLU kink", clear)):
+        for k, w in want.items():
+            res["arrays"][f"{k}, {label}"] = {side: rel(got[side][k][rows.cuda()], w[rows]) for side in got}
+    # the masks: rows whose ReLU mask differs from float64's in any unit
+    for side in got:
+        flipped = ((got[side]["acts"].cpu() > 0) != (ref["H"].transpose(0, 1) > 0)).flatten(1).any(1)
+        res.setdefault("rows with a flipped mask", {})[side] = {"all rows": int(flipped.sum()), "rows clear of the ReLU kink": int((flipped & clear).sum())}
+    print(res, flush=True)
+    json.dump(res, open(os.path.join(out, "perror_blender.json" if BLENDER else "perror.json"), "w"), indent=1)
+
+
+def pstep_trace(out):
+    m = _module().cuda()
+    n = 240_000
+    x = (torch.rand(n, 3) * 2 - 1).cuda()
+    t = torch.full((1, 1), 0.4, device="cuda").expand(n, -1)
+    cots = [torch.randn(n, *s).cuda() for s in ((4, 4), (4,), (3,))]
+    _knob(True)
+    _wgrad_knob(True)
+    for value in ("bf16x3", "fp32"):
+        _precision_knob(value)
+        for _ in range(3):
+            _train_call(m, x, t, cots)
+    torch.cuda.synchronize()
+
+
+def _gain(s, f):
+    """The outcome rule: a gain = the split median below the fp32 median with p10 .. p90 that do not overlap."""
+    if s["median"] < f["median"] and s["p90"] < f["p10"]:
+        return "gain"
+    if s["median"] > f["median"] and s["p10"] > f["p90"]:
+        return "loss"
+    return "no difference (the p10 .. p90 ranges overlap)"
+
+
+def pstep_report(out, md):
+    def load(name):
+        path = os.path.join(out, name)
+        return json.load(open(path)) if os.path.exists(path) else None
+
+    def span(q, digits=3):
+        return f"{q['median']:.{digits}f} ({q['p10']:.{digits}f} .. {q['p90']:.{digits}f})"
+
+    L = ["# Split-bf16 (3-product) mode of the fused MLP kernels against their fp32 mode", "",
+         "Written by `scripts/mlp_forward_bench.py --precision` and `scripts/mlp_train_bench.py --precision` on an MI355X.  The",
+         "baseline is always the fp32 path of the same build; the two sides alternate call by call in one process per table,",
+         f"{WARM} warm-up and {TIMED} timed calls each between device events (5 and 30 for the model step and the frame); median (p10 .. p90).",
+         "Outcome rule: a gain = the split median below the fp32 median with p10 .. p90 ranges that do not overlap, at 240 000 rows,",
+         "for (a) and for (b)."]  # fmt: skip
+    verdicts = {}
+    pt = load("ptime.json")
+    if pt:
+        L += ["", "## (a) `fg_mlp_fwd` alone (`ops.mlp_forward`: points, rotations, scalings; one time for all rows)", "",
+              "| N | bf16x3 ms | fp32 ms | bf16x3 / fp32 | bf16x3 TFLOP/s | fp32 TFLOP/s | by the rule |", "|---|---|---|---|---|---|---|"]  # fmt: skip
+        for n, r in pt["sizes"].items():
+            L.append(f"| {int(n):,} | {span(r['split_ms'])} | {span(r['fp32_ms'])} | {r['ratio']:.2f} | {r['split_tflops']:.1f} | "
+                     f"{r['fp32_tflops']:.1f} | {_gain(r['split_ms'], r['fp32_ms'])} |")  # fmt: skip
+        verdicts["(a)"] = _gain(pt["sizes"]["240000"]["split_ms"], pt["sizes"]["240000"]["fp32_ms"])
+    for name, title in (("ptrain.json", "deformation net, `FG_FUSED_MLP_TRAIN=1`"), ("ptrain_blender.json", "blender net, `FG_FUSED_MLP_TRAIN=2`")):
+        tr = load(name)
+        if tr:
+            L += ["", f"## (b) The whole `ops.mlp_train` forward + backward, `FG_FUSED_MLP_WGRAD=1`: {title}", "",
+                  "| N | bf16x3 ms | fp32 ms | bf16x3 / fp32 | by the rule |", "|---|---|---|---|---|"]  # fmt: skip
+            for n in (str(v) for v in SIZES):
+                if n in tr:
+                    L.append(f"| {int(n):,} | {span(tr[n]['split_ms'])} | {span(tr[n]['fp32_ms'])} | {tr[n]['ratio']:.2f} | {_gain(tr[n]['split_ms'], tr[n]['fp32_ms'])} |")
+            verdicts[f"(b) {title.split(',')[0]}"] = _gain(tr["240000"]["split_ms"], tr["240000"]["fp32_ms"])
+    rows = [(load("pmodel.json"), "model training step, deformation net"), (load("pmodel_blender.json"), "model training step, blender net")]
+    if any(r for r, _ in rows):
+        L += ["", "## (c) One model training step at 240 000 Gaussians, 960 x 540, behind `warm_up` (`FG_FUSED_MLP_TRAIN` and `_WGRAD` set)", "",
+              "| model | bf16x3 ms | fp32 ms | bf16x3 / fp32 |", "|---|---|---|---|"]  # fmt: skip
+        L += [f"| {title} | {span(r['split_ms'], 2)} | {span(r['fp32_ms'], 2)} | {r['split_ms']['median'] / r['fp32_ms']['median']:.2f} |" for r, title in rows if r]
+    fr = load("pframe.json")
+    if fr:
+        L += ["", f"## (d) `get_outputs_for_camera` per frame ({fr['source']}: {fr['n']:,} Gaussians, {fr['width']} x {fr['height']}, eval)", "",
+              "| bf16x3 ms | fp32 ms | bf16x3 / fp32 |", "|---|---|---|",
+              f"| {span(fr['split_ms'], 2)} | {span(fr['fp32_ms'], 2)} | {fr['split_ms']['median'] / fr['fp32_ms']['median']:.2f} |"]  # fmt: skip
+    for sub, title in (("ptrace_fwd", "three `ops.mlp_forward` calls of either precision"), ("ptrace", "three training calls of either precision, `FG_FUSED_MLP_WGRAD=1`")):
+        stats = sorted(glob.glob(os.path.join(out, sub, "**", "*kernel_stats.csv"), recursive=True))
+        if stats:
+            L += ["", f"## (e) Kernels of {title} at N = 240 000 (`rocprofv3 --kernel-trace --stats`, a run of its own)", "",
+                  "| kernel | calls | average us | share % |", "|---|---|---|---|"]  # fmt: skip
+            for r in list(csv.DictReader(open(stats[0])))[:14]:
+                L.append(f"| `{r['Name'][:90]}` | {r['Calls']} | {float(r['AverageNs']) / 1e3:.1f} | {float(r['Percentage']):.1f} |")
+    for name, title in (("perror.json", "deformation net"), ("perror_blender.json", "blender net")):
+        er = load(name)
+        if er:
+            L += ["", f"## (f) Error against float64 at N = 33 000 ({title}, default init, a time per row; max |a - b| / max |b|; the bar is 1e-4)", "",
+                  f"Rows clear of the ReLU's kink by {er['margin']:g} of the layer's largest pre-activation: {er['rows']['rows clear of the ReLU kink']:,} of "
+                  f"{er['rows']['all rows']:,}.  Rows with a ReLU mask other than float64's in any unit -- bf16x3: {er['rows with a flipped mask']['split']['all rows']} of all "
+                  f"rows, {er['rows with a flipped mask']['split']['rows clear of the ReLU kink']} of the clear ones; fp32: {er['rows with a flipped mask']['fp32']['all rows']} and "
+                  f"{er['rows with a flipped mask']['fp32']['rows clear of the ReLU kink']}.  A row with a flipped mask has another gradient, whatever computed it.", "",
+                  "| array, rows | bf16x3 | fp32 |", "|---|---|---|"]  # fmt: skip
+            L += [f"| {k} | {v['split']:.2e} | {v['fp32']:.2e} |" for k, v in er["arrays"].items()]
+    if verdicts:
+        L += ["", "## Outcome by the rule (240 000 rows)", ""] + [f"- {k}: **{v}**" for k, v in verdicts.items()]
+    # (hand-written sections of the file -- everything from the first "## Notes" heading on -- are kept)
+    if os.path.exists(md) and "\n## Notes" in open(md).read():
+        L += ["", "## Notes" + open(md).read().split("\n## Notes", 1)[1].rstrip()]
+    open(md, "w").write("\n".join(L) + "\n")
+    print("\n".join(L))
+
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--step", choices=["time", "error", "model", "trace", "kernel", "report", "wcall", "werror", "wtrain", "wmodel",
-                                       "wtrace", "wreport", "ccall", "ctrain", "cmodel", "cmem", "ctrace", "creport"])  # fmt: skip
+                                       "wtrace", "wreport", "ccall", "ctrain", "cmodel", "cmem", "ctrace", "creport", "ptrain", "pmodel", "perror",
+                                       "ptrace", "preport"])  # fmt: skip
+    ap.add_argument("--precision", action="store_true", help="the split-bf16 mode, FG_FUSED_MLP_PRECISION, against fp32 (profiles/mlp_split_bf16.md)")
     ap.add_argument("--chunked", action="store_true", help="the backward in row chunks, FG_FUSED_MLP_CHUNKED (profiles/mlp_chunked_bwd.md)")
     ap.add_argument("--only", default=None, help="with --chunked: a comma-separated subset of its steps (ccall,base,ctrain,cmodel,cmem,ctrace,creport)")
     ap.add_argument("--parent-lib", default=None, help="with --chunked: the parent commit's build of the library, for the side-by-side table")
@@ -988,12 +1231,18 @@ def main():
         name = "mlp_wgrad"
     if a.chunked or (a.step or "").startswith("c"):
         name = "mlp_chunked_bwd"
+    if a.precision or (a.step or "").startswith("p"):
+        name = "mlp_split"
     if a.lib:
         _use_library(a.lib)
     a.out = a.out or os.path.join(ROOT, "results", name)
-    a.md = a.md or os.path.join(ROOT, "profiles", name + ".md")
+    a.md = a.md or os.path.join(ROOT, "profiles", "mlp_split_bf16.md" if name == "mlp_split" else name + ".md")
     os.makedirs(a.out, exist_ok=True)
     if a.step:
+        if a.step == "preport":
+            return pstep_report(a.out, a.md)
+        if a.step.startswith("p"):
+            return {"ptrain": pstep_train, "pmodel": pstep_model, "perror": pstep_error, "ptrace": pstep_trace}[a.step](a.out)
         if a.step == "report":
             return step_report(a.out, a.md, a.parity)
         if a.step == "wreport":
@@ -1040,6 +1289,14 @@ def main():
         steps = [s for name in order if not a.only or name in a.only.split(",") for s in groups[name]]
     elif not a.wgrad:
         steps.append((60, me + ["report"] + (["--parity", a.parity] if a.parity else [])))
+    if a.precision:
+        me = [sys.executable, os.path.abspath(__file__), "--out", a.out, "--md", a.md, "--step"]
+        steps = [(240, me + ["ptrain"]), (240, me + ["ptrain", "--blender"]), (240, me + ["pmodel"]), (240, me + ["pmodel", "--blender"]),
+                 (300, me + ["perror"])]  # fmt: skip
+        if a.trace:
+            steps.append((180, ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", os.path.join(a.out, "ptrace"),
+                                "-o", "mlp", "--"] + me + ["ptrace"]))  # fmt: skip
+        steps.append((60, me + ["preport"]))
     for limit, cmd in steps:  # chained like &&: the first failure ends the job
         rc = subprocess.call(["timeout", "-k", "10", str(limit)] + cmd)
         if rc != 0:
