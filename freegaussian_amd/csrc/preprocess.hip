@@ -470,7 +470,9 @@ preprocess_bwd_kernel(int N, FeatLayout fl, RawForm raw, float* __restrict__ v_d
       for (int c = 0; c < 4; ++c) g_q[c] = (g_q[c] - dp * a.qn[c]) * a.inv_norm;  // through q/|q|
 #pragma unroll
       for (int c = 0; c < 3; ++c) g_s[c] *= a.es[c];                              // through exp
-      g_o *= a.o * (1.f - a.o);                                                   // through sigmoid
+      // through sigmoid: 1 - o = exp(-x) o where x > 0 -- at a logit of 12, 1 - o formed from o (0.999994) keeps two digits
+      const float logit = opacities[i2];
+      g_o *= a.o * (logit > 0.f ? expf(-logit) * a.o : 1.f - a.o);
     }
     // ---- K8 (behind K7: the means' gradient gets the SH colour's share added) ------------------------
     if (NOTE && kk > 0) view_direction();

@@ -37,7 +37,7 @@ struct Fwd {
   float rz, rz2, tx, ty;
   bool in_x, in_y;  // FOV clamp inactive
   float ja, jb, jc, jd;
-  float c00, c01, c11;  // blurred 2D covariance
+  float o00, c01, o11;  // 2D covariance BEFORE the blur (the blurred diagonal is o00 + eps2d, o11 + eps2d, as rounded here)
   float det_orig, det;
   float m2x, m2y;
   float conic_a, conic_b, conic_c, comp;
@@ -117,10 +117,10 @@ __device__ __forceinline__ Fwd project_core(const Cam& cam, float mx, float my, 
   f.m2y = (cam.fy * f.py) * f.rz + cam.cy;
 
   f.det_orig = c00 * c11 - c01 * c01;
+  f.o00 = c00; f.c01 = c01; f.o11 = c11;
   c00 = c00 + eps2d;
   c11 = c11 + eps2d;
   f.det = c00 * c11 - c01 * c01;
-  f.c00 = c00; f.c01 = c01; f.c11 = c11;
   f.comp = sqrtf(fmaxf(f.det_orig / f.det, 0.0f));
   const float inv_det = 1.0f / f.det;
   f.conic_a = c11 * inv_det;
@@ -151,12 +151,14 @@ __device__ __forceinline__ void project_backward_camera(const Cam& cam, const Fw
     float g01 = -(qa * x01 + qb * x11);
     float g11 = -(qb * x01 + qc * x11);
     if (with_comp) {
-      // comp = sqrt(det_orig/det), both functions of the unblurred covariance o = c - eps
+      // comp = sqrt(det_orig/det), both functions of the unblurred covariance o = c - eps: the forward's own o, not
+      // c - eps formed again (a sub-pixel Gaussian's o is 1e-4 of the 0.3 blur: the difference keeps 3 of its digits)
       if (f.comp > 0.f && vcomp != 0.f) {
-        const float o00 = f.c00 - eps2d, o11 = f.c11 - eps2d, o01 = f.c01;
+        const float o00 = f.o00, o11 = f.o11, o01 = f.c01;
+        const float c00 = o00 + eps2d, c11 = o11 + eps2d;  // (the forward's blurred diagonal, bit for bit)
         const float k = vcomp * 0.5f / f.comp / (f.det * f.det);
-        g00 += k * (o11 * f.det - f.det_orig * f.c11);
-        g11 += k * (o00 * f.det - f.det_orig * f.c00);
+        g00 += k * (o11 * f.det - f.det_orig * c11);
+        g11 += k * (o00 * f.det - f.det_orig * c00);
         // c01 appears twice in the symmetric matrix: half of d/d(o01) goes to each slot
         g01 += k * (o01 * (f.det_orig - f.det));
       }
