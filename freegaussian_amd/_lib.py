@@ -120,6 +120,12 @@ SIGNATURES = {
     "fg_mlp_train_bwd_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32]),  # (N, chunk_slabs, want_g_enc)
     # (N, desc, g_heads, enc, acts, g_enc, const fg_mlp_grads*, chunk_slabs, workspace, bytes, stream)
     "fg_mlp_train_bwd": (c_int, [c_int64, P, P, P, P, P, P, c_int32, P, c_size_t, P]),
+    # the two calls above with a precision word for the weight-gradient products (FG_MLP_FP32 / FG_MLP_BF16X3)
+    "fg_mlp_wgrad_precision_supported": (c_int, [c_int32]),
+    # (N, desc, enc, acts, g_pre, g_heads, const fg_mlp_grads*, wgrad_precision, workspace, bytes, stream)
+    "fg_mlp_param_grads_p": (c_int, [c_int64, P, P, P, P, P, P, c_int32, P, c_size_t, P]),
+    # (N, desc, g_heads, enc, acts, g_enc, const fg_mlp_grads*, chunk_slabs, wgrad_precision, workspace, bytes, stream)
+    "fg_mlp_train_bwd_p": (c_int, [c_int64, P, P, P, P, P, P, c_int32, c_int32, P, c_size_t, P]),
 }  # fmt: skip
 
 # test hooks, not declared in the public header

@@ -31,6 +31,9 @@
 //              columns k >= in_ch of the input products, and elements of outputs not asked for, are not looked at.
 // Rows beyond a slab's end (so beyond N) are never read: both operand tiles hold zeros there.  Columns k >= in_ch of enc
 // are replaced by zeros as they are read.  Two runs on the same inputs are bit for bit equal, whatever else the device does.
+// fg_mlp_param_grads_p / fg_mlp_train_bwd_p take a precision word for the hidden and input products: FG_MLP_FP32 is all of the
+// above (the old entry points pass it); FG_MLP_BF16X3 runs the tile jobs as split-bf16 products in a kernel of their own
+// (mlp_wgrad_split_kernel, further down), everything else unchanged.
 #include "fg_common.h"
 #include "mlp_internal.h"
 
@@ -299,6 +302,200 @@ __global__ void __launch_bounds__(WG_BLOCK) mlp_wgrad_reduce_kernel(const float*
   *dst = s;
 }
 
+// ---- wgrad_precision = FG_MLP_BF16X3: the same jobs, slabs, partial blocks and reduction; the 128 x 128 tile job on
+// v_mfma_f32_32x32x16_bf16, every operand as hi + lo (the contract: include/fgraster.h).  The head jobs are wg_head_job above.
+//   k order  : the contraction runs over the ROWS, so a bf16 fragment wants 8 consecutive rows of one column in one lane: the A
+//              lane (i, h) holds P[rows 16 s + 8 h + j][col i], the B lane (h, j') in[rows 16 s + 8 h + j][col j'], j = 0..7.
+//   step     : 64 rows.  Thread t fetches rows 8 (t & 7) .. + 7 of the four columns 4 (t >> 3) .. + 3 of each operand -- eight
+//              16-byte loads an operand, a wave's load covers 8 rows x 128 bytes (whole cache lines), the next step's issued
+//              before the current step's MFMAs -- splits the 32 values in registers (once per value and job) and writes each column's 8 hi
+//              and 8 lo as one 16-byte LDS store each: the transpose happens in the registers.
+//   LDS      : [128 columns][hi 64 | lo 64 | pad 8] bf16 per operand, 34 816 bytes, 69 632 together: two workgroups a CU.
+//              The column stride is 68 dwords = 4 mod 64.  Stores (bank = dword mod 32, groups of 8 consecutive lanes): the 8
+//              lanes of a group hold the 8 row groups of one column, 16 bytes apart: 32 distinct banks.  Reads (16 bytes, bank =
+//              dword mod 64, the 16-lane groups of ds_read_b128): 16 columns of one lane half, 4 banks apart: 64 distinct banks.
+//   products : per 16-row step s an accumulator takes P_hi.in_hi, then P_hi.in_lo, then P_lo.in_hi; the steps ascend.
+//   bias     : the fp32 column sums come from the fetched registers, before the split: per step a thread adds its 8 rows of
+//              a column in row order and that to its running sum (one per row group r = 0..7 of the 64-row steps); at the end
+//              the 8 running sums of a column are added in the order r = 0..7.
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+constexpr int WGS_K = 64;                  // rows per step: four k-steps of the instruction
+constexpr int WGS_LO = WGS_K;              // where a column's lo values start
+constexpr int WGS_STRIDE = 2 * WGS_K + 8;  // bf16 of a column of the image: 68 dwords
+static_assert(2 * WG_T * WGS_STRIDE * sizeof(__bf16) <= 80 * 1024, "two workgroups share a CU's LDS");
+static_assert(8 * WG_T * sizeof(float) <= WG_T * WGS_STRIDE * sizeof(__bf16), "the bias sums meet in the A image");
+
+// 64 rows x 128 columns into registers: thread t takes the four floats at column 4 (t >> 3) of rows 8 (t & 7) + q.  Rows
+// from `end` on and columns from `cols_ld` on are zeros and are not read (wg_fetch's rules).
+__device__ __forceinline__ void wgs_fetch(f32x4 (&v)[8], const float* __restrict__ src, int64_t ld, int64_t row0, int64_t end,
+                                          int col0, int cols_ld, int tid) {
+  const int c = 4 * (tid >> 3);
+#pragma unroll
+  for (int q = 0; q < 8; ++q) {
+    const int64_t row = row0 + 8 * (tid & 7) + q;
+    f32x4 r = {0.f, 0.f, 0.f, 0.f};
+    if (row < end && c < cols_ld) r = *reinterpret_cast<const f32x4*>(src + row * ld + col0 + c);
+    v[q] = r;
+  }
+}
+
+// ... split, and to the image: a column's 8 rows are one 16-byte store of hi and one of lo; columns from `cols` on (the pad
+// of enc) are zeros
+__device__ __forceinline__ void wgs_stage(__bf16* img, const f32x4 (&v)[8], int cols, int tid) {
+  const int c = 4 * (tid >> 3);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    bf16x8 hi, lo;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const __bf16 h = (__bf16)v[q][e];
+      hi[q] = h;
+      lo[q] = (__bf16)(v[q][e] - (float)h);
+    }
+    if (cols < WG_T && c + e >= cols)
+      for (int q = 0; q < 8; ++q) hi[q] = lo[q] = (__bf16)0.f;
+    __bf16* dst = img + (c + e) * WGS_STRIDE + 8 * (tid & 7);
+    *reinterpret_cast<bf16x8*>(dst) = hi;
+    *reinterpret_cast<bf16x8*>(dst + WGS_LO) = lo;
+  }
+}
+
+__device__ __forceinline__ void wgs_tile_job(const WgArgs& p, uint32_t job, int64_t r0, int64_t r1, float* __restrict__ ws,
+                                             __bf16* As, __bf16* Bs) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int l = (job >> 4) & 15, it = (job >> 8) & 15, jt = (job >> 12) & 15;
+  const uint32_t flags = job >> 16;
+  const bool gemm = flags & WG_F_GEMM, bias = flags & WG_F_BIAS, from_enc = flags & WG_F_ENC;
+
+  const float* a_src = p.g_pre + (int64_t)l * p.pre_rows * WG_W;
+  const int64_t a_r1 = r1 - p.pre_row0;  // the slab's end as g_pre counts the rows
+  const float* b_src = from_enc ? p.enc : p.acts + (int64_t)(l > 0 ? l - 1 : 0) * p.N * WG_W;
+  const int64_t b_ld = from_enc ? p.enc_w : WG_W;
+  const int b_col0 = from_enc ? 0 : jt * WG_T;
+  const int b_cols = from_enc ? p.in_ch : WG_T, b_cols_ld = from_enc ? p.enc_w : WG_T;  // columns kept / in memory
+
+  f32x16 acc[2][2];
+  for (int a = 0; a < 2; ++a)
+    for (int b = 0; b < 2; ++b)
+      for (int e = 0; e < 16; ++e) acc[a][b][e] = 0.f;
+  float bsum[4] = {0.f, 0.f, 0.f, 0.f};
+
+  const int li = lane & 31, lh = lane >> 5;
+  const __bf16* a_rd = As + ((wave >> 1) * 64 + li) * WGS_STRIDE + 8 * lh;
+  const __bf16* b_rd = Bs + ((wave & 1) * 64 + li) * WGS_STRIDE + 8 * lh;
+
+  f32x4 va[8], vb[8];
+  wgs_fetch(va, a_src, WG_W, r0 - p.pre_row0, a_r1, it * WG_T, WG_T, tid);
+  if (gemm) wgs_fetch(vb, b_src, b_ld, r0, r1, b_col0, b_cols_ld, tid);
+  for (int64_t row = r0; row < r1; row += WGS_K) {
+    if (bias) {
+      // this thread's 8 rows of its four columns of P, in row order, before anything is rounded
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float s = va[0][e];
+#pragma unroll
+        for (int q = 1; q < 8; ++q) s += va[q][e];
+        bsum[e] += s;
+      }
+    }
+    if (gemm) {
+      wgs_stage(As, va, WG_T, tid);
+      wgs_stage(Bs, vb, b_cols, tid);
+      __syncthreads();
+    }
+    if (row + WGS_K < r1) {
+      wgs_fetch(va, a_src, WG_W, row + WGS_K - p.pre_row0, a_r1, it * WG_T, WG_T, tid);
+      if (gemm) wgs_fetch(vb, b_src, b_ld, row + WGS_K, r1, b_col0, b_cols_ld, tid);
+    }
+    if (gemm) {
+      // the fragments of step s + 1 are read before the twelve MFMAs of step s
+      bf16x8 ah[2], al[2], bh[2], bl[2];
+#pragma unroll
+      for (int x = 0; x < 2; ++x) {
+        ah[x] = *reinterpret_cast<const bf16x8*>(a_rd + 32 * x * WGS_STRIDE);
+        al[x] = *reinterpret_cast<const bf16x8*>(a_rd + 32 * x * WGS_STRIDE + WGS_LO);
+        bh[x] = *reinterpret_cast<const bf16x8*>(b_rd + 32 * x * WGS_STRIDE);
+        bl[x] = *reinterpret_cast<const bf16x8*>(b_rd + 32 * x * WGS_STRIDE + WGS_LO);
+      }
+#pragma unroll
+      for (int s = 0; s < WGS_K / 16; ++s) {
+        bf16x8 nah[2], nal[2], nbh[2], nbl[2];
+        if (s + 1 < WGS_K / 16) {
+#pragma unroll
+          for (int x = 0; x < 2; ++x) {
+            nah[x] = *reinterpret_cast<const bf16x8*>(a_rd + 16 * (s + 1) + 32 * x * WGS_STRIDE);
+            nal[x] = *reinterpret_cast<const bf16x8*>(a_rd + 16 * (s + 1) + 32 * x * WGS_STRIDE + WGS_LO);
+            nbh[x] = *reinterpret_cast<const bf16x8*>(b_rd + 16 * (s + 1) + 32 * x * WGS_STRIDE);
+            nbl[x] = *reinterpret_cast<const bf16x8*>(b_rd + 16 * (s + 1) + 32 * x * WGS_STRIDE + WGS_LO);
+          }
+        }
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+          for (int b = 0; b < 2; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[a], bh[b], acc[a][b], 0, 0, 0);
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+          for (int b = 0; b < 2; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[a], bl[b], acc[a][b], 0, 0, 0);
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+          for (int b = 0; b < 2; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[a], bh[b], acc[a][b], 0, 0, 0);
+        if (s + 1 < WGS_K / 16) {
+#pragma unroll
+          for (int x = 0; x < 2; ++x) ah[x] = nah[x], al[x] = nal[x], bh[x] = nbh[x], bl[x] = nbl[x];
+        }
+      }
+      __syncthreads();
+    }
+  }
+
+  if (gemm) {
+    // C/D map of the 32x32 MFMA: column = lane & 31, row = (e & 3) + 8 (e >> 2) + 4 (lane >> 5)
+    float* out = from_enc ? ws + WG_OFF_IN + (size_t)(l == 0 ? 0 : 1) * WG_W * WG_T : ws + (size_t)(l - 1) * WG_W * WG_W;
+    const int ld = from_enc ? WG_T : WG_W;
+    for (int a = 0; a < 2; ++a)
+      for (int b = 0; b < 2; ++b)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+          const int i = it * WG_T + (wave >> 1) * 64 + 32 * a + (e & 3) + 8 * (e >> 2) + 4 * lh;
+          const int j = b_col0 + (wave & 1) * 64 + 32 * b + li;
+          out[(size_t)i * ld + j] = acc[a][b][e];
+        }
+  }
+  if (bias) {
+    // the 8 row groups of a column meet through LDS (free after the loop's last barrier) and are added in group order
+    float* red = reinterpret_cast<float*>(As);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) red[(tid & 7) * WG_T + 4 * (tid >> 3) + e] = bsum[e];
+    __syncthreads();
+    if (tid < WG_T) {
+      float s = red[tid];
+#pragma unroll
+      for (int r = 1; r < 8; ++r) s += red[r * WG_T + tid];
+      ws[WG_OFF_BIAS + (size_t)l * WG_W + it * WG_T + tid] = s;
+    }
+  }
+}
+
+// mlp_wgrad_kernel's deal of the (slab, job) list; two workgroups a CU, so that one's split hides under the other's MFMAs
+__global__ void __launch_bounds__(WG_BLOCK, 2) mlp_wgrad_split_kernel(WgArgs p) {
+  __shared__ __attribute__((aligned(16))) __bf16 As[WG_T * WGS_STRIDE];
+  __shared__ __attribute__((aligned(16))) __bf16 Bs[WG_T * WGS_STRIDE];
+  const int64_t total = p.n_slabs * p.n_jobs, run = (total + 7) / 8;
+  const int64_t id = (int64_t)(blockIdx.x & 7) * run + (blockIdx.x >> 3);
+  if (id >= total) return;
+  const int64_t slab = p.slab0 + id / p.n_jobs;
+  const uint32_t job = p.jobs[id % p.n_jobs];
+  const int64_t r0 = slab * p.slab_rows;
+  const int64_t r1 = r0 + p.slab_rows < p.N ? r0 + p.slab_rows : p.N;
+  float* ws = p.ws + (size_t)slab * WG_SLAB_FLOATS;
+  if ((job & 15) == WG_JOB_HEAD)
+    wg_head_job(p, job, r0, r1, ws, reinterpret_cast<float*>(As));
+  else
+    wgs_tile_job(p, job, r0, r1, ws, As, Bs);
+}
+
 }  // namespace
 
 extern "C" size_t fg_mlp_param_grads_workspace_bytes(int64_t N) {
@@ -368,10 +565,11 @@ int wg_plan(const fg_mlp_desc* d, const fg_mlp_grads* out, WgArgs& p, WgOut& o, 
   return FG_OK;
 }
 
-// the jobs of p over the slabs [slab0, slab0 + n_slabs), g_pre as p describes it
-int wg_launch_slabs(WgArgs p, int64_t slab0, int64_t n_slabs, fg_stream_t stream) {
+// the jobs of p over the slabs [slab0, slab0 + n_slabs), g_pre as p describes it; `split`: the tile jobs as split-bf16 products
+int wg_launch_slabs(WgArgs p, int64_t slab0, int64_t n_slabs, bool split, fg_stream_t stream) {
   p.slab0 = slab0, p.n_slabs = n_slabs;
-  hipLaunchKernelGGL(mlp_wgrad_kernel, dim3((unsigned)((n_slabs * p.n_jobs + 7) / 8 * 8)), dim3(WG_BLOCK), 0, fg_hip_stream(stream), p);
+  hipLaunchKernelGGL(split ? mlp_wgrad_split_kernel : mlp_wgrad_kernel, dim3((unsigned)((n_slabs * p.n_jobs + 7) / 8 * 8)), dim3(WG_BLOCK), 0,
+                     fg_hip_stream(stream), p);
   FG_RETURN_IF_LAUNCH_FAILED();
   return FG_OK;
 }
@@ -384,11 +582,16 @@ int wg_launch_reduce(const float* ws, int64_t n_slabs, const WgOut& o, fg_stream
   return FG_OK;
 }
 
+inline bool wg_precision_ok(int32_t precision) { return precision == FG_MLP_FP32 || precision == FG_MLP_BF16X3; }
+
 }  // namespace
 
-extern "C" int fg_mlp_param_grads(int64_t N, const fg_mlp_desc* d, const float* enc, const float* acts, const float* g_pre,
-                                  const float* g_heads, const fg_mlp_grads* out, void* workspace, size_t workspace_bytes,
-                                  fg_stream_t stream) {
+extern "C" int fg_mlp_wgrad_precision_supported(int32_t precision) { return wg_precision_ok(precision); }
+
+extern "C" int fg_mlp_param_grads_p(int64_t N, const fg_mlp_desc* d, const float* enc, const float* acts, const float* g_pre,
+                                    const float* g_heads, const fg_mlp_grads* out, int32_t wgrad_precision, void* workspace,
+                                    size_t workspace_bytes, fg_stream_t stream) {
+  if (!wg_precision_ok(wgrad_precision)) return FG_ERR_INVALID_ARG;
   if (N < 0) return FG_ERR_INVALID_ARG;
   if (N == 0) return FG_OK;
   WgArgs p = {};
@@ -410,8 +613,14 @@ extern "C" int fg_mlp_param_grads(int64_t N, const fg_mlp_desc* d, const float* 
 
   p.enc = enc, p.acts = acts, p.g_pre = g_pre, p.g_heads = g_heads, p.ws = static_cast<float*>(workspace);
   p.N = N, p.slab_rows = slab_rows, p.pre_rows = N, p.pre_row0 = 0;
-  if (int rc = wg_launch_slabs(p, 0, n_slabs, stream)) return rc;
+  if (int rc = wg_launch_slabs(p, 0, n_slabs, wgrad_precision == FG_MLP_BF16X3, stream)) return rc;
   return wg_launch_reduce(p.ws, n_slabs, o, stream);
+}
+
+extern "C" int fg_mlp_param_grads(int64_t N, const fg_mlp_desc* d, const float* enc, const float* acts, const float* g_pre,
+                                  const float* g_heads, const fg_mlp_grads* out, void* workspace, size_t workspace_bytes,
+                                  fg_stream_t stream) {
+  return fg_mlp_param_grads_p(N, d, enc, acts, g_pre, g_heads, out, FG_MLP_FP32, workspace, workspace_bytes, stream);
 }
 
 // ---- fg_mlp_train_bwd: the chain (mlp.hip) and the slab jobs above, one chunk of slabs at a time, so that g_pre is a
@@ -448,9 +657,10 @@ extern "C" size_t fg_mlp_train_bwd_workspace_bytes(int64_t N, int32_t chunk_slab
          fg_mlp_param_grads_workspace_bytes(N);
 }
 
-extern "C" int fg_mlp_train_bwd(int64_t N, const fg_mlp_desc* d, const float* g_heads, const float* enc, const float* acts,
-                                float* g_enc, const fg_mlp_grads* out, int32_t chunk_slabs, void* workspace, size_t workspace_bytes,
-                                fg_stream_t stream) {
+extern "C" int fg_mlp_train_bwd_p(int64_t N, const fg_mlp_desc* d, const float* g_heads, const float* enc, const float* acts,
+                                  float* g_enc, const fg_mlp_grads* out, int32_t chunk_slabs, int32_t wgrad_precision,
+                                  void* workspace, size_t workspace_bytes, fg_stream_t stream) {
+  if (!wg_precision_ok(wgrad_precision)) return FG_ERR_INVALID_ARG;
   if (N < 0) return FG_ERR_INVALID_ARG;
   if (N == 0) return FG_OK;
   if (chunk_slabs < 0) return FG_ERR_INVALID_ARG;
@@ -483,7 +693,13 @@ extern "C" int fg_mlp_train_bwd(int64_t N, const fg_mlp_desc* d, const float* g_
     if (int rc = fg_mlp_detail::bwd_launch_rows(N, d, r0, r1, g_heads, acts, g_pre, chunk_rows, g_enc, workspace, stream)) return rc;
     p.pre_row0 = r0;
     if (p.n_jobs > 0)
-      if (int rc = wg_launch_slabs(p, s0, s1 - s0, stream)) return rc;
+      if (int rc = wg_launch_slabs(p, s0, s1 - s0, wgrad_precision == FG_MLP_BF16X3, stream)) return rc;
   }
   return p.n_jobs > 0 ? wg_launch_reduce(p.ws, n_slabs, o, stream) : FG_OK;
+}
+
+extern "C" int fg_mlp_train_bwd(int64_t N, const fg_mlp_desc* d, const float* g_heads, const float* enc, const float* acts,
+                                float* g_enc, const fg_mlp_grads* out, int32_t chunk_slabs, void* workspace, size_t workspace_bytes,
+                                fg_stream_t stream) {
+  return fg_mlp_train_bwd_p(N, d, g_heads, enc, acts, g_enc, out, chunk_slabs, FG_MLP_FP32, workspace, workspace_bytes, stream);
 }

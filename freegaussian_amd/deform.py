@@ -8,7 +8,9 @@ forward with saved activations, the fused backward data chain, and the weight gr
 ``FG_FUSED_MLP_WGRAD=1`` (opt-in) on top of either, the weight gradients are one fused call too (``ops.mlp_param_grads``); with
 ``FG_FUSED_MLP_CHUNKED=1`` (opt-in) on top of both, the backward is one call that works through the rows in chunks and keeps no
 ``[8,N,256]`` gradient array (``ops.mlp_train_backward``); with ``FG_FUSED_MLP_PRECISION=bf16x3`` (opt-in) whichever of these
-fused calls takes a call forms its trunk and data-chain products as split-bf16 products (``fused_precision``).  Behaviour and
+fused calls takes a call forms its trunk and data-chain products as split-bf16 products (``fused_precision``); with
+``FG_FUSED_MLP_WGRAD_PRECISION=bf16x3`` (opt-in) on top of ``FG_FUSED_MLP_WGRAD=1`` the fused weight-gradient products are
+split-bf16 products too (``fused_wgrad_precision``).  Behaviour and
 ``state_dict`` key names follow the reference's ``FreeGaussianDeformableModel`` / ``FreeGaussianControllableModel``
 (freegaussian/freegaussian_model.py:1054-1145) so stage-1 checkpoints load unchanged; outputs are
 checked against golden vectors produced by the reference classes (tests/golden/g_mlp.npz)."""
@@ -158,6 +160,18 @@ def _precision_keywords() -> dict:
     return {} if knob == "fp32" else {"precision": knob}
 
 
+def fused_wgrad_precision() -> str:
+    """The precision of the fused parameter-gradient products: ``FG_FUSED_MLP_WGRAD_PRECISION`` (opt-in; read here and
+    nowhere else, on the host, on every call) -- unset or "fp32": the exact-fp32 kernel; "bf16x3": the split-bf16 tile job
+    of ``fg_mlp_param_grads_p`` (include/fgraster.h; profiles/mlp_wgrad_split.md).  Anything else is a ``ValueError``: a
+    typo must not train silently in fp32.  It has effect only where ``FG_FUSED_MLP_WGRAD=1`` already asks for the fused
+    products, and does not depend on ``FG_FUSED_MLP_PRECISION``."""
+    knob = os.environ.get("FG_FUSED_MLP_WGRAD_PRECISION", "fp32")
+    if knob not in ("fp32", "bf16x3"):
+        raise ValueError(f"FG_FUSED_MLP_WGRAD_PRECISION wants fp32 or bf16x3, got {knob!r}")
+    return knob
+
+
 def fused_train_applies(module: nn.Module, x: torch.Tensor, other: torch.Tensor) -> bool:
     """Whether a taped ``module(x, other)`` runs as one ``ops.mlp_train`` call (``fused_train_mode``)."""
     return fused_train_mode(module, x, other) != ""
@@ -171,11 +185,17 @@ def _train_keywords(mode: str) -> dict:
     the smallest, within 1 % of ``FUSED_MIN_ROWS``, the fewest rows a fused training call sees).
     ``FG_FUSED_MLP_CHUNKED=1`` (opt-in; read here and nowhere else, on the host, on every call; unset = off) on top of that
     knob -- without it it does nothing -- = the backward is one ``fg_mlp_train_bwd`` call over row chunks: the same gradients
-    bit for bit, 8 KB per row less memory (profiles/mlp_chunked_bwd.md)."""
+    bit for bit, 8 KB per row less memory (profiles/mlp_chunked_bwd.md).
+    ``FG_FUSED_MLP_WGRAD_PRECISION=bf16x3`` (opt-in; ``fused_wgrad_precision``) on top of ``FG_FUSED_MLP_WGRAD=1`` -- without it
+    it does nothing -- = the fused parameter gradients' hidden and input products are split-bf16 products
+    (profiles/mlp_wgrad_split.md); independent of ``FG_FUSED_MLP_PRECISION``."""
     kw = {"input_grads": True} if mode == "2" else {}
     kw.update(_precision_keywords())  # (FG_FUSED_MLP_PRECISION: fused_precision above)
+    wgrad_precision = fused_wgrad_precision()  # (read, so validated, whether or not it has an effect)
     if os.environ.get("FG_FUSED_MLP_WGRAD", "0") == "1":
         kw["fused_param_grads"] = True
+        if wgrad_precision != "fp32":
+            kw["param_grads_precision"] = wgrad_precision
         if os.environ.get("FG_FUSED_MLP_CHUNKED", "0") == "1":
             kw["chunked_backward"] = True
     return kw

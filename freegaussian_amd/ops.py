@@ -1387,15 +1387,18 @@ def mlp_wgrad_slab_rows(N: int) -> int:
 
 
 def mlp_param_grads(enc: torch.Tensor, H: torch.Tensor, G: torch.Tensor, g_heads: torch.Tensor, aux_width: int, head_rows,
-                    want=None):
+                    want=None, precision: str = "fp32"):
     """The parameter gradients of the fused training path in one call (``fg_mlp_param_grads``): from ``enc``
     [N, padded 63 + aux_width] and ``H`` [8,N,256] as ``fg_mlp_train_fwd`` stores them, ``G`` [8,N,256] as ``fg_mlp_bwd``
     does and the head cotangents ``g_heads`` [N, sum(head_rows)] ->  ``(gW x 8, gb x 8, gW_head per head, gb_head per
     head)``, the tuple of ``deform.mlp_param_grads`` in ``nn.Linear``'s layouts.  ``want``: one boolean per gradient in the
     order of ``_MlpTrain``'s ``params`` (trunk weights, trunk biases, head weights, head biases); an unwanted one is not
     formed and comes back as ``None``.  Row slabs on the exact-fp32 matrix instructions, partial sums added in slab order:
-    no atomics, two calls on the same arrays are bit for bit equal.  CUDA float32 contiguous tensors; no host
-    synchronisation: capturable."""
+    no atomics, two calls on the same arrays are bit for bit equal.  ``precision``: "fp32" (the default: that call, as
+    ever) or "bf16x3" -- the hidden and input products as split-bf16 products (``fg_mlp_param_grads_p``, the contract in
+    include/fgraster.h: three bf16 products for one, slabs, order and workspace unchanged; biases fp32 sums, head gradients
+    the fp32 mode's bits).  CUDA float32 contiguous tensors; no host synchronisation: capturable."""
+    prec = _mlp_precision("mlp_param_grads", precision)
     tensors = (enc, H, G, g_heads)
     if any(not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() for t in tensors):
         raise ValueError("mlp_param_grads wants contiguous CUDA float32 tensors")
@@ -1431,8 +1434,12 @@ def mlp_param_grads(enc: torch.Tensor, H: torch.Tensor, G: torch.Tensor, g_heads
             g.head_weight[i], g.head_bias[i] = _ptr(outs[16 + i]), _ptr(outs[16 + n + i])
         with torch.cuda.device(dev):
             ws = torch.empty(int(_lib.load().fg_mlp_param_grads_workspace_bytes(N)), dtype=torch.uint8, device=dev)
-            _call("fg_mlp_param_grads", N, ctypes.addressof(d), _ptr(enc), _ptr(H), _ptr(G), _ptr(g_heads), ctypes.addressof(g),
-                  _ptr(ws), ws.numel(), _stream())  # fmt: skip
+            if prec == _lib.MLP_FP32:
+                _call("fg_mlp_param_grads", N, ctypes.addressof(d), _ptr(enc), _ptr(H), _ptr(G), _ptr(g_heads), ctypes.addressof(g),
+                      _ptr(ws), ws.numel(), _stream())  # fmt: skip
+            else:
+                _call("fg_mlp_param_grads_p", N, ctypes.addressof(d), _ptr(enc), _ptr(H), _ptr(G), _ptr(g_heads), ctypes.addressof(g),
+                      prec, _ptr(ws), ws.numel(), _stream())  # fmt: skip
     return tuple(outs[:8]), tuple(outs[8:16]), tuple(outs[16 : 16 + n]), tuple(outs[16 + n :])
 
 
@@ -1443,7 +1450,8 @@ def mlp_train_chunk_rows(N: int, chunk_slabs: int = 0) -> int:
 
 
 def mlp_train_backward(enc: torch.Tensor, H: torch.Tensor, g_heads: torch.Tensor, trunk, heads, aux_width: int, head_rows,
-                       want=None, want_g_enc: bool = False, chunk_slabs: int = 0, precision: str = "fp32"):
+                       want=None, want_g_enc: bool = False, chunk_slabs: int = 0, precision: str = "fp32",
+                       param_grads_precision: str = "fp32"):
     """The whole backward of the fused training path in one call that never holds ``G`` [8,N,256] (``fg_mlp_train_bwd``;
     DESIGN.md §6 A): from ``enc`` [N, padded 63 + aux_width] and ``H`` [8,N,256] as ``fg_mlp_train_fwd`` stores them, the
     head cotangents ``g_heads`` [N, sum(head_rows)] and the network's parameters (``trunk`` / ``heads`` as for
@@ -1454,9 +1462,12 @@ def mlp_train_backward(enc: torch.Tensor, H: torch.Tensor, g_heads: torch.Tensor
     ``mlp_param_grads`` gives, for every ``chunk_slabs``.  ``want`` as for ``mlp_param_grads``; ``want_g_enc``: also the
     gradient of the encoded input row [N, padded 63 + aux_width] (``mlp_input_grads`` takes it to ``x`` / ``aux``).
     ``precision``: as for ``mlp_forward`` -- "bf16x3" splits the data chain's products (and ``g_enc``'s); the parameter
-    gradients stay exact-fp32 products of the arrays the chain leaves.  CUDA
+    gradients stay exact-fp32 products of the arrays the chain leaves unless ``param_grads_precision`` is "bf16x3": then
+    the hidden and input products are the split-bf16 products of ``mlp_param_grads(precision="bf16x3")``, bit for bit
+    (``fg_mlp_train_bwd_p``; the two words are independent).  CUDA
     float32 contiguous tensors; no host synchronisation: capturable."""
     prec = _mlp_precision("mlp_train_backward", precision)
+    wprec = _mlp_precision("mlp_train_backward", param_grads_precision)
     tensors = (enc, H, g_heads)
     if any(not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() for t in tensors):
         raise ValueError("mlp_train_backward wants contiguous CUDA float32 tensors")
@@ -1496,8 +1507,12 @@ def mlp_train_backward(enc: torch.Tensor, H: torch.Tensor, g_heads: torch.Tensor
         with torch.cuda.device(dev):
             need = int(_lib.load().fg_mlp_train_bwd_workspace_bytes(N, chunk_slabs, int(bool(want_g_enc))))
             ws = torch.empty(need, dtype=torch.uint8, device=dev)
-            _call("fg_mlp_train_bwd", N, ctypes.addressof(d), _ptr(g_heads), _ptr(enc), _ptr(H), _ptr(g_enc), ctypes.addressof(g),
-                  chunk_slabs, _ptr(ws), ws.numel(), _stream())  # fmt: skip
+            if wprec == _lib.MLP_FP32:
+                _call("fg_mlp_train_bwd", N, ctypes.addressof(d), _ptr(g_heads), _ptr(enc), _ptr(H), _ptr(g_enc), ctypes.addressof(g),
+                      chunk_slabs, _ptr(ws), ws.numel(), _stream())  # fmt: skip
+            else:
+                _call("fg_mlp_train_bwd_p", N, ctypes.addressof(d), _ptr(g_heads), _ptr(enc), _ptr(H), _ptr(g_enc), ctypes.addressof(g),
+                      chunk_slabs, wprec, _ptr(ws), ws.numel(), _stream())  # fmt: skip
     return tuple(outs[:8]), tuple(outs[8:16]), tuple(outs[16 : 16 + n]), tuple(outs[16 + n :]), g_enc
 
 
@@ -1506,11 +1521,12 @@ class _MlpTrain(torch.autograd.Function):
     ``x``, ``aux``, the number of heads, whether ``x`` / ``aux`` may get a gradient (then ``fg_mlp_bwd_inputs`` where one
     of them wants it), whether the parameter gradients come from ``fg_mlp_param_grads``, the chunked backward (None = off;
     an int = the whole backward is one ``fg_mlp_train_bwd`` call with that ``chunk_slabs``, 0 being the library's constant),
-    the precision ("fp32" / "bf16x3": kept in the context, so every form of the backward runs in the forward's),
+    the precision ("fp32" / "bf16x3": kept in the context, so every form of the backward runs in the forward's), the
+    precision of the fused parameter-gradient products (kept in the context too; "bf16x3" only with the fused products),
     then the 8 trunk weights, the 8 trunk biases, the head weights, the head biases."""
 
     @staticmethod
-    def forward(ctx, x, aux, n_heads, input_grads, fused_param_grads, chunk_slabs, precision, *params):
+    def forward(ctx, x, aux, n_heads, input_grads, fused_param_grads, chunk_slabs, precision, param_grads_precision, *params):
         trunk, heads = list(zip(params[:8], params[8:16])), list(zip(params[16 : 16 + n_heads], params[16 + n_heads :]))
         d, N, rows, keep = _mlp_desc("mlp_train", x, aux, trunk, heads, _lib.MLP_PLAIN)
         d.precision = _mlp_precision("mlp_train", precision)
@@ -1526,6 +1542,7 @@ class _MlpTrain(torch.autograd.Function):
         ctx.input_grads, ctx.one_row_aux = bool(input_grads), d.aux_stride == 0
         ctx.fused_param_grads = bool(fused_param_grads)
         ctx.chunk_slabs, ctx.precision = chunk_slabs, precision
+        ctx.param_grads_precision = param_grads_precision
         return out
 
     @staticmethod
@@ -1542,12 +1559,15 @@ class _MlpTrain(torch.autograd.Function):
         N = g_heads.shape[0]
         want_x, want_aux = (ctx.input_grads and need for need in ctx.needs_input_grad[:2])
         g_x = g_aux = None
+        # (the default passes nothing new: the calls below are then, argument for argument, what they were)
+        wkw = {} if ctx.param_grads_precision == "fp32" else {"param_grads_precision": ctx.param_grads_precision}
         if ctx.chunk_slabs is not None:  # no G: the chain and the products chunk by chunk, in one call
-            gW, gb, gWh, gbh, g_enc = mlp_train_backward(enc, H, g_heads, trunk, heads, ctx.aux_width, rows, want=ctx.needs_input_grad[7:],
-                                                         want_g_enc=want_x or want_aux, chunk_slabs=ctx.chunk_slabs, precision=ctx.precision)  # fmt: skip
+            gW, gb, gWh, gbh, g_enc = mlp_train_backward(enc, H, g_heads, trunk, heads, ctx.aux_width, rows, want=ctx.needs_input_grad[8:],
+                                                         want_g_enc=want_x or want_aux, chunk_slabs=ctx.chunk_slabs, precision=ctx.precision,
+                                                         **wkw)  # fmt: skip
             if g_enc is not None:
                 g_x, g_aux = mlp_input_grads(g_enc, enc, ctx.aux_width, want_x, want_aux, ctx.one_row_aux)
-            return (g_x, g_aux, None, None, None, None, None, *gW, *gb, *gWh, *gbh)
+            return (g_x, g_aux, None, None, None, None, None, None, *gW, *gb, *gWh, *gbh)
         G = torch.empty_like(H)
         with torch.cuda.device(G.device):
             if want_x or want_aux:
@@ -1560,15 +1580,17 @@ class _MlpTrain(torch.autograd.Function):
                 ws = torch.empty(int(_lib.load().fg_mlp_train_workspace_bytes(N)), dtype=torch.uint8, device=G.device)
                 _call("fg_mlp_bwd", N, ctypes.addressof(d), _ptr(g_heads), _ptr(H), _ptr(G), _ptr(ws), ws.numel(), _stream())
         if ctx.fused_param_grads:
-            gW, gb, gWh, gbh = mlp_param_grads(enc, H, G, g_heads, ctx.aux_width, rows, want=ctx.needs_input_grad[7:])
-            return (g_x, g_aux, None, None, None, None, None, *gW, *gb, *gWh, *gbh)
+            gW, gb, gWh, gbh = mlp_param_grads(enc, H, G, g_heads, ctx.aux_width, rows, want=ctx.needs_input_grad[8:],
+                                               **({"precision": wkw["param_grads_precision"]} if wkw else {}))
+            return (g_x, g_aux, None, None, None, None, None, None, *gW, *gb, *gWh, *gbh)
         gW, gb, gWh, gbh = deform.mlp_param_grads(enc[:, : 63 + ctx.aux_width], H, G, g_heads, rows)
         grads = (*gW, *gb, *gWh, *gbh)
-        return (g_x, g_aux, None, None, None, None, None, *(g if need else None for g, need in zip(grads, ctx.needs_input_grad[7:])))
+        return (g_x, g_aux, None, None, None, None, None, None, *(g if need else None for g, need in zip(grads, ctx.needs_input_grad[8:])))
 
 
 def mlp_train(x: torch.Tensor, aux: torch.Tensor, trunk, heads, input_grads: bool = False,
-              fused_param_grads: bool = False, chunked_backward=False, precision: str = "fp32") -> torch.Tensor:
+              fused_param_grads: bool = False, chunked_backward=False, precision: str = "fp32",
+              param_grads_precision: str = "fp32") -> torch.Tensor:
     """The network of ``mlp_forward`` for training (``fg_mlp_train_fwd`` / ``fg_mlp_bwd``): the raw head outputs
     ``[N, rows_total]`` (the heads side by side in the order given, bit for bit ``mlp_forward(mode="plain")``), recorded
     for autograd.  The forward keeps the encoded input row and the eight post-ReLU activations (``[8,N,256]``); the
@@ -1585,9 +1607,15 @@ def mlp_train(x: torch.Tensor, aux: torch.Tensor, trunk, heads, input_grads: boo
     implies the fused parameter gradients: with ``fused_param_grads=False`` it is a ``ValueError``.
     ``precision``: as for ``mlp_forward``; "bf16x3" runs the forward's trunk and the backward's data chain (in every form
     above: two calls, with input gradients, chunked) on split-bf16 products.  What is stored stays fp32, and the parameter
-    gradients -- fused or not -- stay exact-fp32 products of it.  CUDA float32
+    gradients -- fused or not -- stay exact-fp32 products of it.
+    ``param_grads_precision``: "bf16x3" forms the hidden and input products of the FUSED parameter gradients (two calls or
+    chunked) as split-bf16 products (``mlp_param_grads(precision="bf16x3")``; biases and head gradients as before); it is
+    independent of ``precision``, changes neither the outputs nor the input gradients, and with
+    ``fused_param_grads=False`` it is a ``ValueError``: the library products cannot split.  CUDA float32
     tensors, N >= 1; ``aux`` as for ``mlp_forward``.  No host synchronisation: capturable."""
     _mlp_precision("mlp_train", precision)
+    if _mlp_precision("mlp_train", param_grads_precision) != _lib.MLP_FP32 and not fused_param_grads:
+        raise ValueError("mlp_train: param_grads_precision='bf16x3' splits the fused parameter gradients; pass fused_param_grads=True")
     chunk_slabs = None
     if chunked_backward is not False and chunked_backward is not None:
         if chunked_backward is True:
@@ -1610,7 +1638,8 @@ def mlp_train(x: torch.Tensor, aux: torch.Tensor, trunk, heads, input_grads: boo
     if input_grads and aux.requires_grad and aux.dim() == 2 and aux.shape[0] > 1 and aux.stride(0) == 0:
         aux = aux[:1]  # (one row for all: autograd's own expand carries the [1, A] sum back)
     params = [w for w, _ in trunk] + [b for _, b in trunk] + [w for w, _ in heads] + [b for _, b in heads]
-    return _MlpTrain.apply(x, aux, len(heads), bool(input_grads), bool(fused_param_grads), chunk_slabs, precision, *params)
+    return _MlpTrain.apply(x, aux, len(heads), bool(input_grads), bool(fused_param_grads), chunk_slabs, precision,
+                           param_grads_precision, *params)
 
 
 # --------------------------------------------------------------------------------------------

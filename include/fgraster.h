@@ -48,7 +48,8 @@ typedef void* fg_stream_t;
 #define FG_ABI_MINOR 1 /* symbols added since FG_ABI_VERSION was last raised: 1 = fg_abi_minor, fg_mlp_train_bwd* */
 /* (fg_mlp_precision_supported, added later still, is discovered BY NAME -- dlsym, or ctypes' hasattr -- not by the minor
  * number, which stays 1: a library without the symbol takes fg_mlp_desc::precision as the reserved word it was and
- * computes in fp32.) */
+ * computes in fp32.  Likewise BY NAME: fg_mlp_wgrad_precision_supported, fg_mlp_param_grads_p and fg_mlp_train_bwd_p -- a
+ * library without them forms the weight gradients in exact fp32 through fg_mlp_param_grads / fg_mlp_train_bwd.) */
 #define FG_COUNT_OUT_WORDS 16 /* int64 words of a count_out block (fg_stbin_count, fg_step_io): ABI 9 */
 
 int fg_abi_version(void);
@@ -840,7 +841,8 @@ int fg_knn(int64_t n, const float* xyz, int k, float* dist2_out, int32_t* idx_ou
  *     non-finite inputs give non-finite outputs (|v| beyond bf16's largest finite value, 3.39e38, splits to infinity).
  *     Workspace sizes, arguments and error codes are those of FG_MLP_FP32.
  * Honoured by fg_mlp_fwd, fg_mlp_train_fwd, fg_mlp_bwd, fg_mlp_bwd_inputs and fg_mlp_train_bwd (whose chunks run the same
- * chain kernel); IGNORED by fg_mlp_param_grads (always fp32).  Any other value: FG_ERR_INVALID_ARG from the five calls.
+ * chain kernel); IGNORED by fg_mlp_param_grads (always fp32; the weight-gradient products have a word of their own, the
+ * wgrad_precision of fg_mlp_param_grads_p / fg_mlp_train_bwd_p further down).  Any other value: FG_ERR_INVALID_ARG from the five calls.
  * fg_mlp_precision_supported(precision) = 1 where this library takes the value, else 0: ask before the call. */
 #define FG_MLP_FP32 0
 #define FG_MLP_BF16X3 1
@@ -1011,6 +1013,43 @@ int64_t fg_mlp_train_bwd_chunk_rows(int64_t N, int32_t chunk_slabs);
 size_t fg_mlp_train_bwd_workspace_bytes(int64_t N, int32_t chunk_slabs, int32_t want_g_enc);
 int fg_mlp_train_bwd(int64_t N, const fg_mlp_desc* desc, const float* g_heads, const float* enc, const float* acts, float* g_enc,
                      const fg_mlp_grads* out, int32_t chunk_slabs, void* workspace, size_t workspace_bytes, fg_stream_t stream);
+
+/* ---- K10 weight-gradient products in split bf16 (found BY NAME, see FG_ABI_MINOR): fg_mlp_param_grads and fg_mlp_train_bwd with
+ * one more word, wgrad_precision, which governs the hidden and input products gW_l = P_l^T in_l and nothing else.
+ * fg_mlp_desc::precision keeps its meaning: it governs the chain of fg_mlp_train_bwd_p and is ignored by fg_mlp_param_grads_p.
+ * The two words are independent: all four combinations are legal.
+ *   FG_MLP_FP32    fg_mlp_param_grads / fg_mlp_train_bwd themselves: the old functions ARE the new ones with this value, bit for
+ *                  bit and launch for launch.
+ *   FG_MLP_BF16X3  opt-in.  Same slabs (fg_mlp_param_grads_slab_rows(N)), same jobs, same partial blocks, same reduction in slab
+ *                  order, same workspace; the 128 x 128 tile jobs run on v_mfma_f32_32x32x16_bf16.  The contract:
+ *     split(v):  as for fg_mlp_desc::precision: hi = bf16(v) rounded to nearest even, lo = bf16(v - float(hi)).  Both operands,
+ *                P_l and in_l, are split as they are read, once per value and tile job.
+ *     chain   :  an output element (i, j) of one slab starts from 0 and walks the slab's rows in steps of 16, ascending.  Per
+ *                step s it takes P_hi.in_hi, then P_hi.in_lo, then P_lo.in_hi, each the instruction's own sum over the rows
+ *                k = 16 s + 8 h + j (lane half h, j = 0..7) of P[k][i] in[k][j], accumulated in fp32; P_lo.in_lo is dropped.
+ *                Rows from the slab's end on are zeros and are never read; the pad columns k >= in_ch of enc are zeros.  At most
+ *                4096 rows = 256 steps to a chain; the slabs' partials are added in slab order by the unchanged reduction.
+ *     biases  :  gb_l stays an fp32 sum of the unsplit P_l, taken from the fetched values before the split.  Order, per slab
+ *                and column: the rows go in blocks of 64; row group r = 0..7 of a block is its rows 8 r .. 8 r + 7; a group's 8
+ *                values are added in row order and that sum to the running sum of its r; after the last block the 8 running
+ *                sums are added in the order r = 0..7.  (Not the fp32 mode's order: the sums may differ in the last bits.)
+ *     heads   :  head weight and bias gradients are the fp32 mode's, bit for bit: the same jobs, the same code
+ *                (v_mfma_f32_16x16x4_f32; 1/112 of the FLOP).
+ *     No atomics: two runs are bit for bit equal; zero cotangents give exact zeros.  Against float64 the trunk weight gradients
+ *     stay within 1e-4 of each array's largest magnitude (emulated and measured: about 5e-6 .. 2e-5; with the third term left
+ *     out some 2e-3).  A single 1.0 in P_l at (r, i) makes row i of gW_l exactly hi(in_l[r]) + lo(in_l[r]).
+ * Any other wgrad_precision: FG_ERR_INVALID_ARG, before anything else about the call is looked at (N == 0 with a good value
+ * stays FG_OK).  Workspace queries, sizes, alignment rules and every other error code are those of the old calls.
+ * fg_mlp_train_bwd_p stays bit for bit the chain call followed by fg_mlp_param_grads_p, for every chunk_slabs and both values
+ * of either word.  fg_mlp_wgrad_precision_supported(precision) = 1 for FG_MLP_FP32 and FG_MLP_BF16X3, else 0.
+ * Measured (profiles/mlp_wgrad_split.md). */
+int fg_mlp_wgrad_precision_supported(int32_t precision);
+int fg_mlp_param_grads_p(int64_t N, const fg_mlp_desc* desc, const float* enc, const float* acts, const float* g_pre,
+                         const float* g_heads, const fg_mlp_grads* out, int32_t wgrad_precision, void* workspace,
+                         size_t workspace_bytes, fg_stream_t stream);
+int fg_mlp_train_bwd_p(int64_t N, const fg_mlp_desc* desc, const float* g_heads, const float* enc, const float* acts, float* g_enc,
+                       const fg_mlp_grads* out, int32_t chunk_slabs, int32_t wgrad_precision, void* workspace,
+                       size_t workspace_bytes, fg_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -73,6 +73,20 @@ profiles/mlp_split_bf16.md from these and from what ``scripts/mlp_forward_bench.
                    all rows and over the rows clear of the ReLU's kink by 1e-4
     --step ptrace  three training calls of either precision at N = 240 000 for ``rocprofv3`` (with --trace)
     --step preport profiles/mlp_split_bf16.md
+
+With ``--wgrad-precision`` it compares the opt-in split-bf16 mode of the fused parameter-gradient products
+(``FG_FUSED_MLP_WGRAD_PRECISION=bf16x3`` on top of ``FG_FUSED_MLP_WGRAD=1``; ``fg_mlp_param_grads_p``) with the fp32 entry
+point OF THE SAME BUILD, the sides alternating call by call, and writes profiles/mlp_wgrad_split.md:
+
+    --step scall     ``ops.mlp_param_grads`` alone, precision "bf16x3" against "fp32", at the three sizes, aux widths 21 and 30
+    --step serror    both at N = 33 000 against ``deform.mlp_param_grads`` of the same arrays in float64 on the CPU
+    --step strain    the whole fused training call for both chain precisions x both values of the new knob, the four
+                     alternating call by call (with --blender: the blender net)
+    --step smodel    one model training step at 240 000 Gaussians, 960 x 540, the same four settings
+    --step strace    three training calls of each setting at N = 240 000 for ``rocprofv3 --kernel-trace --stats`` (with --trace)
+    --step scounters three calls of the split products alone for ``rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE``
+                     (with --trace; a run of its own, no tracing beside the counters)
+    --step sreport   profiles/mlp_wgrad_split.md (its hand-written ``## Notes`` section is kept)
 """
 import argparse
 import copy
@@ -1207,11 +1221,235 @@ def pstep_report(out, md):
     print("\n".join(L))
 
 
+# ---- --wgrad-precision: the split-bf16 mode of the fused parameter-gradient products ---------------------------------------
+WGRAD_PRECISION_KNOB = "FG_FUSED_MLP_WGRAD_PRECISION"
+
+
+def _wgrad_precision_knob(value):
+    if value == "fp32":
+        os.environ.pop(WGRAD_PRECISION_KNOB, None)
+    else:
+        os.environ[WGRAD_PRECISION_KNOB] = value
+
+
+def sstep_call(out):
+    """``ops.mlp_param_grads`` alone, precision="bf16x3" against "fp32" of the same build, alternating call by call."""
+    from freegaussian_amd import ops
+
+    res = {}
+    for A in (21, 30):
+        for n in SIZES:
+            enc, H, G, gh = _wgrad_arrays(n, A)
+            s_, f = _timed_pair(lambda: ops.mlp_param_grads(enc, H, G, gh, A, WGRAD_ROWS, precision="bf16x3"),
+                                lambda: ops.mlp_param_grads(enc, H, G, gh, A, WGRAD_ROWS))  # fmt: skip
+            qs, qf = _quantiles(s_), _quantiles(f)
+            fl = (WGRAD_FLOP_PER_ROW + 4 * 256 * (63 + A)) * n
+            res[f"{A},{n}"] = {"aux_width": A, "n": n, "split_ms": qs, "fp32_ms": qf, "ratio": qs["median"] / qf["median"],
+                               "split_tflops": fl / qs["median"] / 1e9, "fp32_tflops": fl / qf["median"] / 1e9,
+                               "operand_gb_per_s": 16384.0 * n / qs["median"] / 1e6}  # fmt: skip
+            print(res[f"{A},{n}"], flush=True)
+            del enc, H, G, gh
+            torch.cuda.empty_cache()
+    json.dump(res, open(os.path.join(out, "scall.json"), "w"), indent=1)
+
+
+def sstep_error(out):
+    from freegaussian_amd import deform, ops
+
+    n, res = 33_000, {}
+
+    def rel(a, b):
+        return float((a.double().cpu() - b).abs().max() / b.abs().max())
+
+    for A in (21, 30):
+        enc, H, G, gh = _wgrad_arrays(n, A)
+        want = deform.mlp_param_grads(enc[:, : 63 + A].double().cpu(), H.double().cpu(), G.double().cpu(), gh.double().cpu(), WGRAD_ROWS)
+        for name in ("bf16x3", "fp32"):
+            got = ops.mlp_param_grads(enc, H, G, gh, A, WGRAD_ROWS, precision=name)
+            for kind, gs, ws in zip(("trunk weights", "trunk biases", "head weights", "head biases"), got, want):
+                res.setdefault(f"{kind}, aux width {A}", {})[name] = max(rel(g, w) for g, w in zip(gs, ws))
+    print(res, flush=True)
+    json.dump(res, open(os.path.join(out, "serror.json"), "w"), indent=1)
+
+
+_COMBOS = [(chain, wgrad) for chain in ("fp32", "bf16x3") for wgrad in ("fp32", "bf16x3")]
+
+
+def _timed_combos(run, warm=WARM, timed=TIMED):
+    """The four (chain precision, weight-gradient precision) settings alternating call by call: name -> ms list."""
+    ms = {c: [] for c in _COMBOS}
+    for i in range(warm + timed):
+        for c in _COMBOS:
+            _precision_knob(c[0])
+            _wgrad_precision_knob(c[1])
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            run()
+            b.record()
+            b.synchronize()
+            if i >= warm:
+                ms[c].append(a.elapsed_time(b))
+    return {f"{c[0]},{c[1]}": _quantiles(v) for c, v in ms.items()}
+
+
+def _count_wgrad_precisions():
+    from freegaussian_amd import ops
+
+    seen = []
+    real = ops.mlp_train
+    ops.mlp_train = lambda *a, **k: seen.append((k.get("precision", "fp32"), k.get("param_grads_precision", "fp32"))) or real(*a, **k)
+    return seen
+
+
+def sstep_train(out):
+    m = _module().cuda()
+    _knob(True)
+    _wgrad_knob(True)
+    seen, res = _count_wgrad_precisions(), {}
+    for n in SIZES:
+        g = torch.Generator().manual_seed(n)
+        x = (torch.rand(n, 3, generator=g) * 2 - 1).cuda()
+        t = torch.full((1, 1), 0.4, device="cuda").expand(n, -1)
+        cots = [torch.randn(n, *s, generator=g).cuda() for s in ((4, 4), (4,), (3,))]
+        before = len(seen)
+        res[str(n)] = _timed_combos(lambda: _train_call(m, x, t, cots))
+        assert seen[before:] == _COMBOS * (WARM + TIMED)  # every side took the fused call, each in its own setting
+        print(n, res[str(n)], flush=True)
+    json.dump(res, open(os.path.join(out, "strain_blender.json" if BLENDER else "strain.json"), "w"), indent=1)
+
+
+def sstep_model(out):
+    from freegaussian_amd.model import Camera, FreeGaussianModel, FreeGaussianModelConfig
+    from freegaussian_amd.scenes import look_at_viewmat
+
+    torch.manual_seed(0)
+    n, W, H = 240_000, 960, 540
+    cfg = FreeGaussianModelConfig(background_color="white", num_downscales=0, warm_up=3000)
+    model = FreeGaussianModel(cfg, seed_points=(torch.rand(n, 3) - 0.5) * 2.0, init_scales=-4.5, is_blender=BLENDER)
+    with torch.no_grad():
+        for q in model.deform.parameters():
+            q.mul_(0.3)
+    model.step = 4000
+    model = model.cuda().train()
+    c2w = torch.linalg.inv(look_at_viewmat(torch.tensor([0.3, -0.2, -3.0]), torch.zeros(3)))
+    c2w[:3, 1:3] *= -1
+    cam = Camera(c2w[None, :3], 750.0, 750.0, W / 2, H / 2, W, H, times=torch.tensor([[0.4]]))
+    gt = torch.rand(H, W, 3, device="cuda")
+    _knob(True)
+    _wgrad_knob(True)
+    seen = _count_wgrad_precisions()
+
+    def step():
+        model.zero_grad(set_to_none=True)
+        model.get_loss_dict(model.get_outputs(cam), {"image": gt})["main_loss"].backward()
+
+    warm, timed = 5, 30
+    res = {"n": n, "width": W, "height": H, "ms": _timed_combos(step, warm=warm, timed=timed)}
+    assert seen == _COMBOS * (warm + timed)
+    print(res, flush=True)
+    json.dump(res, open(os.path.join(out, "smodel_blender.json" if BLENDER else "smodel.json"), "w"), indent=1)
+
+
+def sstep_trace(out):
+    """Three training calls of each of the four settings at N = 240 000, then three calls alone: for ``rocprofv3``."""
+    from freegaussian_amd import ops
+
+    m = _module().cuda()
+    n = 240_000
+    x = (torch.rand(n, 3) * 2 - 1).cuda()
+    t = torch.full((1, 1), 0.4, device="cuda").expand(n, -1)
+    cots = [torch.randn(n, *s).cuda() for s in ((4, 4), (4,), (3,))]
+    _knob(True)
+    _wgrad_knob(True)
+    for chain, wgrad in _COMBOS:
+        _precision_knob(chain)
+        _wgrad_precision_knob(wgrad)
+        for _ in range(3):
+            _train_call(m, x, t, cots)
+    torch.cuda.synchronize()
+
+
+def sstep_counters(out):
+    """Three calls of the split products alone at N = 240 000: for a ``rocprofv3 --pmc`` run of its own."""
+    from freegaussian_amd import ops
+
+    enc, H, G, gh = _wgrad_arrays(240_000, 21)
+    for _ in range(3):
+        ops.mlp_param_grads(enc, H, G, gh, 21, WGRAD_ROWS, precision="bf16x3")
+    torch.cuda.synchronize()
+
+
+def sstep_report(out, md):
+    def load(name):
+        path = os.path.join(out, name)
+        return json.load(open(path)) if os.path.exists(path) else None
+
+    L = ["# Split-bf16 (3-product) mode of the fused parameter-gradient products against their fp32 mode", "",
+         "Written by `scripts/mlp_train_bench.py --wgrad-precision` on an MI355X.  The baseline is the fp32 entry point of the same",
+         "build; the sides alternate call by call in one process per table, "
+         f"{WARM} warm-up and {TIMED} timed calls each between device events (5 and 30 for the model step); median (p10 .. p90).",
+         "Outcome rule: a gain = the split median below the fp32 median with p10 .. p90 ranges that do not overlap, at 240 000 rows."]  # fmt: skip
+    verdicts = {}
+    sc = load("scall.json")
+    if sc:
+        L += ["", "## (a) `fg_mlp_param_grads_p` alone (`ops.mlp_param_grads(precision=...)`, the tests' random arrays)", "",
+              "| aux width | N | bf16x3 ms | fp32 ms | bf16x3 / fp32 | bf16x3 TFLOP/s | fp32 TFLOP/s | operand bytes / bf16x3 time, GB/s | by the rule |",
+              "|---|---|---|---|---|---|---|---|---|"]  # fmt: skip
+        for r in sc.values():
+            L.append(f"| {r['aux_width']} | {r['n']:,} | {_ms(r['split_ms'])} | {_ms(r['fp32_ms'])} | {r['ratio']:.2f} | {r['split_tflops']:.1f} | "
+                     f"{r['fp32_tflops']:.1f} | {r['operand_gb_per_s']:.0f} | {_gain(r['split_ms'], r['fp32_ms'])} |")  # fmt: skip
+        verdicts["(a) the call alone, aux width 21"] = _gain(sc["21,240000"]["split_ms"], sc["21,240000"]["fp32_ms"])
+    for name, title in (("strain.json", "deformation net, `FG_FUSED_MLP_TRAIN=1`"), ("strain_blender.json", "blender net, `FG_FUSED_MLP_TRAIN=2`")):
+        tr = load(name)
+        if tr:
+            L += ["", f"## (b) The whole `ops.mlp_train` forward + backward, `FG_FUSED_MLP_WGRAD=1`: {title}", "",
+                  "Columns: `FG_FUSED_MLP_PRECISION`, `FG_FUSED_MLP_WGRAD_PRECISION`.", "",
+                  "| N | fp32, fp32 ms | fp32, bf16x3 ms | ratio | bf16x3, fp32 ms | bf16x3, bf16x3 ms | ratio | by the rule (chain fp32 / bf16x3) |",
+                  "|---|---|---|---|---|---|---|---|"]  # fmt: skip
+            for n in (str(v) for v in SIZES):
+                if n in tr:
+                    r = tr[n]
+                    L.append(f"| {int(n):,} | {_ms(r['fp32,fp32'])} | {_ms(r['fp32,bf16x3'])} | {r['fp32,bf16x3']['median'] / r['fp32,fp32']['median']:.2f} | "
+                             f"{_ms(r['bf16x3,fp32'])} | {_ms(r['bf16x3,bf16x3'])} | {r['bf16x3,bf16x3']['median'] / r['bf16x3,fp32']['median']:.2f} | "
+                             f"{_gain(r['fp32,bf16x3'], r['fp32,fp32'])} / {_gain(r['bf16x3,bf16x3'], r['bf16x3,fp32'])} |")  # fmt: skip
+            r = tr["240000"]
+            verdicts[f"(b) {title.split(',')[0]}, chain fp32"] = _gain(r["fp32,bf16x3"], r["fp32,fp32"])
+            verdicts[f"(b) {title.split(',')[0]}, chain bf16x3"] = _gain(r["bf16x3,bf16x3"], r["bf16x3,fp32"])
+    rows = [(load("smodel.json"), "deformation net"), (load("smodel_blender.json"), "blender net")]
+    if any(r for r, _ in rows):
+        L += ["", "## (c) One model training step at 240 000 Gaussians, 960 x 540, behind `warm_up` (`FG_FUSED_MLP_TRAIN` and `_WGRAD` set)", "",
+              "| model | fp32, fp32 ms | fp32, bf16x3 ms | bf16x3, fp32 ms | bf16x3, bf16x3 ms |", "|---|---|---|---|---|"]  # fmt: skip
+        for r, title in rows:
+            if r:
+                q = r["ms"]
+                L.append(f"| {title} | " + " | ".join(f"{q[k]['median']:.2f} ({q[k]['p10']:.2f} .. {q[k]['p90']:.2f})" for k in ("fp32,fp32", "fp32,bf16x3", "bf16x3,fp32", "bf16x3,bf16x3")) + " |")
+    stats = sorted(glob.glob(os.path.join(out, "strace", "**", "*kernel_stats.csv"), recursive=True))
+    if stats:
+        L += ["", "## (d) Kernels of three training calls of each of the four settings at N = 240 000 (`rocprofv3 --kernel-trace --stats`, a run of its own)", "",
+              "| kernel | calls | average us | share % |", "|---|---|---|---|"]  # fmt: skip
+        for r in list(csv.DictReader(open(stats[0])))[:16]:
+            L.append(f"| `{r['Name'][:90]}` | {r['Calls']} | {float(r['AverageNs']) / 1e3:.1f} | {float(r['Percentage']):.1f} |")
+    er = load("serror.json")
+    if er:
+        L += ["", "## (e) Error against float64 of the same arrays at N = 33 000 (max |a - b| / max |b|; the bar is 1e-4)", "",
+              "| gradients | bf16x3 | fp32 |", "|---|---|---|"]  # fmt: skip
+        L += [f"| {k} | {v['bf16x3']:.2e} | {v['fp32']:.2e} |" for k, v in er.items()]
+    if verdicts:
+        L += ["", "## Outcome by the rule (240 000 rows)", ""] + [f"- {k}: **{v}**" for k, v in verdicts.items()]
+    # (hand-written sections of the file -- everything from the first "## Notes" heading on -- are kept)
+    if os.path.exists(md) and "\n## Notes" in open(md).read():
+        L += ["", "## Notes" + open(md).read().split("\n## Notes", 1)[1].rstrip()]
+    open(md, "w").write("\n".join(L) + "\n")
+    print("\n".join(L))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--step", choices=["time", "error", "model", "trace", "kernel", "report", "wcall", "werror", "wtrain", "wmodel",
                                        "wtrace", "wreport", "ccall", "ctrain", "cmodel", "cmem", "ctrace", "creport", "ptrain", "pmodel", "perror",
-                                       "ptrace", "preport"])  # fmt: skip
+                                       "ptrace", "preport", "scall", "serror", "strain", "smodel", "strace", "scounters", "sreport"])  # fmt: skip
+    ap.add_argument("--wgrad-precision", action="store_true",
+                    help="the split-bf16 mode of the parameter-gradient products, FG_FUSED_MLP_WGRAD_PRECISION, against fp32 (profiles/mlp_wgrad_split.md)")
     ap.add_argument("--precision", action="store_true", help="the split-bf16 mode, FG_FUSED_MLP_PRECISION, against fp32 (profiles/mlp_split_bf16.md)")
     ap.add_argument("--chunked", action="store_true", help="the backward in row chunks, FG_FUSED_MLP_CHUNKED (profiles/mlp_chunked_bwd.md)")
     ap.add_argument("--only", default=None, help="with --chunked: a comma-separated subset of its steps (ccall,base,ctrain,cmodel,cmem,ctrace,creport)")
@@ -1233,12 +1471,19 @@ def main():
         name = "mlp_chunked_bwd"
     if a.precision or (a.step or "").startswith("p"):
         name = "mlp_split"
+    if a.wgrad_precision or (a.step or "").startswith("s"):
+        name = "mlp_wgrad_split"
     if a.lib:
         _use_library(a.lib)
     a.out = a.out or os.path.join(ROOT, "results", name)
     a.md = a.md or os.path.join(ROOT, "profiles", "mlp_split_bf16.md" if name == "mlp_split" else name + ".md")
     os.makedirs(a.out, exist_ok=True)
     if a.step:
+        if a.step == "sreport":
+            return sstep_report(a.out, a.md)
+        if a.step.startswith("s"):
+            return {"scall": sstep_call, "serror": sstep_error, "strain": sstep_train, "smodel": sstep_model, "strace": sstep_trace,
+                    "scounters": sstep_counters}[a.step](a.out)  # fmt: skip
         if a.step == "preport":
             return pstep_report(a.out, a.md)
         if a.step.startswith("p"):
@@ -1297,6 +1542,15 @@ def main():
             steps.append((180, ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", os.path.join(a.out, "ptrace"),
                                 "-o", "mlp", "--"] + me + ["ptrace"]))  # fmt: skip
         steps.append((60, me + ["preport"]))
+    if a.wgrad_precision:
+        me = [sys.executable, os.path.abspath(__file__), "--out", a.out, "--md", a.md, "--step"]
+        steps = [(300, me + ["scall"]), (120, me + ["serror"]), (300, me + ["strain"]), (300, me + ["strain", "--blender"]), (300, me + ["smodel"])]
+        if a.trace:  # the kernel trace, then the LDS counters: a run each, the counters with no tracing beside them
+            steps.append((180, ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", os.path.join(a.out, "strace"),
+                                "-o", "mlp", "--"] + me + ["strace"]))  # fmt: skip
+            steps.append((180, ["rocprofv3", "--pmc", "SQ_LDS_BANK_CONFLICT", "SQ_LDS_IDX_ACTIVE", "--output-format", "csv", "-d",
+                                os.path.join(a.out, "scounters"), "-o", "mlp", "--"] + me + ["scounters"]))  # fmt: skip
+        steps.append((60, me + ["sreport"]))
     for limit, cmd in steps:  # chained like &&: the first failure ends the job
         rc = subprocess.call(["timeout", "-k", "10", str(limit)] + cmd)
         if rc != 0:
