@@ -1,0 +1,270 @@
+"""The compositing stage's restatement (tests/raster_restatement.py) and its regime scene, checked on the CPU: the fp32
+restatement is the pinned oracle's ``rasterize`` / ``rasterize_backward(alpha_out=)``, every regime is what it is named for,
+the pixels left out for sitting on a decision threshold are few and cost no row more than a fifth of its footprint, fp32 and
+float64 take the same decisions on every pixel that is kept, and the row-wise bound the GPU test applies (F x the fp32
+restatement's own row distance from float64, per regime, cotangent group and tensor) catches each wrong restatement."""
+import functools
+
+import pytest
+import torch
+
+import raster_restatement as R
+from oracle import raster_oracle as O
+
+C = 3
+
+
+@functools.lru_cache(maxsize=None)
+def _scene():
+    return R.regime_scene(R.SEED)
+
+
+@functools.lru_cache(maxsize=None)
+def _margins():
+    return R.margins(_scene())
+
+
+@functools.lru_cache(maxsize=None)
+def _grads(dtype, mutant=None, channels=C):
+    return R.gradients(_scene(), channels, dtype, _margins()["kept"], mutant=mutant)
+
+
+def _tile_pixels(tile):
+    ty, tx = divmod(tile, R.TILE_W)
+    return slice(ty * R.TILE, (ty + 1) * R.TILE), slice(tx * R.TILE, (tx + 1) * R.TILE)
+
+
+def _footprints():
+    """[N] pixels each row contributes to (float64), and how many of them are kept."""
+    sc, m = _scene(), _margins()
+    total, kept = torch.zeros(len(sc.labels)), torch.zeros(len(sc.labels))
+    for t, s, e, y0, y1, x0, x1 in R._tiles(sc):
+        if e > s:
+            ids = sc.flatten_ids[s:e].long()
+            inc = m["contributing"][t].float()
+            total.index_add_(0, ids, inc.sum(0))
+            kept.index_add_(0, ids, (inc * m["kept"][y0:y1, x0:x1].reshape(-1, 1).float()).sum(0))
+    return total, kept
+
+
+@pytest.mark.parametrize("channels", [1, 3, 8])
+def test_fp32_restatement_is_the_pinned_oracle(channels):
+    """Measured: bit for bit -- forward, last_ids and all five gradients (the formulae and their order are the oracle's)."""
+    sc = _scene()
+    kept = _margins()["kept"]
+    feats = sc.features(channels)
+    r, a, last = O.rasterize(sc.means2d, sc.conics, feats, sc.opacities, sc.width, sc.height, R.TILE, sc.offsets, sc.flatten_ids)
+    fwd = R.composite(sc, channels, torch.float32)
+    assert torch.equal(fwd["render"], r) and torch.equal(fwd["alpha"], a[..., 0]) and torch.equal(fwd["last_ids"], last)
+    vr, va = R.cotangents(channels, "both", kept)
+    ref = O.rasterize_backward(sc.means2d, sc.conics, feats, sc.opacities, sc.width, sc.height, R.TILE, sc.offsets,
+                               sc.flatten_ids, vr.float(), va.float(), alpha_out=a)  # fmt: skip
+    grads, _ = R.backward(sc, channels, vr, va, fwd["alpha"], torch.float32)
+    for name, x in zip(("means2d", "absgrad", "conics", "features", "opacities"), ref):
+        assert bool(torch.isfinite(x).all()), name
+        assert torch.equal(grads[name].reshape(x.shape), x), name
+
+
+def test_census_every_regime_is_what_it_is_named_for():
+    sc, m = _scene(), _margins()
+    for name, n in R.COUNTS.items():
+        assert len(sc.rows(name)) == n
+    assert (sc.width, sc.height) == (72, 40) and sc.offsets.numel() == R.TILE_W * R.TILE_H + 1
+    lens = (sc.offsets[1:] - sc.offsets[:-1]).long()
+    total, _ = _footprints()
+    f64, g64 = _grads(torch.float64)
+    # faint and occluded: exactly zero in every group and tensor; no pixel takes them
+    for name in ("faint", "occluded"):
+        rows = sc.rows(name)
+        assert bool((total[rows] == 0).all())
+        for group in R.GROUPS:
+            for tensor in R.TENSORS:
+                assert bool(R.zero_rows(g64[group][0][tensor])[rows].all()), (name, group, tensor)
+    assert bool((sc.opacities[sc.rows("faint")] < O.ALPHA_SKIP).all())
+    # every other regime has rows that contribute; barely: a few pixels each
+    for name in R.COUNTS:
+        if name not in ("faint", "occluded"):
+            assert bool((total[sc.rows(name)] > 0).any()), name
+    barely = total[sc.rows("barely")]
+    assert 0 < float(barely[barely > 0].median()) <= 40
+    # opaque: the 0.999 clamp holds on pixels that take the row; plain rows are never clamped
+    clamped = torch.zeros(len(sc.labels))
+    reach = {}
+    for t, s, e, y0, y1, x0, x1 in R._tiles(sc):
+        if e > s:
+            ids = sc.flatten_ids[s:e].long()
+            px, py = R._pixel_centres(y0, y1, x0, x1, torch.float64)
+            _, _, sigma, _, _, include, stopped = R._walk(px, py, sc.means2d.double()[ids], sc.conics.double()[ids], sc.opacities.double()[ids])
+            over = include & (sc.opacities.double()[ids][None, :] * torch.exp(-sigma.clamp_min(0)) > O.ALPHA_MAX)
+            clamped.index_add_(0, ids, over.float().sum(0))
+            reach[t] = (sigma, include, stopped, ids)
+    assert bool((sc.opacities[sc.rows("opaque")] == 1.0).all()) and int((clamped[sc.rows("opaque")] > 0).sum()) >= 8
+    assert bool((clamped[sc.rows("plain", "deep", "needle", "edge", "subpixel")] == 0).all())
+    # deep: one list beyond 256 entries (the staging batch of every pixels-per-lane body is 64, 128 or 256), nothing stops
+    assert int(lens[R.DEEP_TILE]) > 256 and int(lens.argmax()) == R.DEEP_TILE
+    ys, xs = _tile_pixels(R.DEEP_TILE)
+    assert not bool(f64["stopped"][ys, xs].any())
+    sigma, include, _, ids = reach[R.DEEP_TILE]
+    deep_here = torch.tensor([sc.labels[int(i)] == "deep" for i in ids])
+    assert int(deep_here.sum()) == R.COUNTS["deep"] and int(include[:, deep_here].any(0).sum()) > 256
+    assert int(include[:, 256:].any(0).sum()) > 32  # entries beyond the first 256 are taken
+    # wall: every pixel of its tile stops, inside the wall
+    ys, xs = _tile_pixels(R.WALL_TILE)
+    assert bool(f64["stopped"][ys, xs].all())
+    _, include, _, ids = reach[R.WALL_TILE]
+    assert all(sc.labels[int(i)] == "wall" for i in ids[include.any(0)])
+    assert set(sc.labels[int(i)] for i in ids) >= {"wall", "occluded"}
+    # indefinite: b^2 > a c; every row has pixels it skips for sigma < 0 and pixels that take it
+    ind = sc.rows("indefinite")
+    con = sc.conics.double()[ind]
+    assert bool((con[:, 1] ** 2 > con[:, 0] * con[:, 2]).all())
+    skipped, taken = torch.zeros(len(sc.labels)), torch.zeros(len(sc.labels))
+    for t, (sigma, include, stopped, ids) in reach.items():
+        skipped.index_add_(0, ids, ((sigma < 0) & m["evaluated"][t]).float().sum(0))
+        taken.index_add_(0, ids, include.float().sum(0))
+    assert bool((skipped[ind] > 0).all()) and bool((taken[ind] > 0).all())
+    assert bool((skipped[sc.rows(*[k for k in R.COUNTS if k != "indefinite"])] == 0).all())
+    # partial tiles hold contributing rows; no tile is empty (the huge rows reach every one)
+    cls = R.pixel_class()
+    partial = cls == R.PIXEL_CLASSES.index("partial")
+    assert int(partial.sum()) == 72 * 40 - 64 * 32 and bool((f64["weight"][partial] > 0).float().mean() > 0.9)
+    assert bool((lens > 0).all())
+    huge_lists = torch.zeros(len(sc.labels))
+    huge_lists.index_add_(0, sc.flatten_ids.long(), torch.ones(sc.flatten_ids.numel()))
+    assert bool((huge_lists[sc.rows("huge")] == R.TILE_W * R.TILE_H).all())
+    # edge: centres outside the image, still contributing
+    ex = sc.means2d[sc.rows("edge"), 0]
+    assert bool(((ex < 0) | (ex > sc.width)).all()) and bool((total[sc.rows("edge")] > 0).all())
+    # sub-pixel: a 3 x 3 block of pixels at the most
+    assert bool((total[sc.rows("subpixel")] <= 9).all())
+
+
+def test_exclusions_are_few_and_cost_no_row_much():
+    """Conditions on the chosen seed, not measurements: at most 1.5 % of the pixels excluded; every contributing row keeps at
+    least 80 % of the pixels it contributes to."""
+    m = _margins()
+    excluded = 1.0 - float(m["kept"].float().mean())
+    total, kept = _footprints()
+    share = (kept / total)[total > 0]
+    print(f"excluded {int((~m['kept']).sum())} of {m['kept'].numel()} pixels ({100 * excluded:.2f} %): "
+          + ", ".join(f"{k} {int((m[k] < (R.T_MARGIN if k == 'stop' else R.ALPHA_MARGIN)).sum())}" for k in ("skip", "clamp", "stop", "sigma"))
+          + f"; smallest kept share of a row {float(share.min()):.3f}; {int((total > 0).sum())} contributing rows")  # fmt: skip
+    assert 0 < excluded <= 0.015
+    assert float(share.min()) >= 0.8
+
+
+def test_fp32_and_float64_decide_alike_on_kept_pixels():
+    sc, kept = _scene(), _margins()["kept"]
+    f32, f64 = R.composite(sc, C, torch.float32), R.composite(sc, C, torch.float64)
+    assert torch.equal(f32["last_ids"][kept], f64["last_ids"][kept])
+    assert torch.equal(f32["stopped"][kept], f64["stopped"][kept])
+    for t, s, e, y0, y1, x0, x1 in R._tiles(sc):
+        if e > s:
+            k = kept[y0:y1, x0:x1].reshape(-1)
+            assert torch.equal(f32["include"][t][k], f64["include"][t][k]), t
+
+
+def test_yardsticks_are_floored_and_finite():
+    for channels in (1, 3, 4, 8):
+        f32, g32 = _grads(torch.float32, None, channels)
+        f64, g64 = _grads(torch.float64, None, channels)
+        for what, per_class in R.forward_yardstick(f32, f64, _margins()["kept"]).items():
+            for cls, e in per_class.items():
+                assert R.FLOOR <= e < 1e-4, (channels, what, cls, e)
+        for group in R.GROUPS:
+            grads, accum = g64[group]
+            for tensor in R.TENSORS:
+                assert bool(torch.isfinite(grads[tensor]).all()) and bool((accum[tensor] >= 0).all())
+                # a row is exactly zero where its accumulation is
+                assert bool(R.zero_rows(grads[tensor])[R.zero_rows(accum[tensor])].all())
+                assert bool((g32[group][0][tensor][R.zero_rows(grads[tensor])] == 0).all()), (group, tensor)
+                for regime, e in R.yardstick(_scene().labels, g32[group][0][tensor], grads[tensor], accum[tensor]).items():
+                    assert R.FLOOR <= e < 1e-3, (channels, group, tensor, regime, e)
+
+
+LIVE = tuple(k for k in R.COUNTS if k not in ("faint", "occluded"))
+GEOMETRY = ("means2d", "absgrad", "conics", "opacities")
+# (mutant, cotangent groups that drive it, tensors it reaches, regimes it concerns)
+MUTANT_CASES = [
+    # the clamped pixel of an opaque row is the one its mean sits in: dx, dy ~ 0.03 sigma there and the position and
+    # shape gradients through it vanish; the opacity gradient does not
+    ("clamp_passes_gradient", R.GROUPS, ("opacities",), ("opaque",)),
+    # the rows the stop rule drops at every pixel: the wall's rear rows and everything behind it
+    ("stop_entry_composited", R.GROUPS, R.TENSORS, ("wall", "occluded")),
+    # (the alpha group has no suffix sums: v_render = 0)
+    ("suffix_includes_self", ("render", "both"), GEOMETRY, LIVE),
+    ("conic_b_halved", R.GROUPS, ("conics",), LIVE),
+    ("absgrad_abs_of_sum", R.GROUPS, ("absgrad",), LIVE),
+]
+
+
+def mutant_shares(factor):
+    """-> {(mutant, group, tensor, regime): (caught, rows, smallest caught-making F)}: a row of the mutant's float64 gradient
+    is CAUGHT when the GPU test would flag it -- not zero where the true row is exactly zero, or at least 4 * factor * E32
+    from the true row.  Rows that are zero in both do not count (the mutant does not reach them)."""
+    sc = _scene()
+    _, g32 = _grads(torch.float32)
+    _, g64 = _grads(torch.float64)
+    out = {}
+    for mutant, groups, tensors, regimes in MUTANT_CASES:
+        _, gm = _grads(torch.float64, mutant)
+        for group in groups:
+            for tensor in tensors:
+                ref, acc = g64[group][0][tensor], g64[group][1][tensor]
+                e32 = R.yardstick(sc.labels, g32[group][0][tensor], ref, acc)
+                d = R.row_distance(gm[group][0][tensor], ref, acc)
+                zero, zero_m = R.zero_rows(ref), R.zero_rows(gm[group][0][tensor])
+                for regime in regimes:
+                    rows = sc.rows(regime)
+                    rows = rows[~(zero[rows] & zero_m[rows])]
+                    if len(rows) == 0 and group == "alpha" and tensor == "features":
+                        continue  # (no colour gradient without v_render)
+                    caught = torch.where(zero[rows], ~zero_m[rows], d[rows] >= 4 * factor * e32[regime])
+                    ratios = torch.where(zero[rows], torch.full_like(d[rows], float("inf")), d[rows] / e32[regime])
+                    # the largest F at which three quarters of the rows are still caught
+                    k = max(int(-(-3 * len(rows) // 4)), 1)
+                    cap = float(torch.sort(ratios, descending=True).values[k - 1]) / 4 if len(rows) else 0.0
+                    out[(mutant, group, tensor, regime)] = (int(caught.sum()), len(rows), cap)
+    return out
+
+
+def test_every_mutant_is_listed():
+    assert {c[0] for c in MUTANT_CASES} == set(R.MUTANTS)
+
+
+def test_mutants_are_caught_by_the_row_bound():
+    """On at least three quarters of the rows of each regime a mutant concerns, in each cotangent group that drives it, the
+    mutant's float64 gradient is at least 4 * F * E32 from the true one, or not zero where the true one is exactly zero
+    (cancellation may hide it on single rows): the GPU bound F * E32 has teeth, and this caps F.  Only
+    ``stop_entry_composited`` changes the forward."""
+    f64, _ = _grads(torch.float64)
+    for mutant in R.MUTANTS:
+        fm, _ = _grads(torch.float64, mutant)
+        assert torch.equal(fm["render"], f64["render"]) == (mutant != "stop_entry_composited"), mutant
+    factor = 1.0 if R.F is None else R.F
+    shares = mutant_shares(factor)
+    cap = min(v[2] for v in shares.values())
+    worst = {}
+    for (mutant, group, tensor, regime), (caught, rows, c) in shares.items():
+        key = (mutant, regime)
+        if key not in worst or c < worst[key][4]:
+            worst[key] = (caught, rows, group, tensor, c)
+    for (mutant, regime), (caught, rows, group, tensor, c) in worst.items():
+        print(f"{mutant} {regime}: {caught}/{rows} rows caught at F = {factor:g} in its weakest cell ({group}, {tensor}), which caps F at {c:.1f}")
+    print(f"the cap on F: {cap:.1f}")
+    failures = [f"{k}: {v[0]}/{v[1]}" for k, v in shares.items() if v[1] == 0 or 4 * v[0] < 3 * v[1]]
+    assert not failures, "\n".join(failures)
+    assert R.F is None or R.F <= cap
+    # where the true gradient is exactly zero the mutant's is not: the wall's rear rows and everything behind it
+    sc = _scene()
+    _, g64 = _grads(torch.float64)
+    _, gm = _grads(torch.float64, "stop_entry_composited")
+    for group in R.GROUPS:
+        for tensor in R.TENSORS:
+            if group == "alpha" and tensor == "features":
+                continue  # (no colour gradient without v_render)
+            zero = R.zero_rows(g64[group][0][tensor])
+            for regime in ("wall", "occluded"):
+                rows = sc.rows(regime)
+                rows = rows[zero[rows]]
+                assert len(rows) >= 4 and not bool(R.zero_rows(gm[group][0][tensor])[rows].any()), (group, tensor, regime)
