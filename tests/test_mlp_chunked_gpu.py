@@ -373,28 +373,29 @@ def test_modules_with_the_knob_set_and_unset(kind, train, spy, monkeypatch):
 
 def test_model_training_step_with_the_knob_set_and_unset(spy, monkeypatch):
     """The default (blender) model, one training step with the knob set and one with it unset: the loss and every gradient
-    equal bit for bit."""
-    from freegaussian_amd.model import Camera, FreeGaussianModel, FreeGaussianModelConfig
-    from freegaussian_amd.scenes import look_at_viewmat
+    equal bit for bit.
 
-    # The render's backward adds a splat's gradient with one float atomic per (splat, job), so two runs of it agree bit for bit
-    # only where no splat gets more than two addends (a + b = b + a; a third makes the order show: DESIGN.md, "atomic order").
-    # An image of ONE 16 x 16 tile gives every splat one job, so the step is repeatable and "equal" can be asked of everything.
-    torch.manual_seed(0)
-    n, W, H = D.FUSED_MIN_ROWS, 16, 16  # the smallest count that reaches the dispatch
-    cfg = FreeGaussianModelConfig(background_color="white", num_downscales=0, warm_up=3000)
-    model = FreeGaussianModel(cfg, seed_points=(torch.rand(n, 3) - 0.5) * 2.0, init_scales=-3.8, is_blender=True)
-    with torch.no_grad():
-        model.gauss_params["scales"].normal_(-3.8, 0.3)
-        model.gauss_params["features_rest"].normal_(0, 0.1)
-        for q in model.deform.parameters():
-            q.mul_(0.3)
-    model.step = 4000  # behind warm_up: the deformation net runs
-    model = model.to(DEV).train()
-    c2w = torch.linalg.inv(look_at_viewmat(torch.tensor([0.3, -0.2, -3.0]), torch.zeros(3)))
-    c2w[:3, 1:3] *= -1
-    cam = Camera(c2w[None, :3], 56.0, 60.0, W / 2, H / 2, W, H, times=torch.tensor([[0.4]]))
-    gt = torch.rand(H, W, 3, generator=torch.Generator().manual_seed(12)).to(DEV)
+    The render's backward adds into a splat's gradient with one float atomic per WAVEFRONT that has a contributing pixel, and
+    two runs of it agree bit for bit only where no splat gets more than two such addends (0 + a + b = 0 + b + a; a third makes
+    the order show: DESIGN.md, "atomic order").  An image of one 16 x 16 tile is one workgroup -- of FOUR wavefronts, four
+    pixel rows each (the classic launch below 3000 tiles) -- so a splat gets one addend per 4-row strip it reaches, up to
+    four.  This test used to draw its log-scales around -3.8: one of its 32 768 splats reached three strips, the step had two
+    outcomes and the test failed one run in three (profiles/step_repeatability.md).  Around -5.2 the footprints are the
+    0.3-pixel blur's, no splat reaches more than two strips -- counted below from the step's own records
+    (tests/step_repeat_common.py ``addend_count``) -- and "equal" can be asked of everything."""
+    import step_repeat_common as S
+
+    model, cam, gt = S.make_step(DEV, S.SCALE_MEAN)
+    n, W, H = model.num_points, S.W_STEP, S.H_STEP
+    assert n == D.FUSED_MIN_ROWS  # the smallest count that reaches the dispatch
+    rastered, real_raster = [], ops.rasterize_splats
+
+    def raster(splats, means2d, channels, width, height, tile_size, offsets, ids, **kw):
+        out = real_raster(splats, means2d, channels, width, height, tile_size, offsets, ids, **kw)
+        rastered.append((splats.detach(), offsets, ids, out[2], width, height))
+        return out
+
+    monkeypatch.setattr(ops, "rasterize_splats", raster)
     monkeypatch.setenv("FG_FUSED_MLP_TRAIN", "2")
     monkeypatch.setenv("FG_FUSED_MLP_WGRAD", "1")
     grads, losses = {}, {}
@@ -407,6 +408,16 @@ def test_model_training_step_with_the_knob_set_and_unset(spy, monkeypatch):
         losses[knob] = loss.detach().clone()
         grads[knob] = {k: p.grad.detach().clone() for k, p in model.named_parameters() if p.grad is not None}
     assert spy == ["fg_mlp_train_bwd", "fg_mlp_bwd_inputs", "fg_mlp_param_grads"]  # one step each
+    # the census: both steps took the classic launch (no job lists at one tile), and no splat of either gets a third addend
+    assert S.launch_of(W, H) == "classic" and int(_lib.load().fg_raster_jobs_words(W, H, 16, ops.current().cfg())) == 0
+    assert len(rastered) >= 2
+    for splats, offsets, ids, last_ids, w, h in rastered:
+        assert (w, h) == (W, H)
+        rec = splats.cpu()
+        addends = S.addend_count(n, *S.strip_hits(rec[:, 0:2], rec[:, 3:6], rec[:, 2], offsets, ids, last_ids, W, H), S.groups_classic(1))
+        census = S.census(addends)
+        assert census["max"] <= 2, census
+    assert census["1"] > 0 and census["2"] > 0, census  # (addends do meet: the order is exercised, and cannot show)
     on, off = grads["1"], grads[None]
     assert torch.equal(losses["1"], losses[None]) and set(on) == set(off)
     deform = [k for k in on if k.startswith("deform.")]
