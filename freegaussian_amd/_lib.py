@@ -126,6 +126,12 @@ SIGNATURES = {
     "fg_mlp_param_grads_p": (c_int, [c_int64, P, P, P, P, P, P, c_int32, P, c_size_t, P]),
     # (N, desc, g_heads, enc, acts, g_enc, const fg_mlp_grads*, chunk_slabs, wgrad_precision, workspace, bytes, stream)
     "fg_mlp_train_bwd_p": (c_int, [c_int64, P, P, P, P, P, P, c_int32, c_int32, P, c_size_t, P]),
+    # bilateral-grid slice of one camera's grid [12,GL,GY,GX] over an [H,W,3] image (csrc/bilagrid.hip)
+    "fg_bilagrid_supported": (c_int, [c_int, c_int, c_int]),  # (GX, GY, GL) -> 1 or 0
+    "fg_bilagrid_bwd_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),  # (H, W, GX, GY, GL)
+    "fg_bilagrid_slice_fwd": (c_int, [c_int, c_int, c_int, c_int, c_int, P, P, P, P]),  # (H, W, GX, GY, GL, grid, rgb, out, stream)
+    # (H, W, GX, GY, GL, grid, rgb, v_out, v_rgb, v_grid, workspace, bytes, stream)
+    "fg_bilagrid_slice_bwd": (c_int, [c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P, c_size_t, P]),
 }  # fmt: skip
 
 # test hooks, not declared in the public header

@@ -11,10 +11,15 @@ with the same names, arguments and tensor layouts.  **Parity unpinned**: there i
 reference and the library cannot be run here; ``tests/test_bilagrid.py`` checks it against a scalar restatement of
 trilinear slicing and against the properties the algorithm defines (identity grids, affine recovery).
 
-Plain torch on purpose: an image-sized ``grid_sample`` plus a 3x4 multiply per pixel, off the section-8 hot path and
-off by default -- it is here so a user of the reference who turns the switch on finds it."""
+Torch ops by default: an image-sized ``grid_sample`` plus a 3x4 multiply per pixel, off the section-8 hot path and off by
+default.  ``FG_FUSED_BILAGRID=1`` (opt-in) sends ``apply_to_render`` -- the slice of a whole rendered image, the one use on
+the training path -- through ``ops.bilagrid_apply`` instead (csrc/bilagrid.hip: one streaming launch forward, the grid
+gradient as a gather with a fixed order of addition, no per-pixel matrices in memory; measured in
+profiles/bilagrid_fused.md).  ``slice`` at free coordinates, ``color_correct`` and ``total_variation_loss`` are torch ops
+either way."""
 from __future__ import annotations
 
+import os
 from typing import Dict, Optional
 
 import torch
@@ -88,9 +93,41 @@ def slice(bil_grids: BilateralGrid, xy: torch.Tensor, rgb: torch.Tensor, grid_id
     return {"rgb": out.reshape(shape), "rgb_affine_mats": mats.reshape(*shape[:-1], 3, 4)}
 
 
+def fused_bilagrid() -> bool:
+    """``FG_FUSED_BILAGRID`` (opt-in; read here and nowhere else, on the host, on every call): unset or ``0`` = the torch ops,
+    ``1`` = the fused slice where it applies.  Anything else is an error, not a silent default."""
+    knob = os.environ.get("FG_FUSED_BILAGRID", "0")
+    if knob not in ("0", "1"):
+        raise ValueError(f"FG_FUSED_BILAGRID wants 0 or 1, got {knob!r}")
+    return knob == "1"
+
+
+def fused_applies(bil_grids: BilateralGrid, rgb: torch.Tensor) -> bool:
+    """Does ``apply_to_render`` take the fused call for this image?  Only with the knob set, CUDA float32 tensors, a grid
+    shape and an image size the library takes (its own queries say), one image of at least 2 x 2 pixels."""
+    if not fused_bilagrid():
+        return False
+    grids = bil_grids.grids
+    if not (grids.is_cuda and rgb.is_cuda and grids.dtype == torch.float32 and rgb.dtype == torch.float32):
+        return False
+    if rgb.dim() not in (3, 4) or rgb.shape[-1] != 3 or (rgb.dim() == 4 and rgb.shape[0] != 1):
+        return False
+    H, W = int(rgb.shape[-3]), int(rgb.shape[-2])
+    from . import _lib
+
+    lib = _lib.load()
+    _, _, GL, GY, GX = grids.shape
+    return H >= 2 and W >= 2 and bool(lib.fg_bilagrid_supported(GX, GY, GL)) and lib.fg_bilagrid_bwd_workspace_bytes(H, W, GX, GY, GL) > 0
+
+
 def apply_to_render(bil_grids: BilateralGrid, rgb: torch.Tensor, cam_idx: int, H: int, W: int) -> torch.Tensor:
     """What the reference's base class does with a rendered image [1, H, W, 3] of training camera ``cam_idx``
-    (``_apply_bilateral_grid``, called at ``freegaussian_model.py:882``): a [0, 1]^2 pixel grid, one slice."""
+    (``_apply_bilateral_grid``, called at ``freegaussian_model.py:882``): a [0, 1]^2 pixel grid, one slice.  With
+    ``FG_FUSED_BILAGRID=1`` and tensors the fused kernels take (``fused_applies``): ``ops.bilagrid_apply``."""
+    if fused_applies(bil_grids, rgb) and tuple(rgb.shape[-3:-1]) == (int(H), int(W)):
+        from . import ops
+
+        return ops.bilagrid_apply(bil_grids.grids, int(cam_idx), rgb.reshape(int(H), int(W), 3)).reshape(rgb.shape)
     dev = rgb.device
     gy, gx = torch.meshgrid(torch.linspace(0, 1.0, H, device=dev), torch.linspace(0, 1.0, W, device=dev), indexing="ij")
     grid_xy = torch.stack([gx, gy], dim=-1).unsqueeze(0)

@@ -1202,6 +1202,65 @@ def l1_ssim(pred: torch.Tensor, gt: torch.Tensor):
     return _L1Ssim.apply(_f32(pred, "pred"), _f32(gt.detach(), "gt"))
 
 
+class _BilagridApply(torch.autograd.Function):
+    """One camera's bilateral grid sliced at (x, y, luma) and applied to an [H,W,3] image (csrc/bilagrid.hip): saves its
+    inputs only; the backward recomputes the per-pixel matrices and forms the gradients that are asked for."""
+
+    @staticmethod
+    def forward(ctx, grids, cam_idx, rgb):
+        H, W, _ = rgb.shape
+        _, _, GL, GY, GX = grids.shape
+        block = grids[cam_idx]  # (a view: the camera's [12,GL,GY,GX] block of the contiguous parameter)
+        out = torch.empty_like(rgb)
+        _call("fg_bilagrid_slice_fwd", H, W, GX, GY, GL, _ptr(block), _ptr(rgb), _ptr(out), _stream(), stage="fg_bilagrid_slice_fwd")
+        ctx.save_for_backward(rgb, block)
+        ctx.cam_idx, ctx.grids_shape = cam_idx, grids.shape
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, v_out):
+        rgb, block = ctx.saved_tensors
+        H, W, _ = rgb.shape
+        _, _, GL, GY, GX = ctx.grids_shape
+        want_grids, _, want_rgb = ctx.needs_input_grad
+        if not (want_grids or want_rgb):
+            return None, None, None
+        v_out = _f32(v_out, "v_out")
+        v_rgb = torch.empty_like(rgb) if want_rgb else None
+        v_grids = ws = None
+        n_ws = 0
+        if want_grids:
+            # (dense zeros with the camera's block filled: what torch's index backward gives)
+            v_grids = torch.zeros(ctx.grids_shape, dtype=torch.float32, device=rgb.device)
+            n_ws = int(_lib.load().fg_bilagrid_bwd_workspace_bytes(H, W, GX, GY, GL))
+            ws = torch.empty(n_ws, dtype=torch.uint8, device=rgb.device)
+        _call("fg_bilagrid_slice_bwd", H, W, GX, GY, GL, _ptr(block), _ptr(rgb), _ptr(v_out), _ptr(v_rgb),
+              _ptr(v_grids[ctx.cam_idx]) if want_grids else None, _ptr(ws), n_ws, _stream(), stage="fg_bilagrid_slice_bwd")  # fmt: skip
+        return v_grids, None, v_rgb
+
+
+def bilagrid_apply(grids: torch.Tensor, cam_idx: int, rgb: torch.Tensor) -> torch.Tensor:
+    """``rgb`` [H,W,3] through the bilateral grid ``grids[cam_idx]`` of ``grids`` [num,12,GL,GY,GX] -> [H,W,3]: what
+    ``bilagrid.apply_to_render`` states in torch ops (grid_sample: bilinear, align_corners, border), as one launch forward and
+    -- per gradient that is asked for -- one (``rgb``) or two (``grids``: partial sums, then their fixed-order sum; no
+    atomics, so the gradient is bit for bit reproducible) backward.  Differentiable with respect to ``grids`` and ``rgb``."""
+    if grids.dim() != 5 or grids.shape[1] != 12 or rgb.dim() != 3 or rgb.shape[-1] != 3:
+        raise ValueError(f"grids [num,12,GL,GY,GX] and rgb [H,W,3] expected, got {tuple(grids.shape)} and {tuple(rgb.shape)}")
+    if not (grids.is_cuda and rgb.is_cuda):
+        raise _lib.FgRasterError("bilagrid_apply runs on the GPU only (bilagrid.apply_to_render is the torch statement of it)")
+    cam_idx = int(cam_idx)
+    if not 0 <= cam_idx < grids.shape[0]:
+        raise ValueError(f"cam_idx {cam_idx} outside the {grids.shape[0]} grids")
+    _, _, GL, GY, GX = grids.shape
+    if not _lib.load().fg_bilagrid_supported(GX, GY, GL):
+        raise ValueError(f"bilateral grid shape (X {GX}, Y {GY}, W {GL}) is outside what the fused slice takes")
+    H, W, _ = rgb.shape
+    if H < 2 or W < 2:
+        raise ValueError(f"an image of at least 2 x 2 pixels expected, got {H} x {W}")
+    return _BilagridApply.apply(_f32(grids, "grids"), cam_idx, _f32(rgb, "rgb"))
+
+
 @torch.no_grad()
 def isect_keys(tile_keys, flatten_ids, depths):
     """Reference-style 64-bit keys (tile << 32 | depth bits) of the sorted list."""

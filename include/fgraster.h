@@ -49,7 +49,9 @@ typedef void* fg_stream_t;
 /* (fg_mlp_precision_supported, added later still, is discovered BY NAME -- dlsym, or ctypes' hasattr -- not by the minor
  * number, which stays 1: a library without the symbol takes fg_mlp_desc::precision as the reserved word it was and
  * computes in fp32.  Likewise BY NAME: fg_mlp_wgrad_precision_supported, fg_mlp_param_grads_p and fg_mlp_train_bwd_p -- a
- * library without them forms the weight gradients in exact fp32 through fg_mlp_param_grads / fg_mlp_train_bwd.) */
+ * library without them forms the weight gradients in exact fp32 through fg_mlp_param_grads / fg_mlp_train_bwd.  Likewise BY
+ * NAME: fg_bilagrid_supported, fg_bilagrid_bwd_workspace_bytes, fg_bilagrid_slice_fwd and fg_bilagrid_slice_bwd -- a library
+ * without them has no fused bilateral-grid slice, and the host keeps its torch statement of it.) */
 #define FG_COUNT_OUT_WORDS 16 /* int64 words of a count_out block (fg_stbin_count, fg_step_io): ABI 9 */
 
 int fg_abi_version(void);
@@ -1050,6 +1052,41 @@ int fg_mlp_param_grads_p(int64_t N, const fg_mlp_desc* desc, const float* enc, c
 int fg_mlp_train_bwd_p(int64_t N, const fg_mlp_desc* desc, const float* g_heads, const float* enc, const float* acts, float* g_enc,
                        const fg_mlp_grads* out, int32_t chunk_slabs, int32_t wgrad_precision, void* workspace,
                        size_t workspace_bytes, fg_stream_t stream);
+
+/* ---- BG bilateral-grid colour correction of a rendered image (found BY NAME, see FG_ABI_MINOR): the slice of ONE camera's
+ * grid of 3 x 4 affine colour transforms at (x, y, luma) and its application, forward and backward (csrc/bilagrid.hip;
+ * freegaussian_amd/bilagrid.py apply_to_render is the torch statement: grid_sample with mode = "bilinear", align_corners =
+ * True, padding_mode = "border").  All fp32.
+ *   grid[12, GL, GY, GX]  one camera's block (the host passes the address of grids[cam_idx]);  rgb, out, v_out, v_rgb [H, W, 3].
+ *   Pixel (py, px):  fx = px / (W-1) (GX-1),  fy = py / (H-1) (GY-1),  fz = luma (GL-1),  luma = 0.299f r + 0.587f g + 0.114f b,
+ *   each clamped to [0, n-1];  i0 = min(floor(f), n-1), i1 = min(i0 + 1, n-1), t = f - i0;  A[12] = the trilinear mix of the
+ *   eight corners, read as a 3 x 4 matrix;  out = A[:, :3] rgb + A[:, 3].  (The kernels put a pixel that sits on the last node
+ *   into the last cell with t = 1: the same weights on the same nodes.)
+ *   fg_bilagrid_slice_bwd recomputes A from grid and rgb (the forward saves nothing) and forms
+ *     v_grid[k, z, y, x] = sum over the pixels of  w_z w_y w_x  v_out[k / 4]  (r, g, b, 1)[k % 4]      every element written
+ *     v_rgb = A[:, :3]^T v_out + (0.299f, 0.587f, 0.114f) (GL-1) sum_k (dA/dz)[k] v_out[k / 4] (r, g, b, 1)[k % 4]   overwritten
+ *   with dA/dz the (x, y)-bilinear mix of grid[z1] - grid[z0]; the term through fz is exactly zero where the unclamped
+ *   fz <= 0 or fz >= GL-1 (torch's border rule: an exactly black and an exactly white pixel get none); x and y carry no
+ *   gradient.  Either of v_rgb / v_grid may be null: that gradient is not formed (both null: nothing is launched).
+ *   v_grid is a gather without atomics: the pixels of a grid cell, in chunks of FG_BILAGRID_CHUNK_PIXELS, are summed per level
+ *   and corner into partial blocks in the workspace, and a second launch adds each node's (up to four) cells and their chunks
+ *   in a fixed order: two runs are bit for bit equal, and a node whose four cells hold no pixel is exactly 0.
+ *   A cell of cw x ch pixels takes ceil(cw ch / FG_BILAGRID_CHUNK_PIXELS) chunks; fg_bilagrid_bwd_workspace_bytes =
+ *   (chunks of the largest cell) * GL * 48 * (GX-1) * (GY-1) * 4, with the cell of index c along an axis of n nodes and S
+ *   pixels holding the pixels ceil(c (S-1) / (n-1)) .. ceil((c+1) (S-1) / (n-1)) - 1 (the last cell: up to S - 1).
+ *   Supported: 2 <= GX, GY <= 64, 2 <= GL <= 16 (fg_bilagrid_supported = 1, else 0), 2 <= H, W <= 16384.
+ *   The workspace query is pure and returns 0 for anything unsupported.  workspace: 16-byte aligned, needed for v_grid only.
+ *   FG_ERR_INVALID_ARG: H or W < 2, a null grid / rgb / out / v_out, an output that overlaps an input, another output or the
+ *   workspace, a null or misaligned workspace with v_grid asked for;  FG_ERR_UNSUPPORTED: a grid shape or image size outside the
+ *   range above;  FG_ERR_WORKSPACE: workspace_bytes below the query.  All before any launch.  Asynchronous, capturable in a
+ *   graph, no state, no environment.  Measured (profiles/bilagrid_fused.md). */
+#define FG_BILAGRID_CHUNK_PIXELS 1024
+int fg_bilagrid_supported(int GX, int GY, int GL);
+size_t fg_bilagrid_bwd_workspace_bytes(int H, int W, int GX, int GY, int GL);
+int fg_bilagrid_slice_fwd(int H, int W, int GX, int GY, int GL, const float* grid, const float* rgb, float* out,
+                          fg_stream_t stream);
+int fg_bilagrid_slice_bwd(int H, int W, int GX, int GY, int GL, const float* grid, const float* rgb, const float* v_out,
+                          float* v_rgb, float* v_grid, void* workspace, size_t workspace_bytes, fg_stream_t stream);
 
 #ifdef __cplusplus
 }
