@@ -2,24 +2,10 @@
 // fg_bilagrid_slice_fwd, fg_bilagrid_slice_bwd -- for a build of abi.hip and bilagrid.hip whose HOST code carries
 // AddressSanitizer + UndefinedBehaviorSanitizer (make bilagrid-check).  Every call below returns before a launch: the program
 // needs no GPU and touches none.
-#include <cstdint>
-#include <cstdio>
-
-#include "../../../include/fgraster.h"
-
-static int failures = 0;
-#define EXPECT(what, want)                                                        \
-  do {                                                                            \
-    const long long got_ = (long long)(what), want_ = (long long)(want);          \
-    if (got_ != want_) {                                                          \
-      std::printf("%s:%d: %s = %lld, want %lld\n", __FILE__, __LINE__, #what, got_, want_); \
-      ++failures;                                                                 \
-    }                                                                             \
-  } while (0)
+#include "check_common.h"
 
 // addresses nobody reads, 16 MiB apart: grid, rgb, v_out / out, v_rgb, v_grid, workspace
 static float* at(int i) { return reinterpret_cast<float*>((uintptr_t)4096 + ((uintptr_t)i << 24)); }
-static const size_t BIG = (size_t)1 << 40;
 
 // the header's rule restated: cell c of an axis with n nodes and S pixels starts at ceil(c (S-1) / (n-1)); the last one ends at S
 static long long longest(int S, int n) {
@@ -94,6 +80,5 @@ int main() {
   EXPECT(fg_bilagrid_slice_bwd(H, W, GX, GY, GL, at(0), at(1), at(2), nullptr, at(4), at(5), need - 1, nullptr), FG_ERR_WORKSPACE);
   EXPECT(fg_bilagrid_slice_bwd(H, W, GX, GY, GL, at(0), at(1), at(2), nullptr, nullptr, nullptr, 0, nullptr), FG_OK);
   EXPECT(fg_bilagrid_slice_bwd(H, W, GX, GY, GL, at(0), at(1), at(2), nullptr, nullptr, at(5) + 1, 0, nullptr), FG_OK);
-  std::printf(failures ? "bilagrid_args: %d FAILED\n" : "bilagrid_args: ok\n", failures);
-  return failures ? 1 : 0;
+  return report("bilagrid_args");
 }

@@ -1331,13 +1331,18 @@ def _mlp_precision(who: str, precision) -> int:
     return _MLP_PRECISIONS[precision]
 
 
+def _mlp_layers(who: str, trunk, heads):
+    """``trunk`` and ``heads`` (``nn.Linear`` modules or pairs) as two lists of ``(weight, bias)``, of the counts the kernels take."""
+    pairs, hpairs = ([(m.weight, m.bias) if hasattr(m, "weight") else tuple(m) for m in ms] for ms in (trunk, heads))
+    if len(pairs) != 8 or not 1 <= len(hpairs) <= _lib.MLP_MAX_HEADS:
+        raise ValueError(f"{who} wants 8 trunk layers and 1..{_lib.MLP_MAX_HEADS} heads, got {len(pairs)} and {len(hpairs)}")
+    return pairs, hpairs
+
+
 def _mlp_desc(who: str, x, aux, trunk, heads, mode: int):
     """The ``fg_mlp_desc`` of one call (``who`` names the caller in the errors): ``(desc, N, head rows, tensors the desc
     points into)``.  ``x`` / ``aux`` None: left null (``fg_mlp_bwd`` reads neither), ``aux`` then an int, the aux width."""
-    pairs = [(m.weight, m.bias) if hasattr(m, "weight") else tuple(m) for m in trunk]
-    hpairs = [(m.weight, m.bias) if hasattr(m, "weight") else tuple(m) for m in heads]
-    if len(pairs) != 8 or not 1 <= len(hpairs) <= _lib.MLP_MAX_HEADS:
-        raise ValueError(f"{who} wants 8 trunk layers and 1..{_lib.MLP_MAX_HEADS} heads, got {len(pairs)} and {len(hpairs)}")
+    pairs, hpairs = _mlp_layers(who, trunk, heads)
     d = _lib.MlpDesc()
     keep = []  # (contiguous copies stay alive until the call is enqueued)
     N = None
@@ -1445,6 +1450,55 @@ def mlp_wgrad_slab_rows(N: int) -> int:
     return int(_lib.load().fg_mlp_param_grads_slab_rows(int(N)))
 
 
+def _mlp_grad_args(who: str, tensors, aux_width: int, head_rows, want, chunk_slabs=0):
+    """The refusals the two gradient calls share, in the order both keep (``who`` names the caller in the errors); ``tensors``:
+    ``(enc, H, g_heads)`` or, where the call takes ``G``, ``(enc, H, G, g_heads)``.  Returns ``(N, head rows, want)``."""
+    if any(not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() for t in tensors):
+        raise ValueError(f"{who} wants contiguous CUDA float32 tensors")
+    enc, H, *G, g_heads = tensors
+    rows = [int(r) for r in head_rows]
+    n = len(rows)
+    if not 1 <= aux_width <= 64 or not 1 <= n <= _lib.MLP_MAX_HEADS or min(rows) < 1 or sum(rows) > 16:
+        raise ValueError(f"{who}: aux width {aux_width} / head rows {rows} outside what the kernels take")
+    if not isinstance(chunk_slabs, int) or isinstance(chunk_slabs, bool) or chunk_slabs < 0:
+        raise ValueError(f"{who}: chunk_slabs wants an int >= 0, got {chunk_slabs!r}")
+    N = enc.shape[0]
+    if enc.dim() != 2 or enc.shape[1] != _lib.mlp_enc_width(aux_width):
+        raise ValueError(f"{who} wants enc [N, {_lib.mlp_enc_width(aux_width)}], got {tuple(enc.shape)}")
+    if tuple(H.shape) != (8, N, 256) or any(g.shape != H.shape for g in G):
+        got = " and ".join(str(tuple(t.shape)) for t in (H, *G))
+        raise ValueError(f"{who} wants {'H and G' if G else 'H'} [8, {N}, 256], got {got}")
+    if tuple(g_heads.shape) != (N, sum(rows)):
+        raise ValueError(f"{who} wants g_heads [{N}, {sum(rows)}], got {tuple(g_heads.shape)}")
+    want = [True] * (16 + 2 * n) if want is None else [bool(w) for w in want]
+    if len(want) != 16 + 2 * n:
+        raise ValueError(f"{who}: want has {len(want)} entries for {16 + 2 * n} gradients")
+    return N, rows, want
+
+
+def _mlp_grad_shapes(aux_width: int, rows):
+    """The parameter gradients' shapes in the order of ``_MlpTrain``'s ``params`` (layer 0 takes the encoded row, layer 5 the skip)."""
+    in_ch = 63 + aux_width
+    shapes = [(256, in_ch if l == 0 else (in_ch + 256 if l == 5 else 256)) for l in range(8)] + [(256,)] * 8
+    return shapes + [(r, 256) for r in rows] + [(r,) for r in rows]
+
+
+def _mlp_grad_outs(shapes, want, N: int, dev):
+    """One array per wanted gradient, ``None`` for the others (N = 0: the sums over no rows)."""
+    return [(torch.zeros if N == 0 else torch.empty)(s, dtype=torch.float32, device=dev) if w else None for s, w in zip(shapes, want)]
+
+
+def _mlp_grads_struct(outs, n: int):
+    """The ``fg_mlp_grads`` that points into ``outs`` (``n`` heads); a gradient that is not wanted stays null."""
+    g = _lib.MlpGrads()
+    g.size = ctypes.sizeof(_lib.MlpGrads)
+    for i in range(8):
+        g.weight[i], g.bias[i] = _ptr(outs[i]), _ptr(outs[8 + i])
+    for i in range(n):
+        g.head_weight[i], g.head_bias[i] = _ptr(outs[16 + i]), _ptr(outs[16 + n + i])
+    return g
+
+
 def mlp_param_grads(enc: torch.Tensor, H: torch.Tensor, G: torch.Tensor, g_heads: torch.Tensor, aux_width: int, head_rows,
                     want=None, precision: str = "fp32"):
     """The parameter gradients of the fused training path in one call (``fg_mlp_param_grads``): from ``enc``
@@ -1458,39 +1512,16 @@ def mlp_param_grads(enc: torch.Tensor, H: torch.Tensor, G: torch.Tensor, g_heads
     include/fgraster.h: three bf16 products for one, slabs, order and workspace unchanged; biases fp32 sums, head gradients
     the fp32 mode's bits).  CUDA float32 contiguous tensors; no host synchronisation: capturable."""
     prec = _mlp_precision("mlp_param_grads", precision)
-    tensors = (enc, H, G, g_heads)
-    if any(not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() for t in tensors):
-        raise ValueError("mlp_param_grads wants contiguous CUDA float32 tensors")
-    rows = [int(r) for r in head_rows]
-    n = len(rows)
-    if not 1 <= aux_width <= 64 or not 1 <= n <= _lib.MLP_MAX_HEADS or min(rows) < 1 or sum(rows) > 16:
-        raise ValueError(f"mlp_param_grads: aux width {aux_width} / head rows {rows} outside what the kernels take")
-    N, in_ch = enc.shape[0], 63 + aux_width
-    if enc.dim() != 2 or enc.shape[1] != _lib.mlp_enc_width(aux_width):
-        raise ValueError(f"mlp_param_grads wants enc [N, {_lib.mlp_enc_width(aux_width)}], got {tuple(enc.shape)}")
-    if tuple(H.shape) != (8, N, 256) or G.shape != H.shape:
-        raise ValueError(f"mlp_param_grads wants H and G [8, {N}, 256], got {tuple(H.shape)} and {tuple(G.shape)}")
-    if tuple(g_heads.shape) != (N, sum(rows)):
-        raise ValueError(f"mlp_param_grads wants g_heads [{N}, {sum(rows)}], got {tuple(g_heads.shape)}")
-    want = [True] * (16 + 2 * n) if want is None else [bool(w) for w in want]
-    if len(want) != 16 + 2 * n:
-        raise ValueError(f"mlp_param_grads: want has {len(want)} entries for {16 + 2 * n} gradients")
-    shapes = [(256, in_ch if l == 0 else (in_ch + 256 if l == 5 else 256)) for l in range(8)] + [(256,)] * 8
-    shapes += [(r, 256) for r in rows] + [(r,) for r in rows]
-    dev = enc.device
-    # (N = 0: the sums over no rows)
-    outs = [(torch.zeros if N == 0 else torch.empty)(s, dtype=torch.float32, device=dev) if w else None for s, w in zip(shapes, want)]
+    N, rows, want = _mlp_grad_args("mlp_param_grads", (enc, H, G, g_heads), aux_width, head_rows, want)
+    n, dev = len(rows), enc.device
+    outs = _mlp_grad_outs(_mlp_grad_shapes(aux_width, rows), want, N, dev)
     if N > 0 and any(want):
-        d, g = _lib.MlpDesc(), _lib.MlpGrads()
+        d = _lib.MlpDesc()
         d.size, d.mode, d.depth, d.width, d.multires = ctypes.sizeof(_lib.MlpDesc), _lib.MLP_PLAIN, 8, 256, 10
         d.aux_width, d.n_heads = aux_width, n
-        g.size = ctypes.sizeof(_lib.MlpGrads)
         for i, r in enumerate(rows):
             d.head_rows[i] = r
-        for i in range(8):
-            g.weight[i], g.bias[i] = _ptr(outs[i]), _ptr(outs[8 + i])
-        for i in range(n):
-            g.head_weight[i], g.head_bias[i] = _ptr(outs[16 + i]), _ptr(outs[16 + n + i])
+        g = _mlp_grads_struct(outs, n)
         with torch.cuda.device(dev):
             ws = torch.empty(int(_lib.load().fg_mlp_param_grads_workspace_bytes(N)), dtype=torch.uint8, device=dev)
             if prec == _lib.MLP_FP32:
@@ -1527,42 +1558,16 @@ def mlp_train_backward(enc: torch.Tensor, H: torch.Tensor, g_heads: torch.Tensor
     float32 contiguous tensors; no host synchronisation: capturable."""
     prec = _mlp_precision("mlp_train_backward", precision)
     wprec = _mlp_precision("mlp_train_backward", param_grads_precision)
-    tensors = (enc, H, g_heads)
-    if any(not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() for t in tensors):
-        raise ValueError("mlp_train_backward wants contiguous CUDA float32 tensors")
-    rows = [int(r) for r in head_rows]
-    n = len(rows)
-    if not 1 <= aux_width <= 64 or not 1 <= n <= _lib.MLP_MAX_HEADS or min(rows) < 1 or sum(rows) > 16:
-        raise ValueError(f"mlp_train_backward: aux width {aux_width} / head rows {rows} outside what the kernels take")
-    if not isinstance(chunk_slabs, int) or isinstance(chunk_slabs, bool) or chunk_slabs < 0:
-        raise ValueError(f"mlp_train_backward: chunk_slabs wants an int >= 0, got {chunk_slabs!r}")
-    N, in_ch = enc.shape[0], 63 + aux_width
-    if enc.dim() != 2 or enc.shape[1] != _lib.mlp_enc_width(aux_width):
-        raise ValueError(f"mlp_train_backward wants enc [N, {_lib.mlp_enc_width(aux_width)}], got {tuple(enc.shape)}")
-    if tuple(H.shape) != (8, N, 256):
-        raise ValueError(f"mlp_train_backward wants H [8, {N}, 256], got {tuple(H.shape)}")
-    if tuple(g_heads.shape) != (N, sum(rows)):
-        raise ValueError(f"mlp_train_backward wants g_heads [{N}, {sum(rows)}], got {tuple(g_heads.shape)}")
-    want = [True] * (16 + 2 * n) if want is None else [bool(w) for w in want]
-    if len(want) != 16 + 2 * n:
-        raise ValueError(f"mlp_train_backward: want has {len(want)} entries for {16 + 2 * n} gradients")
+    N, rows, want = _mlp_grad_args("mlp_train_backward", (enc, H, g_heads), aux_width, head_rows, want, chunk_slabs)
     d, _, desc_rows, keep = _mlp_desc("mlp_train_backward", None, aux_width, trunk, heads, _lib.MLP_PLAIN)
     d.precision = prec
     if desc_rows != rows:
         raise ValueError(f"mlp_train_backward: head rows {rows} are not the heads' {desc_rows}")
-    shapes = [(256, in_ch if l == 0 else (in_ch + 256 if l == 5 else 256)) for l in range(8)] + [(256,)] * 8
-    shapes += [(r, 256) for r in rows] + [(r,) for r in rows]
-    dev = enc.device
-    # (N = 0: the sums over no rows)
-    outs = [(torch.zeros if N == 0 else torch.empty)(s, dtype=torch.float32, device=dev) if w else None for s, w in zip(shapes, want)]
+    n, dev = len(rows), enc.device
+    outs = _mlp_grad_outs(_mlp_grad_shapes(aux_width, rows), want, N, dev)
     g_enc = torch.empty_like(enc) if want_g_enc else None
     if N > 0 and (any(want) or want_g_enc):
-        g = _lib.MlpGrads()
-        g.size = ctypes.sizeof(_lib.MlpGrads)
-        for i in range(8):
-            g.weight[i], g.bias[i] = _ptr(outs[i]), _ptr(outs[8 + i])
-        for i in range(n):
-            g.head_weight[i], g.head_bias[i] = _ptr(outs[16 + i]), _ptr(outs[16 + n + i])
+        g = _mlp_grads_struct(outs, n)
         with torch.cuda.device(dev):
             need = int(_lib.load().fg_mlp_train_bwd_workspace_bytes(N, chunk_slabs, int(bool(want_g_enc))))
             ws = torch.empty(need, dtype=torch.uint8, device=dev)
@@ -1573,6 +1578,11 @@ def mlp_train_backward(enc: torch.Tensor, H: torch.Tensor, g_heads: torch.Tensor
                 _call("fg_mlp_train_bwd_p", N, ctypes.addressof(d), _ptr(g_heads), _ptr(enc), _ptr(H), _ptr(g_enc), ctypes.addressof(g),
                       chunk_slabs, wprec, _ptr(ws), ws.numel(), _stream())  # fmt: skip
     return tuple(outs[:8]), tuple(outs[8:16]), tuple(outs[16 : 16 + n]), tuple(outs[16 + n :]), g_enc
+
+
+def _mlp_train_grads(g_x, g_aux, param_grads):
+    """``_MlpTrain.backward``'s result: one entry per input of ``forward`` (``x``, ``aux``, six that are no tensors, the parameters)."""
+    return (g_x, g_aux, None, None, None, None, None, None, *param_grads)
 
 
 class _MlpTrain(torch.autograd.Function):
@@ -1626,7 +1636,7 @@ class _MlpTrain(torch.autograd.Function):
                                                          **wkw)  # fmt: skip
             if g_enc is not None:
                 g_x, g_aux = mlp_input_grads(g_enc, enc, ctx.aux_width, want_x, want_aux, ctx.one_row_aux)
-            return (g_x, g_aux, None, None, None, None, None, None, *gW, *gb, *gWh, *gbh)
+            return _mlp_train_grads(g_x, g_aux, (*gW, *gb, *gWh, *gbh))
         G = torch.empty_like(H)
         with torch.cuda.device(G.device):
             if want_x or want_aux:
@@ -1641,10 +1651,10 @@ class _MlpTrain(torch.autograd.Function):
         if ctx.fused_param_grads:
             gW, gb, gWh, gbh = mlp_param_grads(enc, H, G, g_heads, ctx.aux_width, rows, want=ctx.needs_input_grad[8:],
                                                **({"precision": wkw["param_grads_precision"]} if wkw else {}))
-            return (g_x, g_aux, None, None, None, None, None, None, *gW, *gb, *gWh, *gbh)
+            return _mlp_train_grads(g_x, g_aux, (*gW, *gb, *gWh, *gbh))
         gW, gb, gWh, gbh = deform.mlp_param_grads(enc[:, : 63 + ctx.aux_width], H, G, g_heads, rows)
         grads = (*gW, *gb, *gWh, *gbh)
-        return (g_x, g_aux, None, None, None, None, None, None, *(g if need else None for g, need in zip(grads, ctx.needs_input_grad[8:])))
+        return _mlp_train_grads(g_x, g_aux, (g if need else None for g, need in zip(grads, ctx.needs_input_grad[8:])))
 
 
 def mlp_train(x: torch.Tensor, aux: torch.Tensor, trunk, heads, input_grads: bool = False,
@@ -1685,10 +1695,7 @@ def mlp_train(x: torch.Tensor, aux: torch.Tensor, trunk, heads, input_grads: boo
             raise ValueError(f"mlp_train: chunked_backward wants True or a positive int, got {chunked_backward!r}")
         if not fused_param_grads:
             raise ValueError("mlp_train: chunked_backward forms the fused parameter gradients; pass fused_param_grads=True")
-    trunk = [(m.weight, m.bias) if hasattr(m, "weight") else tuple(m) for m in trunk]
-    heads = [(m.weight, m.bias) if hasattr(m, "weight") else tuple(m) for m in heads]
-    if len(trunk) != 8 or not 1 <= len(heads) <= _lib.MLP_MAX_HEADS:
-        raise ValueError(f"mlp_train wants 8 trunk layers and 1..{_lib.MLP_MAX_HEADS} heads, got {len(trunk)} and {len(heads)}")
+    trunk, heads = _mlp_layers("mlp_train", trunk, heads)
     tensors = [x, aux, *(t for pair in (*trunk, *heads) for t in pair)]
     if any(not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 for t in tensors):
         raise ValueError("mlp_train wants CUDA float32 tensors (and a bias on every layer)")

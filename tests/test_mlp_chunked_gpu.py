@@ -21,14 +21,13 @@ from freegaussian_amd import _lib
 from freegaussian_amd import deform as D
 from freegaussian_amd import ops
 from helpers import REL_TOL, rel_err
+from mlp_common import GUARD, NAN, arena, flat, lib_calls, module_inputs, module_step, named_grads, out_shapes
 from mlp_inputs_common import BLENDER_TIME, clear_inputs, float64_with_input_row, make_net
-from mlp_train_common import cotangents, head_rows, heads_of, loss_of
+from mlp_train_common import cotangents, head_rows, heads_of
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
-NAN = float("nan")
-GUARD = 1024
 ROWS4 = (3, 3, 4, 3)
 
 
@@ -87,10 +86,6 @@ def _case(A, rows, n):
     return enc[:n].contiguous(), H[:, :n].contiguous(), gh[:n].contiguous()
 
 
-def _flat(grads4):
-    return [t for group in grads4 for t in group]
-
-
 def _two_calls(A, rows, n, g_enc, want=None):
     """``fg_mlp_bwd`` (``fg_mlp_bwd_inputs`` where ``g_enc``) into a whole G, then ``ops.mlp_param_grads``:
     (flat gradients, g_enc or None)."""
@@ -108,7 +103,7 @@ def _two_calls(A, rows, n, g_enc, want=None):
         ge = None
         ws = torch.empty(int(lib.fg_mlp_train_workspace_bytes(n)), dtype=torch.uint8, device=DEV)
         ops._call("fg_mlp_bwd", n, ctypes.addressof(d), gh.data_ptr(), H.data_ptr(), G.data_ptr(), ws.data_ptr(), ws.numel(), ops._stream())
-    return _flat(ops.mlp_param_grads(enc, H, G, gh, A, rows, want=want)), ge
+    return flat(ops.mlp_param_grads(enc, H, G, gh, A, rows, want=want)), ge
 
 
 def _reference(A, rows, n, g_enc):
@@ -125,7 +120,7 @@ def _chunked(A, rows, n, g_enc, chunk_slabs, want=None):
     enc, H, gh = _case(A, rows, n)
     trunk, heads = _net(A, rows)
     *grads4, ge = ops.mlp_train_backward(enc, H, gh, trunk, heads, A, rows, want=want, want_g_enc=g_enc, chunk_slabs=chunk_slabs)
-    return _flat(grads4), ge
+    return flat(grads4), ge
 
 
 def _chunkings(n):
@@ -187,20 +182,6 @@ def test_outputs_left_out(group, g_enc):
 
 
 # ---- 3. guarded buffers ---------------------------------------------------------------------------------------------------
-def _arena(*shape):
-    numel = 1
-    for s in shape:
-        numel *= s
-    flat = torch.full((numel + 2 * GUARD,), NAN, device=DEV)
-    return flat, flat[GUARD : GUARD + numel].view(*shape)
-
-
-def _out_shapes(A, rows):
-    in_ch = 63 + A
-    return ([(256, in_ch if l == 0 else (in_ch + 256 if l == 5 else 256)) for l in range(8)] + [(256,)] * 8
-            + [(r, 256) for r in rows] + [(r,) for r in rows])  # fmt: skip
-
-
 @pytest.mark.parametrize("g_enc", [True, False])
 def test_guarded_buffers(g_enc):
     """Every array in an allocation of its own between NaN bands: enc, acts and g_heads end at row N - 1 (what follows them is
@@ -208,14 +189,14 @@ def test_guarded_buffers(g_enc):
     unguarded run's."""
     A, rows, n, c = 30, ROWS4, 5000, 3
     k = len(rows)
-    ins = [_arena(*t.shape) for t in _case(A, rows, n)]
+    ins = [arena(*t.shape) for t in _case(A, rows, n)]
     for (_, view), t in zip(ins, _case(A, rows, n)):
         view.copy_(t)
     ins[0][1][:, 63 + A :] = NAN
     before = [flat.clone() for flat, _ in ins]
     (_, enc), (_, H), (_, gh) = ins
-    outs = [_arena(*s) for s in _out_shapes(A, rows)]
-    ge_flat, ge = _arena(n, _lib.mlp_enc_width(A))
+    outs = [arena(*s) for s in out_shapes(A, rows)]
+    ge_flat, ge = arena(n, _lib.mlp_enc_width(A))
     trunk, heads = _net(A, rows)
     d, _, _, keep = ops._mlp_desc("test", None, A, trunk, heads, _lib.MLP_PLAIN)
     g = _lib.MlpGrads()
@@ -226,7 +207,7 @@ def test_guarded_buffers(g_enc):
         g.head_weight[i], g.head_bias[i] = outs[16 + i][1].data_ptr(), outs[16 + k + i][1].data_ptr()
     need = int(_lib.load().fg_mlp_train_bwd_workspace_bytes(n, c, int(g_enc)))
     assert need % 4 == 0
-    ws_flat, ws = _arena(need // 4)
+    ws_flat, ws = arena(need // 4)
     ops._call("fg_mlp_train_bwd", n, ctypes.addressof(d), gh.data_ptr(), enc.data_ptr(), H.data_ptr(), ge.data_ptr() if g_enc else None,
               ctypes.addressof(g), c, ws.data_ptr(), need, ops._stream())  # fmt: skip
     torch.cuda.synchronize()
@@ -250,20 +231,7 @@ def test_two_calls_are_bitwise_equal():
 @pytest.fixture
 def spy(monkeypatch):
     """The library calls of the backward, by name."""
-    seen = []
-    real_call = ops._call
-
-    def call(name, *a, **k):
-        if name in ("fg_mlp_train_bwd", "fg_mlp_bwd", "fg_mlp_bwd_inputs", "fg_mlp_param_grads"):
-            seen.append(name)
-        return real_call(name, *a, **k)
-
-    monkeypatch.setattr(ops, "_call", call)
-    return seen
-
-
-def _grads_of(m):
-    return {k: (None if p.grad is None else p.grad.detach().clone()) for k, p in m.named_parameters()}
+    return lib_calls(monkeypatch, ("fg_mlp_train_bwd", "fg_mlp_bwd", "fg_mlp_bwd_inputs", "fg_mlp_param_grads"))
 
 
 def test_capture_and_replay_equal_the_eager_call(spy):
@@ -283,7 +251,7 @@ def test_capture_and_replay_equal_the_eager_call(spy):
 
     raw_e = step().clone()
     assert spy == ["fg_mlp_train_bwd"]
-    eager = dict(g_x=x.grad.clone(), g_aux=aux.grad.clone(), params={k: v for k, v in _grads_of(m).items() if v is not None})
+    eager = dict(g_x=x.grad.clone(), g_aux=aux.grad.clone(), params={k: v for k, v in named_grads(m).items() if v is not None})
     assert len(eager["params"]) == 24 and float(eager["g_x"].abs().max()) > 0
     torch.cuda.synchronize()
     graph = torch.cuda.CUDAGraph()
@@ -314,7 +282,7 @@ def test_blender_net_through_mlp_train_against_float64(spy):
     raw = ops.mlp_train(xd, ad, m_dev.linear, heads_of(m_dev), input_grads=True, fused_param_grads=True, chunked_backward=3)
     raw.backward(g_heads.to(DEV))
     assert spy == ["fg_mlp_train_bwd"]
-    got = _grads_of(m_dev)
+    got = named_grads(m_dev)
     errs = {k: rel_err(got[k], w) for k, w in want.items()}
     errs["g_x"], errs["g_aux"], errs["raw"] = rel_err(xd.grad, ref["g_x"]), rel_err(ad.grad, ref["g_aux"]), rel_err(raw, ref["raw"])
     print("mlp_chunked blender n=5000 chunk_slabs=3 against float64: " + ", ".join(f"{k} {v:.2e}" for k, v in errs.items()))
@@ -324,23 +292,11 @@ def test_blender_net_through_mlp_train_against_float64(spy):
 
 
 # ---- 6. through the modules and the model ---------------------------------------------------------------------------------
-def _module_inputs(kind, n, seed=1):
-    g = torch.Generator().manual_seed(seed)
-    x = torch.rand(n, 3, generator=g) * 2 - 1
-    return x, (torch.randn(n, 3, generator=g) * 0.1 if kind == "control" else torch.rand(n, 1, generator=g))
-
-
-def _module_step(m_dev, x, other, cots):
-    m_dev.zero_grad(set_to_none=True)
-    loss_of(m_dev(x, other), cots).backward()
-    return _grads_of(m_dev)
-
-
 @pytest.mark.parametrize("kind,train", [("deform", "1"), ("control", "1"), ("blender", "2"), ("deform", "2")])
 def test_modules_with_the_knob_set_and_unset(kind, train, spy, monkeypatch):
     n = D.FUSED_MIN_ROWS
     m = make_net(kind)
-    x, other = _module_inputs(kind, n, seed=4)
+    x, other = module_inputs(kind, n, seed=4)
     if kind == "blender":
         other = torch.full((1, 1), BLENDER_TIME).expand(n, -1)
     m_dev = copy.deepcopy(m).to(DEV)
@@ -348,10 +304,10 @@ def test_modules_with_the_knob_set_and_unset(kind, train, spy, monkeypatch):
     monkeypatch.setenv("FG_FUSED_MLP_TRAIN", train)
     monkeypatch.setenv("FG_FUSED_MLP_WGRAD", "1")
     monkeypatch.delenv("FG_FUSED_MLP_CHUNKED", raising=False)
-    off = _module_step(m_dev, xd, od, cots)
+    off = module_step(m_dev, xd, od, cots)
     assert spy == ["fg_mlp_bwd_inputs" if kind == "blender" else "fg_mlp_bwd", "fg_mlp_param_grads"]
     monkeypatch.setenv("FG_FUSED_MLP_CHUNKED", "1")
-    on = _module_step(m_dev, xd, od, cots)
+    on = module_step(m_dev, xd, od, cots)
     assert spy[2:] == ["fg_mlp_train_bwd"]
     assert len(off) == 2 * (8 + len(head_rows(m))) + (4 if kind == "blender" else 0) and set(on) == set(off)
     for k in off:
@@ -360,14 +316,14 @@ def test_modules_with_the_knob_set_and_unset(kind, train, spy, monkeypatch):
     frozen = [heads_of(m_dev)[1].weight, heads_of(m_dev)[1].bias, m_dev.linear[3].bias]
     for p in frozen:
         p.requires_grad_(False)
-    part = _module_step(m_dev, xd, od, cots)
+    part = module_step(m_dev, xd, od, cots)
     names = {id(p): k for k, p in m_dev.named_parameters()}
     for k in on:
         assert (part[k] is None) if k in [names[id(p)] for p in frozen] else torch.equal(part[k], on[k]), k
     # without the parameter-gradient knob the new one does nothing
     monkeypatch.delenv("FG_FUSED_MLP_WGRAD")
     del spy[:]
-    _module_step(m_dev, xd, od, cots)
+    module_step(m_dev, xd, od, cots)
     assert "fg_mlp_train_bwd" not in spy and len(spy) == 1
 
 

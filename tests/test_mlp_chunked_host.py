@@ -11,48 +11,24 @@ import torch
 from freegaussian_amd import _lib
 from freegaussian_amd import deform as D
 from freegaussian_amd import ops
+from mlp_common import PTR, addr, desc, grads, header_text, stand_in_for_cuda
 
 OK, INVALID, WORKSPACE, UNSUPPORTED = 0, -1, -3, -4
-PTR, BIG = 4096, 1 << 40  # an address nobody reads (every call below is refused before a launch); a workspace that would do
-HEADER = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "include", "fgraster.h")
+BIG = 1 << 40  # a workspace that would do (every call below is refused before a launch)
 SIZES = (1, 512, 513, 5000, 33_000, 240_000, 1_000_000)
 BLOCK = 4 * (7 * 256 * 256 + 2 * 256 * 128 + 8 * 256 + 16 * 256 + 16)  # one slab's partial results: 2 121 792 bytes
-
-
-def _desc(mode=_lib.MLP_PLAIN, A=21, rows=(3, 3, 4, 3), weights=True):
-    """The shape and, as the chain reads them, the weight pointers; x / aux / out stay null."""
-    d = _lib.MlpDesc()
-    d.size, d.mode, d.depth, d.width, d.multires, d.aux_width = ctypes.sizeof(_lib.MlpDesc), mode, 8, 256, 10, A
-    d.n_heads = len(rows)
-    for i, r in enumerate(rows):
-        d.head_rows[i] = r
-        if weights:
-            d.head_weight[i], d.head_bias[i] = PTR, PTR
-    for l in range(8 if weights else 0):
-        d.weight[l], d.bias[l] = PTR, PTR
-    return d
-
-
-def _grads(weight=range(8), bias=range(8), head_weight=range(4), head_bias=range(4)):
-    g = _lib.MlpGrads()
-    g.size = ctypes.sizeof(_lib.MlpGrads)
-    for name, which in (("weight", weight), ("bias", bias), ("head_weight", head_weight), ("head_bias", head_bias)):
-        for i in which:
-            getattr(g, name)[i] = PTR
-    return g
 
 
 NOTHING = ((), (), (), ())
 
 
 def _call(n, d, g_heads=PTR, enc=PTR, acts=PTR, g_enc=PTR, out="all", chunk_slabs=0, ws=PTR, ws_bytes=0):
-    out = _grads() if isinstance(out, str) else out
-    return _lib.load().fg_mlp_train_bwd(n, ctypes.addressof(d) if d is not None else None, g_heads, enc, acts, g_enc,
-                                        ctypes.addressof(out) if out is not None else None, chunk_slabs, ws, ws_bytes, None)  # fmt: skip
+    out = grads() if isinstance(out, str) else out
+    return _lib.load().fg_mlp_train_bwd(n, addr(d), g_heads, enc, acts, g_enc, addr(out), chunk_slabs, ws, ws_bytes, None)
 
 
 def test_header_and_binding_agree():
-    text = open(HEADER).read()
+    text = header_text()
     lib = _lib.load()
     assert "#define FG_ABI_VERSION 14" in text and _lib.ABI_VERSION == 14 and lib.fg_abi_version() == 14
     assert re.search(r"^#define FG_ABI_MINOR 1\b", text, flags=re.M) and _lib.ABI_MINOR == 1 and lib.fg_abi_minor() >= 1
@@ -126,72 +102,59 @@ def test_workspace_is_the_documented_sum_and_does_not_grow_with_the_array():
 
 def test_error_codes_without_gpu():
     assert _call(0, None, None, None, None, None, None, 0, None, 0) == OK  # N = 0: nothing to do, nothing is looked at
-    assert _call(0, _desc(A=0), chunk_slabs=-1) == OK
-    assert _call(-1, _desc()) == INVALID
+    assert _call(0, desc(A=0), chunk_slabs=-1) == OK
+    assert _call(-1, desc()) == INVALID
     assert _call(100, None) == INVALID
-    assert _call(100, _desc(), chunk_slabs=-1, ws_bytes=BIG) == INVALID
+    assert _call(100, desc(), chunk_slabs=-1, ws_bytes=BIG) == INVALID
     # everything in order but the workspace's size
-    assert _call(100, _desc()) == WORKSPACE
-    assert _call(100, _desc(A=63, rows=(3, 4, 3))) == WORKSPACE and _call(100, _desc(A=1, rows=(16,))) == WORKSPACE
-    assert _call(100, _desc(A=64, rows=(1,)), g_enc=None) == WORKSPACE
+    assert _call(100, desc()) == WORKSPACE
+    assert _call(100, desc(A=63, rows=(3, 4, 3))) == WORKSPACE and _call(100, desc(A=1, rows=(16,))) == WORKSPACE
+    assert _call(100, desc(A=64, rows=(1,)), g_enc=None) == WORKSPACE
     # the chain reads the weights: a descriptor without them is refused (fg_mlp_param_grads alone accepts it)
-    assert _call(100, _desc(weights=False), ws_bytes=BIG) == INVALID
+    assert _call(100, desc(weights=False), ws_bytes=BIG) == INVALID
     for field in ("weight", "bias", "head_weight", "head_bias"):
-        d = _desc()
+        d = desc()
         getattr(d, field)[2] = None
         assert _call(100, d, ws_bytes=BIG) == INVALID, field
-    d = _desc()
+    d = desc()
     d.size -= 8
     assert _call(100, d, ws_bytes=BIG) == INVALID
-    assert _call(100, _desc(mode=_lib.MLP_SE3), ws_bytes=BIG) == INVALID and _call(100, _desc(mode=7), ws_bytes=BIG) == INVALID
+    assert _call(100, desc(mode=_lib.MLP_SE3), ws_bytes=BIG) == INVALID and _call(100, desc(mode=7), ws_bytes=BIG) == INVALID
     for A in (0, 65):
-        assert _call(100, _desc(A=A), ws_bytes=BIG) == INVALID
+        assert _call(100, desc(A=A), ws_bytes=BIG) == INVALID
     for rows in ((0,), (17,), (8, 9)):
-        assert _call(100, _desc(rows=rows), ws_bytes=BIG) == INVALID
+        assert _call(100, desc(rows=rows), ws_bytes=BIG) == INVALID
     for field, value in (("depth", 6), ("width", 128), ("multires", 6)):
-        d = _desc()
+        d = desc()
         setattr(d, field, value)
         assert _call(100, d, ws_bytes=BIG) == UNSUPPORTED, field
     # out: null, a wrong size field
-    assert _call(100, _desc(), out=None, ws_bytes=BIG) == INVALID
-    g = _grads()
+    assert _call(100, desc(), out=None, ws_bytes=BIG) == INVALID
+    g = grads()
     g.size -= 8
-    assert _call(100, _desc(), out=g, ws_bytes=BIG) == INVALID
+    assert _call(100, desc(), out=g, ws_bytes=BIG) == INVALID
     # nothing asked for at all: FG_OK whatever else is null; with g_enc wanted the chunks run, so the chain's inputs are needed
-    assert _call(100, _desc(), None, None, None, None, out=_grads(*NOTHING), ws=None, ws_bytes=0) == OK
-    assert _call(100, _desc(), enc=None, out=_grads(*NOTHING)) == WORKSPACE  # (g_enc alone reads no enc)
-    assert _call(100, _desc(), g_heads=None, out=_grads(*NOTHING), ws_bytes=BIG) == INVALID
-    assert _call(100, _desc(), acts=None, out=_grads(*NOTHING), ws_bytes=BIG) == INVALID
+    assert _call(100, desc(), None, None, None, None, out=grads(*NOTHING), ws=None, ws_bytes=0) == OK
+    assert _call(100, desc(), enc=None, out=grads(*NOTHING)) == WORKSPACE  # (g_enc alone reads no enc)
+    assert _call(100, desc(), g_heads=None, out=grads(*NOTHING), ws_bytes=BIG) == INVALID
+    assert _call(100, desc(), acts=None, out=grads(*NOTHING), ws_bytes=BIG) == INVALID
     # g_heads and acts are read whatever is asked for, enc where weight[0] / weight[5] is
-    only = lambda **kw: _grads(**{**dict(zip(("weight", "bias", "head_weight", "head_bias"), NOTHING)), **kw})  # noqa: E731
+    only = lambda **kw: grads(**{**dict(zip(("weight", "bias", "head_weight", "head_bias"), NOTHING)), **kw})  # noqa: E731
     for out in ("all", only(bias=(3,)), only(head_bias=(1,))):
-        assert _call(100, _desc(), g_heads=None, out=out, g_enc=None, ws_bytes=BIG) == INVALID
-        assert _call(100, _desc(), acts=None, out=out, g_enc=None, ws_bytes=BIG) == INVALID
-    assert _call(100, _desc(), enc=None, out=_grads(weight=(1, 2, 3, 4, 6, 7))) == WORKSPACE
-    assert _call(100, _desc(), enc=None, out=only(weight=(0,)), ws_bytes=BIG) == INVALID
-    assert _call(100, _desc(), enc=None, out=only(weight=(5,)), ws_bytes=BIG) == INVALID
-    assert _call(100, _desc(), enc=None, ws_bytes=BIG) == INVALID
+        assert _call(100, desc(), g_heads=None, out=out, g_enc=None, ws_bytes=BIG) == INVALID
+        assert _call(100, desc(), acts=None, out=out, g_enc=None, ws_bytes=BIG) == INVALID
+    assert _call(100, desc(), enc=None, out=grads(weight=(1, 2, 3, 4, 6, 7))) == WORKSPACE
+    assert _call(100, desc(), enc=None, out=only(weight=(0,)), ws_bytes=BIG) == INVALID
+    assert _call(100, desc(), enc=None, out=only(weight=(5,)), ws_bytes=BIG) == INVALID
+    assert _call(100, desc(), enc=None, ws_bytes=BIG) == INVALID
     # no workspace, one that is not 16-byte aligned, one a byte short (with and without g_enc, for more than one chunk length)
-    assert _call(100, _desc(), ws=None, ws_bytes=BIG) == INVALID
-    assert _call(100, _desc(), ws=PTR + 4, ws_bytes=BIG) == INVALID
+    assert _call(100, desc(), ws=None, ws_bytes=BIG) == INVALID
+    assert _call(100, desc(), ws=PTR + 4, ws_bytes=BIG) == INVALID
     lib = _lib.load()
     for n, c, g_enc in ((100, 0, PTR), (100, 0, None), (5000, 3, PTR), (5000, 1, None), (5000, 99, PTR)):
         need = int(lib.fg_mlp_train_bwd_workspace_bytes(n, c, int(g_enc is not None)))
-        assert need > 0 and _call(n, _desc(), g_enc=g_enc, chunk_slabs=c, ws_bytes=need - 1) == WORKSPACE, (n, c)
+        assert need > 0 and _call(n, desc(), g_enc=g_enc, chunk_slabs=c, ws_bytes=need - 1) == WORKSPACE, (n, c)
     assert int(lib.fg_mlp_train_bwd_workspace_bytes(5000, 3, 1)) > int(lib.fg_mlp_train_bwd_workspace_bytes(5000, 3, 0))
-
-
-def _stand_in_for_cuda(monkeypatch):
-    """``ops.mlp_train`` replaced by a spy that returns zeros, tensors that report CUDA: the dispatch alone, on the CPU."""
-    seen = []
-
-    def fake(x, aux, trunk, heads, **kw):
-        seen.append(kw)
-        return torch.zeros(x.shape[0], sum(h.weight.shape[0] for h in heads)) + 0.0 * trunk[0].bias.sum()
-
-    monkeypatch.setattr(ops, "mlp_train", fake)
-    monkeypatch.setattr(torch.Tensor, "is_cuda", property(lambda self: True))
-    return seen
 
 
 def _nets():
@@ -200,7 +163,7 @@ def _nets():
 
 
 def test_knob_in_the_dispatch(monkeypatch):
-    seen = _stand_in_for_cuda(monkeypatch)
+    seen = stand_in_for_cuda(monkeypatch)
     n = D.FUSED_MIN_ROWS
     x, t, v = torch.rand(n, 3), torch.rand(n, 1), torch.rand(n, 3)
     other = lambda m: v if isinstance(m, D.FreeGaussianControllableModel) else t  # noqa: E731

@@ -18,6 +18,7 @@ from freegaussian_amd import deform as D
 from freegaussian_amd import ops
 from freegaussian_amd.utils import transform_points
 from helpers import REL_TOL, close_except_knife_edge, rel_err
+from mlp_common import NAN
 
 pytestmark = pytest.mark.gpu
 
@@ -29,7 +30,6 @@ DEV = "cuda"
 M = ops.MLP_ROW_TILE
 SIZES = [1, M - 1, M, M + 1, 2 * M + 3, 1000, 33_000]
 N_MAX = max(SIZES)
-NAN = float("nan")
 
 
 def _gold(k):

@@ -12,6 +12,7 @@ import torch
 from freegaussian_amd import _lib
 from freegaussian_amd import deform as D
 from freegaussian_amd import ops
+from mlp_common import PTR, addr, desc, header_text
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 sys.path.insert(0, GOLD)
@@ -20,26 +21,18 @@ from make_golden import fill_params  # noqa: E402  (pure helper)
 OK, INVALID, WORKSPACE, UNSUPPORTED = 0, -1, -3, -4
 
 
-def _desc(mode=_lib.MLP_SE3, A=21, head_rows=(3, 3, 4, 3), ptr=4096):
+def _desc(mode=_lib.MLP_SE3, A=21, head_rows=(3, 3, 4, 3), ptr=PTR):
     """A descriptor whose pointers are set to an address nobody reads (every call below is refused before a launch)."""
-    d = _lib.MlpDesc()
-    d.size, d.mode, d.depth, d.width, d.multires, d.aux_width = ctypes.sizeof(_lib.MlpDesc), mode, 8, 256, 10, A
-    d.n_heads = len(head_rows)
-    for i, r in enumerate(head_rows):
-        d.head_rows[i], d.head_weight[i], d.head_bias[i], d.out[i] = r, ptr, ptr, ptr
-    d.aux_stride, d.x, d.aux = A, ptr, ptr
-    for i in range(8):
-        d.weight[i], d.bias[i] = ptr, ptr
-    return d
+    return desc(mode, A, head_rows, inputs=True, outs=True, ptr=ptr)
 
 
-def _fwd(n, d, ws=4096, ws_bytes=0):
+def _fwd(n, d, ws=PTR, ws_bytes=0):
     """(workspace_bytes = 0: a descriptor that passes every other check still stops at FG_ERR_WORKSPACE)"""
-    return _lib.load().fg_mlp_fwd(n, ctypes.addressof(d) if d is not None else None, ws, ws_bytes, None)
+    return _lib.load().fg_mlp_fwd(n, addr(d), ws, ws_bytes, None)
 
 
 def test_descriptor_matches_the_header():
-    text = open(os.path.join(os.path.dirname(GOLD), "..", "include", "fgraster.h")).read()
+    text = header_text()
     for name, value in (("FG_MLP_ROW_TILE", _lib.MLP_ROW_TILE), ("FG_MLP_MAX_HEADS", _lib.MLP_MAX_HEADS),
                         ("FG_MLP_SE3", _lib.MLP_SE3), ("FG_MLP_PLAIN", _lib.MLP_PLAIN)):  # fmt: skip
         assert f"#define {name} {value}" in text, name

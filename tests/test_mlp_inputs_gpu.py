@@ -17,6 +17,7 @@ from freegaussian_amd import _lib
 from freegaussian_amd import deform as D
 from freegaussian_amd import ops
 from helpers import REL_TOL, rel_err
+from mlp_common import GUARD, NAN, arena, named_grads_or_zeros
 from mlp_inputs_common import (BLENDER_TIME, aux_width, blender_clear_points, clear_inputs, float64_with_input_row, inputs,
                                make_net, module_float64, rows_clear_of_the_kink_aux, timenet_margin)  # fmt: skip
 from mlp_train_common import cotangents, head_rows, heads_of, loss_of, rows_clear_of_the_kink
@@ -28,8 +29,6 @@ M = ops.MLP_ROW_TILE
 SIZES = [1, M - 1, M, M + 1, 2 * M + 1]
 N_MAX = max(SIZES)
 N_DISPATCH = 33_000
-NAN = float("nan")
-GUARD = 1024
 # aux widths 21 and 63 (the modules), and 1, 30, 64: enc widths 88, 128, 64, 96, 128 -- the narrowest row, a pad tail, the
 # blender width, all four waves' blocks live
 KINDS = ["deform", "control", "A1", "A30", "A64"]
@@ -46,33 +45,21 @@ def spy(monkeypatch):
     return seen
 
 
-def _grads(m):
-    return {k: (torch.zeros_like(p) if p.grad is None else p.grad.detach().clone()) for k, p in m.named_parameters()}
-
-
 def _g_heads(m, n, seed=3):
     return torch.randn(n, sum(head_rows(m)), generator=torch.Generator().manual_seed(seed))
 
 
 # ---- the C entry points on guarded buffers ------------------------------------------------------------------------------
-def _arena(*shape):
-    numel = 1
-    for s in shape:
-        numel *= s
-    flat = torch.full((numel + 2 * GUARD,), NAN, device=DEV)
-    return flat, flat[GUARD : GUARD + numel].view(*shape)
-
-
 def _entry_points(m_dev, x, aux, g_heads, plain_too=False):
     """fg_mlp_train_fwd and fg_mlp_bwd_inputs into NaN-filled buffers with a NaN guard band on either side of each: (enc, H,
     G, g_enc[, G of fg_mlp_bwd]); the bands must come back untouched and everything between them finite."""
     x, aux, g_heads = x.to(DEV).contiguous(), aux.to(DEV).contiguous(), g_heads.to(DEV).contiguous()
     d, n, rows, keep = ops._mlp_desc("test", x, aux, m_dev.linear, heads_of(m_dev), _lib.MLP_PLAIN)
     enc_w = _lib.mlp_enc_width(d.aux_width)
-    arenas = [_arena(n, sum(rows)), _arena(n, enc_w), _arena(8, n, 256), _arena(8, n, 256), _arena(n, enc_w), _arena(8, n, 256)]
+    arenas = [arena(n, sum(rows)), arena(n, enc_w), arena(8, n, 256), arena(8, n, 256), arena(n, enc_w), arena(8, n, 256)]
     (_, heads), (_, enc), (_, H), (_, G), (_, g_enc), (_, G_plain) = arenas
     lib = _lib.load()
-    ws_flat, ws = _arena(int(lib.fg_mlp_bwd_inputs_workspace_bytes(n)) // 4)
+    ws_flat, ws = arena(int(lib.fg_mlp_bwd_inputs_workspace_bytes(n)) // 4)
     st = ops._stream()
     ops._call("fg_mlp_train_fwd", n, ctypes.addressof(d), heads.data_ptr(), enc.data_ptr(), H.data_ptr(), ws.data_ptr(),
               int(lib.fg_mlp_train_workspace_bytes(n)), st)  # fmt: skip
@@ -169,7 +156,7 @@ def _train_step(m_dev, x, aux, g_heads, **kw):
     x, aux = x.detach().to(DEV).requires_grad_(True), aux.detach().to(DEV).requires_grad_(True)
     raw = ops.mlp_train(x, aux, m_dev.linear, heads_of(m_dev), **kw)
     raw.backward(g_heads.to(DEV))
-    return raw.detach(), x.grad, aux.grad, _grads(m_dev)
+    return raw.detach(), x.grad, aux.grad, named_grads_or_zeros(m_dev)
 
 
 def _check_param_grads(m_dev, grads, ref):
@@ -235,7 +222,7 @@ def test_ops_without_the_keyword_gives_the_inputs_no_gradient(spy):
     m.zero_grad(set_to_none=True)
     ops.mlp_train(a["x"][:n].to(DEV), a["aux"][:n].to(DEV), m.linear, heads_of(m), input_grads=True).backward(a["g_heads"][:n].to(DEV))
     assert len(spy["bwd"]) == 3 and torch.equal(spy["bwd"][0][2], spy["bwd"][2][2])
-    assert all(torch.equal(grads[k], v) for k, v in _grads(m).items())
+    assert all(torch.equal(grads[k], v) for k, v in named_grads_or_zeros(m).items())
     # and with inputs that do: the parameter gradients are the same bits (g_pre is fg_mlp_bwd's)
     _, _, _, grads3 = _train_step(m, a["x"][:n], a["aux"][:n], a["g_heads"][:n], input_grads=True)
     assert torch.equal(spy["bwd"][3][2], spy["bwd"][0][2]) and all(torch.equal(grads[k], v) for k, v in grads3.items())
@@ -259,7 +246,7 @@ def test_blender_net_through_the_module(spy, monkeypatch):
     assert len(spy["train"]) == 1 and len(spy["bwd"]) == 1
     args, kw = spy["train"][0]
     assert args[1].shape == (1, 30) and args[1].requires_grad and kw == {"input_grads": True}  # the one time: timenet on one row
-    grads = _grads(m_dev)
+    grads = named_grads_or_zeros(m_dev)
     assert set(grads) == set(want) and len(grads) == 24 + 4 and sum(k.startswith("timenet.") for k in grads) == 4
     errs = {f"out{i}": rel_err(o, w) for i, (o, w) in enumerate(zip(outs, want_outs))}
     errs.update({k: rel_err(grads[k], want[k]) for k in sorted(want)})
@@ -320,7 +307,7 @@ def test_capture_and_replay_equal_the_eager_call(spy):
         return raw.detach()
 
     raw_e = step().clone()
-    eager = dict(g_x=x.grad.clone(), g_aux=aux.grad.clone(), G=spy["bwd"][0][2].clone(), params=_grads(m))
+    eager = dict(g_x=x.grad.clone(), g_aux=aux.grad.clone(), G=spy["bwd"][0][2].clone(), params=named_grads_or_zeros(m))
     torch.cuda.synchronize()
     graph = torch.cuda.CUDAGraph()
     with torch.cuda.graph(graph):

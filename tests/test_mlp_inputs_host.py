@@ -2,7 +2,6 @@
 (argument validation and the workspace query; every call returns before a launch), the dispatch predicate under
 ``FG_FUSED_MLP_TRAIN=2``, and the chain from ``g_enc`` to the inputs (``ops.mlp_input_grads``) in float64 against autograd."""
 import ctypes
-import os
 
 import pytest
 import torch
@@ -12,31 +11,23 @@ from freegaussian_amd import deform as D
 from freegaussian_amd import ops
 from freegaussian_amd.utils import positional_encoding
 from helpers import rel_err
+from mlp_common import PTR, addr, desc, header_text
 
 OK, INVALID, WORKSPACE, UNSUPPORTED = 0, -1, -3, -4
-PTR, BIG = 4096, 1 << 40  # an address nobody reads (every call below is refused before a launch); a workspace that would do
+BIG = 1 << 40  # a workspace that would do (every call below is refused before a launch)
 TIN_BYTES = 2 * 32 * 128 * 8 * 4  # the input columns of layers 0 and 5, packed
 
 
-def _desc(mode=_lib.MLP_PLAIN, A=21, rows=(3, 3, 4, 3)):
-    d = _lib.MlpDesc()
-    d.size, d.mode, d.depth, d.width, d.multires, d.aux_width = ctypes.sizeof(_lib.MlpDesc), mode, 8, 256, 10, A
-    d.n_heads = len(rows)
-    for i, r in enumerate(rows):
-        d.head_rows[i], d.head_weight[i], d.head_bias[i] = r, PTR, PTR
-    d.aux_stride, d.x, d.aux = A, PTR, PTR
-    for i in range(8):
-        d.weight[i], d.bias[i] = PTR, PTR
-    return d
+def _desc(*a, **kw):
+    return desc(*a, inputs=True, **kw)
 
 
 def _call(n, d, g_heads=PTR, acts=PTR, g_pre=PTR, g_enc=PTR, ws=PTR, ws_bytes=0):
-    return _lib.load().fg_mlp_bwd_inputs(n, ctypes.addressof(d) if d is not None else None, g_heads, acts, g_pre, g_enc, ws,
-                                         ws_bytes, None)  # fmt: skip
+    return _lib.load().fg_mlp_bwd_inputs(n, addr(d), g_heads, acts, g_pre, g_enc, ws, ws_bytes, None)
 
 
 def test_header_and_binding_agree():
-    text = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "include", "fgraster.h")).read()
+    text = header_text()
     assert f"#define FG_ABI_VERSION {_lib.ABI_VERSION}" in text and _lib.ABI_VERSION >= 13
     assert _lib.load().fg_abi_version() == _lib.ABI_VERSION
     for name in ("fg_mlp_bwd_inputs_workspace_bytes", "fg_mlp_bwd_inputs"):

@@ -19,6 +19,7 @@ from freegaussian_amd import _lib
 from freegaussian_amd import deform as D
 from freegaussian_amd import ops
 from helpers import REL_TOL, rel_err
+from mlp_common import GUARD, NAN, arena, train_step
 from mlp_split_common import ROWS, case
 from mlp_train_common import head_rows, heads_of
 
@@ -26,8 +27,6 @@ pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
 M = ops.MLP_ROW_TILE
-NAN = float("nan")
-GUARD = 1024
 SPLIT = "bf16x3"
 NETS = [("deform", "default"), ("deform", "half_dead"), ("control", "default"), ("control", "half_dead"),
         ("blender", "default"), ("blender", "half_dead")]  # fmt: skip
@@ -57,14 +56,6 @@ def _forward(m_dev, x, aux, precision=SPLIT, outs=None):
     if outs is None:
         outs = [_nan(n, r) for r in head_rows(m_dev)] if mode == "plain" else [_nan(n, 4, 4), _nan(n, 4), _nan(n, 3), _nan(n, 3)]
     return ops.mlp_forward(x, aux, m_dev.linear, heads_of(m_dev), mode=mode, outs=outs, precision=precision)
-
-
-def _arena(*shape):
-    numel = 1
-    for s in shape:
-        numel *= s
-    flat = torch.full((numel + 2 * GUARD,), NAN, device=DEV)
-    return flat, flat[GUARD : GUARD + numel].view(*shape)
 
 
 def _train_fwd(m_dev, x, aux, precision=_lib.MLP_BF16X3, bufs=None, ws=None):
@@ -142,17 +133,6 @@ def test_training_arrays_against_float64(kind, weights):
         assert rel_err(H[l], ref["H"][l]) <= REL_TOL and rel_err(G[l], ref["G"][l]) <= REL_TOL, l
 
 
-def _train_step(m_dev, x, aux, g_heads, **kw):
-    m_dev.requires_grad_(True).zero_grad(set_to_none=True)
-    x = x.detach().clone().requires_grad_(kw.get("input_grads", False))
-    aux = aux.detach().clone().requires_grad_(kw.get("input_grads", False))
-    raw = ops.mlp_train(x, aux, m_dev.linear, heads_of(m_dev), **kw)
-    raw.backward(g_heads)
-    grads = {k: p.grad.detach().clone() for k, p in m_dev.named_parameters() if p.grad is not None}
-    m_dev.requires_grad_(False).zero_grad(set_to_none=True)
-    return raw.detach(), grads, x.grad, aux.grad
-
-
 FORMS = {"library_products": {}, "fused_param_grads": {"fused_param_grads": True}, "input_grads": {"input_grads": True},
          "chunked_1": {"input_grads": True, "fused_param_grads": True, "chunked_backward": 1}}  # fmt: skip
 
@@ -164,7 +144,7 @@ def test_mlp_train_against_float64(kind, weights, form):
     asked for, the gradients of ``x`` and ``aux``."""
     c, m, x, aux, gh = _on_device(kind, weights)
     ref = c["ref"]
-    raw, grads, g_x, g_aux = _train_step(m, x, aux, gh, precision=SPLIT, **FORMS[form])
+    raw, grads, g_x, g_aux = train_step(m, x, aux, gh, precision=SPLIT, **FORMS[form])
     trunk_and_heads = {k: v for k, v in ref["grads"].items() if v is not None and not k.startswith("timenet")}
     assert set(grads) == set(trunk_and_heads) and len(grads) == 2 * (8 + len(head_rows(m)))
     errs = {"heads": rel_err(raw, ref["raw"])}
@@ -259,8 +239,8 @@ def test_null_outputs_guard_bands_and_the_bottom_row():
     lib = _lib.load()
     shapes = ((n, 4, 4), (n, 4), (n, 3), (n, 3))
     for skip in (0, 3, None):  # no d_xyz but pts; d_xyz but no pts; all four
-        arenas = [_arena(*s) for s in shapes]
-        ws_flat, ws = _arena(int(lib.fg_mlp_workspace_bytes(n)) // 4)
+        arenas = [arena(*s) for s in shapes]
+        ws_flat, ws = arena(int(lib.fg_mlp_workspace_bytes(n)) // 4)
         d, _, _, keep = ops._mlp_desc("test", x, aux, m.linear, heads_of(m), _lib.MLP_SE3)
         d.precision = _lib.MLP_BF16X3
         for i, (_, view) in enumerate(arenas):
@@ -277,16 +257,16 @@ def test_null_outputs_guard_bands_and_the_bottom_row():
     A = aux.shape[1]
     raw, enc, H = _train_fwd(m, x, aux)
     G, ge = _bwd(m, A, H, gh, inputs=True)
-    fwd = [_arena(*t.shape) for t in (raw, enc, H)]
-    ws_flat, ws = _arena(int(lib.fg_mlp_train_workspace_bytes(n)) // 4)
+    fwd = [arena(*t.shape) for t in (raw, enc, H)]
+    ws_flat, ws = arena(int(lib.fg_mlp_train_workspace_bytes(n)) // 4)
     _train_fwd(m, x, aux, bufs=[v for _, v in fwd], ws=ws)
     for ins in (True, False):
-        bwd = [_arena(*G.shape), _arena(*ge.shape)]
-        hin = [_arena(*H.shape), _arena(*gh.shape)]
+        bwd = [arena(*G.shape), arena(*ge.shape)]
+        hin = [arena(*H.shape), arena(*gh.shape)]
         hin[0][1].copy_(H), hin[1][1].copy_(gh)
         before = [flat.clone() for flat, _ in hin]
         need = lib.fg_mlp_bwd_inputs_workspace_bytes(n) if ins else lib.fg_mlp_train_workspace_bytes(n)
-        wsb_flat, wsb = _arena(int(need) // 4)
+        wsb_flat, wsb = arena(int(need) // 4)
         _bwd(m, A, hin[0][1], hin[1][1], inputs=ins, bufs=(bwd[0][1], bwd[1][1] if ins else None), ws=wsb)
         torch.cuda.synchronize()
         for flat in [f for f, _ in fwd] + [bwd[0][0], ws_flat, wsb_flat] + ([bwd[1][0]] if ins else []):

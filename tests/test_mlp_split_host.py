@@ -5,7 +5,6 @@ the arithmetic of the contract itself, emulated on the CPU (tests/mlp_split_comm
 The emulation's measured errors (``max|a-b| / max|b|``, 1024 rows clear of the kink by 1e-4; three terms, then two):
 about 5e-6 .. 1.5e-5 per array for the three-term product, some 1e-3 with the third term left out."""
 import ctypes
-import os
 import re
 import subprocess
 
@@ -16,30 +15,19 @@ from freegaussian_amd import _lib
 from freegaussian_amd import deform as D
 from freegaussian_amd import ops
 from helpers import REL_TOL, rel_err
+from mlp_common import PTR, desc, grads, header_text
 from mlp_split_common import MARGIN, POOL, ROWS, case, emulate, product, split, trunk_weight_grads
 
 OK, INVALID, WORKSPACE = 0, -1, -3
-PTR, BIG = 4096, 1 << 40  # an address nobody reads (every call below is refused before a launch); a workspace that would do
-ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+BIG = 1 << 40  # a workspace that would do (every call below is refused before a launch)
 
 
-def _desc(precision, mode=_lib.MLP_PLAIN, A=21, rows=(3, 3, 4, 3)):
-    d = _lib.MlpDesc()
-    d.size, d.mode, d.depth, d.width, d.multires, d.aux_width = ctypes.sizeof(_lib.MlpDesc), mode, 8, 256, 10, A
-    d.n_heads, d.precision = len(rows), precision
-    for i, r in enumerate(rows):
-        d.head_rows[i], d.head_weight[i], d.head_bias[i] = r, PTR, PTR
-    d.aux_stride, d.x, d.aux = A, PTR, PTR
-    for i in range(8):
-        d.weight[i], d.bias[i] = PTR, PTR
-    return d
+def _desc(precision, **kw):
+    return desc(precision=precision, inputs=True, **kw)
 
 
 def _grads():
-    g = _lib.MlpGrads()
-    g.size = ctypes.sizeof(_lib.MlpGrads)
-    g.weight[1] = PTR
-    return g
+    return grads(weight=(1,), bias=(), head_weight=(), head_bias=())
 
 
 def _calls():
@@ -57,7 +45,7 @@ def _calls():
 
 
 def test_header_binding_and_library_agree_on_the_query():
-    text = open(os.path.join(ROOT, "include", "fgraster.h")).read()
+    text = header_text()
     assert "int fg_mlp_precision_supported(int32_t precision);" in text
     assert "#define FG_MLP_FP32 0" in text and "#define FG_MLP_BF16X3 1" in text
     assert (_lib.MLP_FP32, _lib.MLP_BF16X3) == (0, 1)
@@ -76,7 +64,7 @@ def test_the_descriptor_keeps_its_layout():
     assert ctypes.sizeof(_lib.MlpDesc) == 12 * 4 + 8 + (2 + 8 + 8 + 3 * _lib.MLP_MAX_HEADS) * 8
     assert _lib.MlpDesc.precision.offset == 11 * 4 and _lib.MlpDesc.precision.size == 4
     assert _lib.MlpDesc().precision == _lib.MLP_FP32  # what every earlier caller passes
-    text = open(os.path.join(ROOT, "include", "fgraster.h")).read()
+    text = header_text()
     body = text[text.index("typedef struct fg_mlp_desc {") : text.index("} fg_mlp_desc;")]
     assert re.search(r"int32_t head_rows\[FG_MLP_MAX_HEADS\];\s*int32_t precision;[^\n]*\n\s*int64_t aux_stride;", body)
     # fg_mlp_grads keeps its own reserved word

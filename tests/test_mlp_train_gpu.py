@@ -18,6 +18,7 @@ from freegaussian_amd import _lib
 from freegaussian_amd import deform as D
 from freegaussian_amd import ops
 from helpers import REL_TOL, rel_err
+from mlp_common import GUARD, NAN, arena, named_grads_or_zeros
 from mlp_train_common import (assembled, aux_of, cotangents, half_dead_, head_rows, heads_of, loss_of, manual_float64,
                               outputs_from_raw, rows_clear_of_the_kink)  # fmt: skip
 
@@ -28,8 +29,6 @@ M = ops.MLP_ROW_TILE
 CHUNK = D._TallLinear.CHUNK
 SIZES = [1, M - 1, M, M + 1, 2 * M + 1, CHUNK + 65, 33_000]
 N_MAX = max(SIZES)
-NAN = float("nan")
-GUARD = 1024
 
 
 def _net(kind, weights="default"):
@@ -62,17 +61,13 @@ def spy(monkeypatch):
     return seen
 
 
-def _grads(m):
-    return {k: (torch.zeros_like(p) if p.grad is None else p.grad.detach().clone()) for k, p in m.named_parameters()}
-
-
 def _fused_step(m_dev, x, other, cots):
     """One taped ops.mlp_train + the module's head arithmetic + backward: (raw heads, outputs, parameter gradients)."""
     m_dev.zero_grad(set_to_none=True)
     raw = ops.mlp_train(x.to(DEV), aux_of(m_dev, other.to(DEV)), m_dev.linear, heads_of(m_dev))
     outs = outputs_from_raw(m_dev, raw)
     loss_of(outs, [None if c is None else c.to(DEV) for c in cots]).backward()
-    return raw.detach(), [o.detach() for o in outs], _grads(m_dev)
+    return raw.detach(), [o.detach() for o in outs], named_grads_or_zeros(m_dev)
 
 
 # ---- 1. float64 arbiter ----------------------------------------------------------------------------------------------
@@ -122,7 +117,7 @@ def test_activations_and_gradients_against_float64(kind, weights, n, spy, monkey
         m.zero_grad(set_to_none=True)
         outs = m(x.to(DEV), other.to(DEV))
         loss_of(outs, [c.to(DEV) for c in cots]).backward()
-        outs, grads = [o.detach() for o in outs], _grads(m)
+        outs, grads = [o.detach() for o in outs], named_grads_or_zeros(m)
     else:
         _, outs, grads = _fused_step(m, x, other, cots)
     assert len(spy["train"]) == 1 and len(spy["bwd"]) == 1
@@ -147,19 +142,11 @@ def test_raw_heads_equal_the_inference_kernel_bitwise(kind):
 
 
 # ---- 3. the C entry points on guarded buffers ---------------------------------------------------------------------------
-def _arena(*shape):
-    numel = 1
-    for s in shape:
-        numel *= s
-    flat = torch.full((numel + 2 * GUARD,), NAN, device=DEV)
-    return flat, flat[GUARD : GUARD + numel].view(*shape)
-
-
 def _entry_points(m_dev, x, aux, g_heads):
     """fg_mlp_train_fwd and fg_mlp_bwd into NaN-filled buffers with a NaN guard band on either side of each: (heads, enc,
     H, G); the bands must come back untouched and everything between them finite."""
     d, n, rows, keep = ops._mlp_desc("test", x, aux, m_dev.linear, heads_of(m_dev), _lib.MLP_PLAIN)
-    arenas = [_arena(n, sum(rows)), _arena(n, _lib.mlp_enc_width(d.aux_width)), _arena(8, n, 256), _arena(8, n, 256)]
+    arenas = [arena(n, sum(rows)), arena(n, _lib.mlp_enc_width(d.aux_width)), arena(8, n, 256), arena(8, n, 256)]
     (_, heads), (_, enc), (_, H), (_, G) = arenas
     ws = torch.empty(int(_lib.load().fg_mlp_train_workspace_bytes(n)), dtype=torch.uint8, device=DEV)
     args = (ws.data_ptr(), ws.numel(), ops._stream())
@@ -266,7 +253,7 @@ def test_unused_head_counts_as_zeros():
     outs = m(x.to(DEV), other.to(DEV))  # (below FUSED_MIN_ROWS and the variable unset: the torch ops)
     loss_of(outs, [None if c is None else c.to(DEV) for c in cots]).backward()
     assert m.gaussian_scaling.weight.grad is None
-    plain = _grads(m)
+    plain = named_grads_or_zeros(m)
     assert bool((fused["gaussian_scaling.weight"] == 0).all()) and bool((fused["gaussian_scaling.bias"] == 0).all())
     for k in plain:
         if not k.startswith("gaussian_scaling"):

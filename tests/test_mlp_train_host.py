@@ -2,7 +2,6 @@
 validation and the workspace query; every call returns before a launch), ``ops.mlp_train``'s refusals, the dispatch
 predicate, and the parameter-gradient assembly (``deform.mlp_param_grads``) in float64 against autograd through the modules."""
 import ctypes
-import os
 
 import pytest
 import torch
@@ -11,34 +10,27 @@ from freegaussian_amd import _lib
 from freegaussian_amd import deform as D
 from freegaussian_amd import ops
 from helpers import rel_err
+from mlp_common import PTR, addr, desc, header_text
 from mlp_train_common import assembled, cotangents, half_dead_, head_rows, loss_of, manual_float64
 
 OK, INVALID, WORKSPACE, UNSUPPORTED = 0, -1, -3, -4
-PTR, BIG = 4096, 1 << 40  # an address nobody reads (every call below is refused before a launch); a workspace that would do
+BIG = 1 << 40  # a workspace that would do (every call below is refused before a launch)
 
 
-def _desc(mode=_lib.MLP_PLAIN, A=21, rows=(3, 3, 4, 3)):
-    d = _lib.MlpDesc()
-    d.size, d.mode, d.depth, d.width, d.multires, d.aux_width = ctypes.sizeof(_lib.MlpDesc), mode, 8, 256, 10, A
-    d.n_heads = len(rows)
-    for i, r in enumerate(rows):
-        d.head_rows[i], d.head_weight[i], d.head_bias[i] = r, PTR, PTR
-    d.aux_stride, d.x, d.aux = A, PTR, PTR
-    for i in range(8):
-        d.weight[i], d.bias[i] = PTR, PTR
-    return d
+def _desc(*a, **kw):
+    return desc(*a, inputs=True, **kw)
 
 
 def _fwd(n, d, heads=PTR, enc=PTR, acts=PTR, ws=PTR, ws_bytes=0):
-    return _lib.load().fg_mlp_train_fwd(n, ctypes.addressof(d) if d is not None else None, heads, enc, acts, ws, ws_bytes, None)
+    return _lib.load().fg_mlp_train_fwd(n, addr(d), heads, enc, acts, ws, ws_bytes, None)
 
 
 def _bwd(n, d, g_heads=PTR, acts=PTR, g_pre=PTR, ws=PTR, ws_bytes=0):
-    return _lib.load().fg_mlp_bwd(n, ctypes.addressof(d) if d is not None else None, g_heads, acts, g_pre, ws, ws_bytes, None)
+    return _lib.load().fg_mlp_bwd(n, addr(d), g_heads, acts, g_pre, ws, ws_bytes, None)
 
 
 def test_header_constants_and_binding_agree():
-    text = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "include", "fgraster.h")).read()
+    text = header_text()
     assert f"#define FG_ABI_VERSION {_lib.ABI_VERSION}" in text and _lib.ABI_VERSION >= 12
     assert "#define FG_MLP_ENC_WIDTH(aux_width) ((63 + (aux_width) + 7) / 8 * 8)" in text
     assert [_lib.mlp_enc_width(a) for a in (1, 2, 21, 63, 64)] == [64, 72, 88, 128, 128]

@@ -19,15 +19,14 @@ from freegaussian_amd import _lib
 from freegaussian_amd import deform as D
 from freegaussian_amd import ops
 from helpers import REL_TOL, rel_err
+from mlp_common import GUARD, NAN, arena, flat, grad_names, lib_calls, module_inputs, module_step, named_grads, out_shapes
 from mlp_inputs_common import BLENDER_TIME, clear_inputs, float64_with_input_row, make_net
-from mlp_train_common import aux_of, cotangents, head_rows, heads_of, loss_of, manual_float64, rows_clear_of_the_kink
+from mlp_train_common import aux_of, cotangents, head_rows, heads_of, manual_float64, rows_clear_of_the_kink
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
 CHUNK = D._TallLinear.CHUNK
-NAN = float("nan")
-GUARD = 1024
 N_MAX = 33_000
 ROWS4 = (3, 3, 4, 3)
 
@@ -90,23 +89,14 @@ def _float64(A, rows, n):
     return _WANT[key]
 
 
-def _names(rows):
-    k = len(rows)
-    return [f"gW[{l}]" for l in range(8)] + [f"gb[{l}]" for l in range(8)] + [f"gWh[{h}]" for h in range(k)] + [f"gbh[{h}]" for h in range(k)]
-
-
-def _flat(grads4):
-    return [t for group in grads4 for t in group]
-
-
 def _run(A, rows, n, want=None):
     dev = [t.to(DEV) for t in _case(A, rows, n)]
-    return _flat(ops.mlp_param_grads(*dev, A, rows, want=want))
+    return flat(ops.mlp_param_grads(*dev, A, rows, want=want))
 
 
 def _check(tag, got, want, rows):
     worst = {}
-    for name, g, w in zip(_names(rows), got, want):
+    for name, g, w in zip(grad_names(rows), got, want):
         assert g.shape == w.shape and g.dtype == torch.float32, name
         assert bool(torch.isfinite(g).all()), name
         err = rel_err(g, w)
@@ -132,31 +122,17 @@ def test_every_aux_width_and_head_set_against_float64(A, rows, n):
 
 
 # ---- 2. only what is asked for is written, only what belongs is read -----------------------------------------------------
-def _arena(*shape):
-    numel = 1
-    for s in shape:
-        numel *= s
-    flat = torch.full((numel + 2 * GUARD,), NAN, device=DEV)
-    return flat, flat[GUARD : GUARD + numel].view(*shape)
-
-
-def _out_shapes(A, rows):
-    in_ch = 63 + A
-    return ([(256, in_ch if l == 0 else (in_ch + 256 if l == 5 else 256)) for l in range(8)] + [(256,)] * 8
-            + [(r, 256) for r in rows] + [(r,) for r in rows])  # fmt: skip
-
-
 def _entry_point(A, rows, n, want=None):
     """fg_mlp_param_grads on inputs and outputs carved from NaN-filled arenas: NaN in enc's pad columns and directly behind
     acts[7, n - 1], g_pre[7, n - 1] and g_heads[n - 1] (the guard bands).  Returns (outputs, arenas of the outputs)."""
     k = len(rows)
     want = [True] * (16 + 2 * k) if want is None else want
-    ins = [_arena(*t.shape) for t in _case(A, rows, n)]
+    ins = [arena(*t.shape) for t in _case(A, rows, n)]
     for (flat, view), t in zip(ins, _case(A, rows, n)):
         view.copy_(t)
     ins[0][1][:, 63 + A :] = NAN
     before = [flat.clone() for flat, _ in ins]
-    outs = [_arena(*s) for s in _out_shapes(A, rows)]
+    outs = [arena(*s) for s in out_shapes(A, rows)]
     d, g = _lib.MlpDesc(), _lib.MlpGrads()
     d.size, d.mode, d.depth, d.width, d.multires = ctypes.sizeof(_lib.MlpDesc), _lib.MLP_PLAIN, 8, 256, 10
     d.aux_width, d.n_heads, g.size = A, k, ctypes.sizeof(_lib.MlpGrads)
@@ -167,7 +143,7 @@ def _entry_point(A, rows, n, want=None):
         g.weight[i], g.bias[i] = ptr(i), ptr(8 + i)
     for i in range(k):
         g.head_weight[i], g.head_bias[i] = ptr(16 + i), ptr(16 + k + i)
-    ws_flat, ws = _arena(int(_lib.load().fg_mlp_param_grads_workspace_bytes(n)) // 4)
+    ws_flat, ws = arena(int(_lib.load().fg_mlp_param_grads_workspace_bytes(n)) // 4)
     ops._call("fg_mlp_param_grads", n, ctypes.addressof(d), *(view.data_ptr() for _, view in ins), ctypes.addressof(g),
               ws.data_ptr(), ws.numel() * 4, ops._stream())  # fmt: skip
     torch.cuda.synchronize()
@@ -218,15 +194,15 @@ def test_nullable_outputs(group):
 def test_two_calls_are_bitwise_equal_whatever_else_runs():
     A, n = 30, 8193
     dev = [t.to(DEV) for t in _case(A, ROWS4, n)]
-    first = _flat(ops.mlp_param_grads(*dev, A, ROWS4))
-    again = _flat(ops.mlp_param_grads(*dev, A, ROWS4))
+    first = flat(ops.mlp_param_grads(*dev, A, ROWS4))
+    again = flat(ops.mlp_param_grads(*dev, A, ROWS4))
     side = torch.cuda.Stream()
     a, b = torch.randn(2048, 2048, device=DEV), torch.randn(2048, 2048, device=DEV)
     torch.cuda.synchronize()
     with torch.cuda.stream(side):  # an unrelated kernel queued on another stream, sharing the device with the call
         for _ in range(4):
             a = a @ b
-    busy = _flat(ops.mlp_param_grads(*dev, A, ROWS4))
+    busy = flat(ops.mlp_param_grads(*dev, A, ROWS4))
     torch.cuda.synchronize()
     for x, y, z in zip(first, again, busy):
         assert torch.equal(x, y) and torch.equal(x, z)
@@ -239,7 +215,7 @@ def test_capture_and_replay_equal_the_eager_call():
     torch.cuda.synchronize()
     graph = torch.cuda.CUDAGraph()
     with torch.cuda.graph(graph):
-        captured = _flat(ops.mlp_param_grads(*static, A, ROWS4))
+        captured = flat(ops.mlp_param_grads(*static, A, ROWS4))
     # other inputs, written in place: rows n .. 2 n of the same pool
     enc, H, G, gh = _arrays(A)
     fresh = [enc[n : 2 * n], H[:, n : 2 * n], G[:, n : 2 * n], gh[n : 2 * n, : sum(ROWS4)]]
@@ -249,7 +225,7 @@ def test_capture_and_replay_equal_the_eager_call():
         out.fill_(NAN)
     graph.replay()
     torch.cuda.synchronize()
-    eager = _flat(ops.mlp_param_grads(*static, A, ROWS4))
+    eager = flat(ops.mlp_param_grads(*static, A, ROWS4))
     for c, e in zip(captured, eager):
         assert bool(torch.isfinite(c).all()) and torch.equal(c, e)
 
@@ -258,7 +234,7 @@ def test_capture_and_replay_equal_the_eager_call():
 def test_zero_cotangents_give_exact_zeros():
     A, n = 30, 8193
     enc, H, G, gh = (t.to(DEV) for t in _case(A, ROWS4, n))
-    for out in _flat(ops.mlp_param_grads(enc, H, torch.zeros_like(G), torch.zeros_like(gh), A, ROWS4)):
+    for out in flat(ops.mlp_param_grads(enc, H, torch.zeros_like(G), torch.zeros_like(gh), A, ROWS4)):
         assert bool((out == 0).all())
 
 
@@ -276,7 +252,7 @@ def test_a_single_one_lands_in_one_row_of_one_gradient(n):
     for i, r in enumerate(places):
         l, j = (i * 3 + 5) % 8, (i * 67 + 129) % 256
         G[l, r, j] = 1.0
-        out = _flat(ops.mlp_param_grads(enc, H, G, gh, A, rows))
+        out = flat(ops.mlp_param_grads(enc, H, G, gh, A, rows))
         G[l, r, j] = 0.0
         for k, t in enumerate(out):
             want = torch.zeros_like(t)
@@ -285,7 +261,7 @@ def test_a_single_one_lands_in_one_row_of_one_gradient(n):
             assert torch.equal(t, want), (r, l, j, k)
         o = (i * 5 + 4) % sum(rows)  # head cotangent column o = row o of the stacked head gradients
         gh[r, o] = 1.0
-        out = _flat(ops.mlp_param_grads(enc, H, G, gh, A, rows))
+        out = flat(ops.mlp_param_grads(enc, H, G, gh, A, rows))
         gh[r, o] = 0.0
         assert all(bool((t == 0).all()) for t in out[:16])
         assert torch.equal(torch.cat(out[16:20]), torch.zeros(13, 256, device=DEV).index_fill_(0, torch.tensor([o], device=DEV), 1.0))
@@ -303,8 +279,8 @@ def test_rows_are_matched_with_their_own_rows():
     g = torch.Generator().manual_seed(7)
     G = (torch.rand(8, n, 256, generator=g) < 0.01).float()
     gh = (torch.rand(n, sum(rows), generator=g) < 0.05).float()
-    want = _flat(D.mlp_param_grads(enc[:, : 63 + A].double(), H.double(), G.double(), gh.double(), rows))
-    got = _flat(ops.mlp_param_grads(enc.to(DEV), H.to(DEV), G.to(DEV), gh.to(DEV), A, rows))
+    want = flat(D.mlp_param_grads(enc[:, : 63 + A].double(), H.double(), G.double(), gh.double(), rows))
+    got = flat(ops.mlp_param_grads(enc.to(DEV), H.to(DEV), G.to(DEV), gh.to(DEV), A, rows))
     for k, (a, b) in enumerate(zip(got, want)):
         assert float(b.abs().max()) < 2**24 and torch.equal(a.cpu().double(), b), k
 
@@ -313,29 +289,18 @@ def test_rows_are_matched_with_their_own_rows():
 @pytest.fixture
 def spy(monkeypatch):
     """Calls of deform.mlp_param_grads, of ops.mlp_param_grads and of the library's fg_mlp_param_grads."""
-    seen = {"torch": [], "ops": [], "lib": []}
-    real_torch, real_ops, real_call = D.mlp_param_grads, ops.mlp_param_grads, ops._call
+    seen = {"torch": [], "ops": [], "lib": lib_calls(monkeypatch, ("fg_mlp_param_grads",))}
+    real_torch, real_ops = D.mlp_param_grads, ops.mlp_param_grads
     monkeypatch.setattr(D, "mlp_param_grads", lambda *a: seen["torch"].append(a) or real_torch(*a))
     monkeypatch.setattr(ops, "mlp_param_grads", lambda *a, **k: seen["ops"].append((a, k)) or real_ops(*a, **k))
-
-    def call(name, *a, **k):
-        if name == "fg_mlp_param_grads":
-            seen["lib"].append(name)
-        return real_call(name, *a, **k)
-
-    monkeypatch.setattr(ops, "_call", call)
     return seen
-
-
-def _grads_of(m):
-    return {k: (None if p.grad is None else p.grad.detach().clone()) for k, p in m.named_parameters()}
 
 
 def _train_step(m_dev, x, aux, g_heads, **kw):
     m_dev.zero_grad(set_to_none=True)
     raw = ops.mlp_train(x, aux, m_dev.linear, heads_of(m_dev), **kw)
     raw.backward(g_heads)
-    return raw.detach(), _grads_of(m_dev)
+    return raw.detach(), named_grads(m_dev)
 
 
 @pytest.mark.parametrize("n", [65, 3 * CHUNK + 65])
@@ -349,7 +314,7 @@ def test_through_mlp_train_against_float64(kind, n, spy):
         want = {k: v for k, v in want.items() if v is not None}
         kw = dict(input_grads=True)
     else:
-        x, other = (t[: n + n // 2 + 64] for t in _module_inputs(kind, n + n // 2 + 64))
+        x, other = (t[: n + n // 2 + 64] for t in module_inputs(kind, n + n // 2 + 64))
         ok = rows_clear_of_the_kink(m, x, other)
         assert int(ok.sum()) >= n
         x, other = x[ok][:n].contiguous(), other[ok][:n].contiguous()
@@ -382,35 +347,23 @@ def test_through_mlp_train_against_float64(kind, n, spy):
         assert e_on < REL_TOL and e_off < REL_TOL, (k, e_on, e_off)
 
 
-def _module_inputs(kind, n, seed=1):
-    g = torch.Generator().manual_seed(seed)
-    x = torch.rand(n, 3, generator=g) * 2 - 1
-    return x, (torch.randn(n, 3, generator=g) * 0.1 if kind == "control" else torch.rand(n, 1, generator=g))
-
-
 # ---- 7. through the modules and the model -------------------------------------------------------------------------------
-def _module_step(m_dev, x, other, cots):
-    m_dev.zero_grad(set_to_none=True)
-    loss_of(m_dev(x, other), cots).backward()
-    return _grads_of(m_dev)
-
-
 @pytest.mark.parametrize("kind,train", [("deform", "1"), ("control", "1"), ("blender", "2")])
 def test_modules_with_the_knob_set_and_unset(kind, train, spy, monkeypatch):
     n = D.FUSED_MIN_ROWS + 65
     m = make_net(kind)
     # (both settings form their gradients from the same H and G, bit for bit: no row has to be kept clear of the ReLU's kink)
-    x, other = _module_inputs(kind, n, seed=4)
+    x, other = module_inputs(kind, n, seed=4)
     if kind == "blender":
         other = torch.full((1, 1), BLENDER_TIME).expand(n, -1)
     m_dev = copy.deepcopy(m).to(DEV)
     xd, od, cots = x.to(DEV), other.to(DEV), [c.to(DEV) for c in cotangents(m, n)]
     monkeypatch.setenv("FG_FUSED_MLP_TRAIN", train)
     monkeypatch.delenv("FG_FUSED_MLP_WGRAD", raising=False)
-    off = _module_step(m_dev, xd, od, cots)
+    off = module_step(m_dev, xd, od, cots)
     assert (len(spy["torch"]), len(spy["lib"])) == (1, 0)
     monkeypatch.setenv("FG_FUSED_MLP_WGRAD", "1")
-    on = _module_step(m_dev, xd, od, cots)
+    on = module_step(m_dev, xd, od, cots)
     assert (len(spy["torch"]), len(spy["lib"])) == (1, 1)
     errs = {k: rel_err(on[k], off[k]) for k in off}
     print(f"mlp_wgrad module {kind}: worst {max(errs.values()):.2e}")
@@ -421,7 +374,7 @@ def test_modules_with_the_knob_set_and_unset(kind, train, spy, monkeypatch):
     frozen = [heads_of(m_dev)[1].weight, heads_of(m_dev)[1].bias, m_dev.linear[3].bias]
     for p in frozen:
         p.requires_grad_(False)
-    part = _module_step(m_dev, xd, od, cots)
+    part = module_step(m_dev, xd, od, cots)
     args, kwargs = spy["ops"][-1]
     k_heads = len(head_rows(m))
     assert [i for i, w in enumerate(kwargs["want"]) if not w] == [8 + 3, 16 + 1, 16 + k_heads + 1]
@@ -434,7 +387,7 @@ def test_modules_with_the_knob_set_and_unset(kind, train, spy, monkeypatch):
     # without the training knob the new one does nothing
     monkeypatch.delenv("FG_FUSED_MLP_TRAIN")
     calls = len(spy["lib"])
-    _module_step(m_dev, xd, od, cots)
+    module_step(m_dev, xd, od, cots)
     assert len(spy["lib"]) == calls
 
 

@@ -11,39 +11,24 @@ import torch
 from freegaussian_amd import _lib
 from freegaussian_amd import deform as D
 from freegaussian_amd import ops
+from mlp_common import PTR, addr, desc, grads, header_text, stand_in_for_cuda
 
 OK, INVALID, WORKSPACE, UNSUPPORTED = 0, -1, -3, -4
-PTR, BIG = 4096, 1 << 40  # an address nobody reads (every call below is refused before a launch); a workspace that would do
-HEADER = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "include", "fgraster.h")
+BIG = 1 << 40  # a workspace that would do (every call below is refused before a launch)
 
 
-def _desc(mode=_lib.MLP_PLAIN, A=21, rows=(3, 3, 4, 3)):
+def _desc(*a, **kw):
     """The shape alone: every parameter and input pointer of the descriptor stays null."""
-    d = _lib.MlpDesc()
-    d.size, d.mode, d.depth, d.width, d.multires, d.aux_width = ctypes.sizeof(_lib.MlpDesc), mode, 8, 256, 10, A
-    d.n_heads = len(rows)
-    for i, r in enumerate(rows):
-        d.head_rows[i] = r
-    return d
-
-
-def _grads(weight=range(8), bias=range(8), head_weight=range(4), head_bias=range(4)):
-    g = _lib.MlpGrads()
-    g.size = ctypes.sizeof(_lib.MlpGrads)
-    for name, which in (("weight", weight), ("bias", bias), ("head_weight", head_weight), ("head_bias", head_bias)):
-        for i in which:
-            getattr(g, name)[i] = PTR
-    return g
+    return desc(*a, weights=False, **kw)
 
 
 def _call(n, d, enc=PTR, acts=PTR, g_pre=PTR, g_heads=PTR, out="all", ws=PTR, ws_bytes=0):
-    out = _grads() if isinstance(out, str) else out
-    return _lib.load().fg_mlp_param_grads(n, ctypes.addressof(d) if d is not None else None, enc, acts, g_pre, g_heads,
-                                          ctypes.addressof(out) if out is not None else None, ws, ws_bytes, None)  # fmt: skip
+    out = grads() if isinstance(out, str) else out
+    return _lib.load().fg_mlp_param_grads(n, addr(d), enc, acts, g_pre, g_heads, addr(out), ws, ws_bytes, None)
 
 
 def test_header_and_binding_agree():
-    text = open(HEADER).read()
+    text = header_text()
     assert "#define FG_ABI_VERSION 14" in text and _lib.ABI_VERSION == 14 and _lib.load().fg_abi_version() == 14
     for name in ("fg_mlp_param_grads_workspace_bytes", "fg_mlp_param_grads"):
         assert name in _lib.SIGNATURES and f"{name}(" in text
@@ -92,10 +77,10 @@ def test_error_codes_without_gpu():
         assert _call(100, d) == UNSUPPORTED, field
     # out: null, a wrong size field, every pointer null (nothing to do: no workspace is asked for)
     assert _call(100, _desc(), out=None, ws_bytes=BIG) == INVALID
-    g = _grads()
+    g = grads()
     g.size -= 8
     assert _call(100, _desc(), out=g, ws_bytes=BIG) == INVALID
-    assert _call(100, _desc(), None, None, None, None, out=_grads((), (), (), ()), ws=None, ws_bytes=0) == OK
+    assert _call(100, _desc(), None, None, None, None, out=grads((), (), (), ()), ws=None, ws_bytes=0) == OK
     # each null input whose product is wanted
     for i in range(4):
         bufs = [PTR] * 4
@@ -103,10 +88,10 @@ def test_error_codes_without_gpu():
         assert _call(100, _desc(), *bufs, ws_bytes=BIG) == INVALID, i
     # ... and a null input that no gradient asked for reads
     none = ((), (), (), ())
-    only = lambda **kw: _grads(**{**dict(zip(("weight", "bias", "head_weight", "head_bias"), none)), **kw})  # noqa: E731
-    assert _call(100, _desc(), enc=None, out=_grads(weight=(1, 2, 3, 4, 6, 7))) == WORKSPACE
-    assert _call(100, _desc(), enc=None, out=_grads(weight=(0,)), ws_bytes=BIG) == INVALID
-    assert _call(100, _desc(), enc=None, out=_grads(weight=(5,)), ws_bytes=BIG) == INVALID
+    only = lambda **kw: grads(**{**dict(zip(("weight", "bias", "head_weight", "head_bias"), none)), **kw})  # noqa: E731
+    assert _call(100, _desc(), enc=None, out=grads(weight=(1, 2, 3, 4, 6, 7))) == WORKSPACE
+    assert _call(100, _desc(), enc=None, out=grads(weight=(0,)), ws_bytes=BIG) == INVALID
+    assert _call(100, _desc(), enc=None, out=grads(weight=(5,)), ws_bytes=BIG) == INVALID
     assert _call(100, _desc(), acts=None, out=only(weight=(0,), bias=range(8), head_bias=range(4))) == WORKSPACE
     assert _call(100, _desc(), acts=None, out=only(weight=(5,)), ws_bytes=BIG) == INVALID
     assert _call(100, _desc(), acts=None, out=only(head_weight=(2,)), ws_bytes=BIG) == INVALID
@@ -163,7 +148,8 @@ def test_ops_refuses_cpu_tensors_and_bad_shapes(monkeypatch):
         (enc, H[:, :-1].contiguous(), G[:, :-1].contiguous(), gh, 21, rows),  # mismatched N
         (enc, H, torch.zeros(7, n, 256), gh, 21, rows),  # G.shape != H.shape
         (enc, H, G, gh, 21, (3, 3, 4)),  # head rows that do not sum to g_heads' width
-        (enc, H, G, gh, 22, rows),  # an enc of another aux width
+        # an enc of another aux width: 63 + 26 pads to 96 (63 + 22 pads to enc's own 88, which ops has no reason to refuse)
+        (enc, H, G, gh, 26, rows),
         (enc, H, G, gh, 21, rows, [True] * 5),  # a want of the wrong length
     ]
     for args in bad:
@@ -173,15 +159,7 @@ def test_ops_refuses_cpu_tensors_and_bad_shapes(monkeypatch):
 
 
 def _stand_in_for_cuda(monkeypatch):
-    """``ops.mlp_train`` replaced by a spy that returns zeros, tensors that report CUDA: the dispatch alone, on the CPU."""
-    seen = []
-
-    def fake(x, aux, trunk, heads, **kw):
-        seen.append(kw)
-        return torch.zeros(x.shape[0], sum(h.weight.shape[0] for h in heads)) + 0.0 * trunk[0].bias.sum()
-
-    monkeypatch.setattr(ops, "mlp_train", fake)
-    return seen
+    return stand_in_for_cuda(monkeypatch, is_cuda=False)  # (the tests below decide themselves which tensors report CUDA)
 
 
 def test_knob_unset_passes_no_fused_param_grads(monkeypatch):

@@ -21,15 +21,14 @@ from freegaussian_amd import _lib
 from freegaussian_amd import deform as D
 from freegaussian_amd import ops
 from helpers import REL_TOL, rel_err
+from mlp_common import GUARD, NAN, arena, flat, grad_names, lib_calls, module_inputs, module_step, out_shapes, train_step
 from mlp_inputs_common import BLENDER_TIME, make_net
 from mlp_split_common import ROWS, case, split
-from mlp_train_common import cotangents, head_rows, heads_of, loss_of
+from mlp_train_common import cotangents, head_rows, heads_of
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
-NAN = float("nan")
-GUARD = 1024
 N_MAX = 33_000
 ROWS4 = (3, 3, 4, 3)
 SPLIT = "bf16x3"
@@ -81,29 +80,20 @@ def _float64(A, rows, n):
     return _WANT[key]
 
 
-def _names(rows):
-    k = len(rows)
-    return [f"gW[{l}]" for l in range(8)] + [f"gb[{l}]" for l in range(8)] + [f"gWh[{h}]" for h in range(k)] + [f"gbh[{h}]" for h in range(k)]
-
-
-def _flat(grads4):
-    return [t for group in grads4 for t in group]
-
-
 def _run(A, rows, n, want=None, precision=SPLIT):
     dev = [t.to(DEV) for t in _case(A, rows, n)]
-    return _flat(ops.mlp_param_grads(*dev, A, rows, want=want, precision=precision))
+    return flat(ops.mlp_param_grads(*dev, A, rows, want=want, precision=precision))
 
 
 def _check(tag, got, want, rows):
     worst = {}
-    for name, g, w in zip(_names(rows), got, want):
+    for name, g, w in zip(grad_names(rows), got, want):
         assert g.shape == w.shape and g.dtype == torch.float32, name
         assert bool(torch.isfinite(g).all()), name
         err = rel_err(g, w)
         worst[name.split("[")[0]] = max(worst.get(name.split("[")[0], 0.0), err)
     print(f"mlp_wgrad_split {tag}: " + ", ".join(f"{k} {v:.2e}" for k, v in worst.items()))
-    for name, g, w in zip(_names(rows), got, want):
+    for name, g, w in zip(grad_names(rows), got, want):
         assert rel_err(g, w) < REL_TOL, (tag, name, rel_err(g, w))
 
 
@@ -163,8 +153,8 @@ def test_a_single_one_in_the_cotangents_returns_hi_plus_lo_of_the_input_row():
     places = [(0, 37, 200), (0, s + 5, 3), (5, 0, 129), (5, n - 1, 255), (3, s - 1, 64), (3, 2 * s + 8, 0), (7, 15, 31), (1, s + 16, 127)]
     for l, r, i in places:
         G[l, r, i] = 1.0
-        got = _flat(ops.mlp_param_grads(enc, H, G, gh, A, ROWS4, precision=SPLIT))
-        exact = _flat(ops.mlp_param_grads(enc, H, G, gh, A, ROWS4))
+        got = flat(ops.mlp_param_grads(enc, H, G, gh, A, ROWS4, precision=SPLIT))
+        exact = flat(ops.mlp_param_grads(enc, H, G, gh, A, ROWS4))
         G[l, r, i] = 0.0
         row = _input_row(l, r, enc, H, in_ch)
         want = torch.zeros_like(got[l])
@@ -190,8 +180,8 @@ def test_a_single_one_in_the_inputs_returns_hi_plus_lo_of_the_cotangent_row():
     enc, H = torch.zeros(n, _lib.mlp_enc_width(A), device=DEV), torch.zeros(8, n, 256, device=DEV)
     for l, r, j in [(1, 37, 200), (4, s + 5, 3), (5, 2 * s + 8, 129), (7, n - 1, 255), (2, s - 1, 0)]:
         H[l - 1, r, j] = 1.0
-        got = _flat(ops.mlp_param_grads(enc, H, G, gh, A, ROWS4, precision=SPLIT))
-        exact = _flat(ops.mlp_param_grads(enc, H, G, gh, A, ROWS4))
+        got = flat(ops.mlp_param_grads(enc, H, G, gh, A, ROWS4, precision=SPLIT))
+        exact = flat(ops.mlp_param_grads(enc, H, G, gh, A, ROWS4))
         H[l - 1, r, j] = 0.0
         col = j + (in_ch if l == 5 else 0)
         want = torch.zeros_like(got[l])
@@ -203,7 +193,7 @@ def test_a_single_one_in_the_inputs_returns_hi_plus_lo_of_the_cotangent_row():
                 assert bool((got[k] == 0).all()), (l, r, j, k)
     for r, j in [(37, 0), (s + 5, 62), (n - 1, in_ch - 1)]:  # enc: layers 0 and 5 at once
         enc[r, j] = 1.0
-        got = _flat(ops.mlp_param_grads(enc, H, G, gh, A, ROWS4, precision=SPLIT))
+        got = flat(ops.mlp_param_grads(enc, H, G, gh, A, ROWS4, precision=SPLIT))
         enc[r, j] = 0.0
         for l in (0, 5):
             want = torch.zeros_like(got[l])
@@ -224,8 +214,8 @@ def test_rows_are_matched_with_their_own_rows():
     g = torch.Generator().manual_seed(7)
     G = (torch.rand(8, n, 256, generator=g) < 0.01).float()
     gh = (torch.rand(n, sum(rows), generator=g) < 0.05).float()
-    want = _flat(D.mlp_param_grads(enc[:, : 63 + A].double(), H.double(), G.double(), gh.double(), rows))
-    got = _flat(ops.mlp_param_grads(enc.to(DEV), H.to(DEV), G.to(DEV), gh.to(DEV), A, rows, precision=SPLIT))
+    want = flat(D.mlp_param_grads(enc[:, : 63 + A].double(), H.double(), G.double(), gh.double(), rows))
+    got = flat(ops.mlp_param_grads(enc.to(DEV), H.to(DEV), G.to(DEV), gh.to(DEV), A, rows, precision=SPLIT))
     for k, (a, b) in enumerate(zip(got, want)):
         assert float(b.abs().max()) < 2**24 and torch.equal(a.cpu().double(), b), k
 
@@ -233,7 +223,7 @@ def test_rows_are_matched_with_their_own_rows():
 def test_zero_cotangents_give_exact_zeros():
     A, n = 30, 8193
     enc, H, G, gh = (t.to(DEV) for t in _case(A, ROWS4, n))
-    for out in _flat(ops.mlp_param_grads(enc, H, torch.zeros_like(G), torch.zeros_like(gh), A, ROWS4, precision=SPLIT)):
+    for out in flat(ops.mlp_param_grads(enc, H, torch.zeros_like(G), torch.zeros_like(gh), A, ROWS4, precision=SPLIT)):
         assert bool((out == 0).all())
 
 
@@ -255,31 +245,17 @@ def test_beside_the_fp32_mode(n):
 
 
 # ---- 4. only what is asked for is written, only what belongs is read -----------------------------------------------------
-def _arena(*shape):
-    numel = 1
-    for s in shape:
-        numel *= s
-    flat = torch.full((numel + 2 * GUARD,), NAN, device=DEV)
-    return flat, flat[GUARD : GUARD + numel].view(*shape)
-
-
-def _out_shapes(A, rows):
-    in_ch = 63 + A
-    return ([(256, in_ch if l == 0 else (in_ch + 256 if l == 5 else 256)) for l in range(8)] + [(256,)] * 8
-            + [(r, 256) for r in rows] + [(r,) for r in rows])  # fmt: skip
-
-
 def _entry_point(A, rows, n, want=None):
     """fg_mlp_param_grads_p (FG_MLP_BF16X3) on inputs and outputs carved from NaN-filled arenas: NaN in enc's pad columns and
     directly behind acts[7, n - 1], g_pre[7, n - 1] and g_heads[n - 1] (the guard bands).  Returns (outputs, their arenas)."""
     k = len(rows)
     want = [True] * (16 + 2 * k) if want is None else want
-    ins = [_arena(*t.shape) for t in _case(A, rows, n)]
+    ins = [arena(*t.shape) for t in _case(A, rows, n)]
     for (flat, view), t in zip(ins, _case(A, rows, n)):
         view.copy_(t)
     ins[0][1][:, 63 + A :] = NAN
     before = [flat.clone() for flat, _ in ins]
-    outs = [_arena(*s) for s in _out_shapes(A, rows)]
+    outs = [arena(*s) for s in out_shapes(A, rows)]
     d, g = _lib.MlpDesc(), _lib.MlpGrads()
     d.size, d.mode, d.depth, d.width, d.multires = ctypes.sizeof(_lib.MlpDesc), _lib.MLP_PLAIN, 8, 256, 10
     d.aux_width, d.n_heads, g.size = A, k, ctypes.sizeof(_lib.MlpGrads)
@@ -290,7 +266,7 @@ def _entry_point(A, rows, n, want=None):
         g.weight[i], g.bias[i] = ptr(i), ptr(8 + i)
     for i in range(k):
         g.head_weight[i], g.head_bias[i] = ptr(16 + i), ptr(16 + k + i)
-    ws_flat, ws = _arena(int(_lib.load().fg_mlp_param_grads_workspace_bytes(n)) // 4)
+    ws_flat, ws = arena(int(_lib.load().fg_mlp_param_grads_workspace_bytes(n)) // 4)
     ops._call("fg_mlp_param_grads_p", n, ctypes.addressof(d), *(view.data_ptr() for _, view in ins), ctypes.addressof(g),
               _lib.MLP_BF16X3, ws.data_ptr(), ws.numel() * 4, ops._stream())  # fmt: skip
     torch.cuda.synchronize()
@@ -339,8 +315,8 @@ def test_nullable_outputs(group):
 def test_two_calls_are_bitwise_equal():
     A, n = 30, 8193
     dev = [t.to(DEV) for t in _case(A, ROWS4, n)]
-    first = _flat(ops.mlp_param_grads(*dev, A, ROWS4, precision=SPLIT))
-    again = _flat(ops.mlp_param_grads(*dev, A, ROWS4, precision=SPLIT))
+    first = flat(ops.mlp_param_grads(*dev, A, ROWS4, precision=SPLIT))
+    again = flat(ops.mlp_param_grads(*dev, A, ROWS4, precision=SPLIT))
     for x, y in zip(first, again):
         assert torch.equal(x, y)
 
@@ -352,7 +328,7 @@ def test_capture_and_replay_equal_the_eager_call():
     torch.cuda.synchronize()
     graph = torch.cuda.CUDAGraph()
     with torch.cuda.graph(graph):
-        captured = _flat(ops.mlp_param_grads(*static, A, ROWS4, precision=SPLIT))
+        captured = flat(ops.mlp_param_grads(*static, A, ROWS4, precision=SPLIT))
     # other inputs, written in place: rows n .. 2 n of the same pool
     enc, H, G, gh = _arrays(A)
     fresh = [enc[n : 2 * n], H[:, n : 2 * n], G[:, n : 2 * n], gh[n : 2 * n, : sum(ROWS4)]]
@@ -362,7 +338,7 @@ def test_capture_and_replay_equal_the_eager_call():
         out.fill_(NAN)
     graph.replay()
     torch.cuda.synchronize()
-    eager = _flat(ops.mlp_param_grads(*static, A, ROWS4, precision=SPLIT))
+    eager = flat(ops.mlp_param_grads(*static, A, ROWS4, precision=SPLIT))
     for c, e in zip(captured, eager):
         assert bool(torch.isfinite(c).all()) and torch.equal(c, e)
 
@@ -408,7 +384,7 @@ def _chain_then_products(chain, g_enc, wgrad):
         ge = None
         ws = torch.empty(int(lib.fg_mlp_train_workspace_bytes(n)), dtype=torch.uint8, device=DEV)
         ops._call("fg_mlp_bwd", n, ctypes.addressof(d), gh.data_ptr(), H.data_ptr(), G.data_ptr(), ws.data_ptr(), ws.numel(), ops._stream())
-    return _flat(ops.mlp_param_grads(enc, H, G, gh, A, ROWS4, precision=wgrad)), ge
+    return flat(ops.mlp_param_grads(enc, H, G, gh, A, ROWS4, precision=wgrad)), ge
 
 
 @pytest.mark.parametrize("g_enc", [True, False])
@@ -423,7 +399,7 @@ def test_the_chunked_call_equals_the_two_calls(chain, g_enc):
     for chunk_slabs in (1, 2, 3):
         *grads4, ge = ops.mlp_train_backward(c["enc"], c["H"], c["gh"], c["trunk"], c["heads"], c["A"], ROWS4, want_g_enc=g_enc,
                                              chunk_slabs=chunk_slabs, precision=chain, param_grads_precision=SPLIT)  # fmt: skip
-        for i, (a, b) in enumerate(zip(_flat(grads4), want)):
+        for i, (a, b) in enumerate(zip(flat(grads4), want)):
             assert torch.equal(a, b), (chunk_slabs, i)
         assert (ge is None and want_ge is None) or torch.equal(ge, want_ge), chunk_slabs
 
@@ -432,21 +408,7 @@ def test_the_chunked_call_equals_the_two_calls(chain, g_enc):
 @pytest.fixture
 def spy(monkeypatch):
     """The library calls by name."""
-    seen = []
-    real = ops._call
-    monkeypatch.setattr(ops, "_call", lambda name, *a, **k: (seen.append(name), real(name, *a, **k))[1])
-    return seen
-
-
-def _train_step(m_dev, x, aux, g_heads, **kw):
-    m_dev.requires_grad_(True).zero_grad(set_to_none=True)
-    x = x.detach().clone().requires_grad_(kw.get("input_grads", False))
-    aux = aux.detach().clone().requires_grad_(kw.get("input_grads", False))
-    raw = ops.mlp_train(x, aux, m_dev.linear, heads_of(m_dev), **kw)
-    raw.backward(g_heads)
-    grads = {k: p.grad.detach().clone() for k, p in m_dev.named_parameters() if p.grad is not None}
-    m_dev.requires_grad_(False).zero_grad(set_to_none=True)
-    return raw.detach(), grads, x.grad, aux.grad
+    return lib_calls(monkeypatch)
 
 
 FORMS = {"two_calls": {"fused_param_grads": True},
@@ -467,7 +429,7 @@ def test_through_mlp_train_against_float64(kind, form, spy):
         runs = {}
         for wgrad in ("fp32", SPLIT):
             del spy[:]
-            runs[wgrad] = _train_step(m, x, aux, gh, precision=chain, param_grads_precision=wgrad, **FORMS[form])
+            runs[wgrad] = train_step(m, x, aux, gh, precision=chain, param_grads_precision=wgrad, **FORMS[form])
             assert (spy.count(new_name), spy.count(old_name)) == ((1, 0) if wgrad == SPLIT else (0, 1)), (chain, wgrad, spy)
             raw, grads, g_x, g_aux = runs[wgrad]
             assert set(grads) == set(want) and len(grads) == 2 * (8 + len(head_rows(m)))
@@ -489,28 +451,12 @@ def test_through_mlp_train_against_float64(kind, form, spy):
 
 
 # ---- 8. through the modules ---------------------------------------------------------------------------------------------
-def _module_inputs(kind, n, seed=1):
-    g = torch.Generator().manual_seed(seed)
-    x = torch.rand(n, 3, generator=g) * 2 - 1
-    return x, (torch.randn(n, 3, generator=g) * 0.1 if kind == "control" else torch.rand(n, 1, generator=g))
-
-
-def _grads_of(m):
-    return {k: (None if p.grad is None else p.grad.detach().clone()) for k, p in m.named_parameters()}
-
-
-def _module_step(m_dev, x, other, cots):
-    m_dev.zero_grad(set_to_none=True)
-    loss_of(m_dev(x, other), cots).backward()
-    return _grads_of(m_dev)
-
-
 @pytest.mark.parametrize("kind,train", [("deform", "1"), ("control", "1"), ("blender", "2")])
 def test_modules_with_the_knob_set_and_unset(kind, train, spy, monkeypatch):
     n = D.FUSED_MIN_ROWS + 65
     m = make_net(kind)
     # (both settings form their gradients from the same H and G, bit for bit: no row has to be kept clear of the ReLU's kink)
-    x, other = _module_inputs(kind, n, seed=4)
+    x, other = module_inputs(kind, n, seed=4)
     if kind == "blender":
         other = torch.full((1, 1), BLENDER_TIME).expand(n, -1)
     m_dev = copy.deepcopy(m).to(DEV)
@@ -519,10 +465,10 @@ def test_modules_with_the_knob_set_and_unset(kind, train, spy, monkeypatch):
         monkeypatch.delenv(name, raising=False)
     monkeypatch.setenv("FG_FUSED_MLP_TRAIN", train)
     monkeypatch.setenv("FG_FUSED_MLP_WGRAD", "1")
-    off = _module_step(m_dev, xd, od, cots)
+    off = module_step(m_dev, xd, od, cots)
     assert (spy.count("fg_mlp_param_grads"), spy.count("fg_mlp_param_grads_p")) == (1, 0)
     monkeypatch.setenv("FG_FUSED_MLP_WGRAD_PRECISION", SPLIT)
-    on = _module_step(m_dev, xd, od, cots)
+    on = module_step(m_dev, xd, od, cots)
     assert (spy.count("fg_mlp_param_grads"), spy.count("fg_mlp_param_grads_p")) == (1, 1)
     errs = {k: rel_err(on[k], off[k]) for k in off}
     print(f"mlp_wgrad_split module {kind}: worst {max(errs.values()):.2e}")
@@ -534,7 +480,7 @@ def test_modules_with_the_knob_set_and_unset(kind, train, spy, monkeypatch):
     frozen = [heads_of(m_dev)[1].weight, heads_of(m_dev)[1].bias, m_dev.linear[3].bias]
     for p in frozen:
         p.requires_grad_(False)
-    part = _module_step(m_dev, xd, od, cots)
+    part = module_step(m_dev, xd, od, cots)
     assert spy.count("fg_mlp_param_grads_p") == 2
     names = {id(p): k for k, p in m_dev.named_parameters()}
     for k in on:
@@ -547,9 +493,9 @@ def test_modules_with_the_knob_set_and_unset(kind, train, spy, monkeypatch):
     # without FG_FUSED_MLP_WGRAD the knob does nothing: the library products, the bits of the knob unset
     monkeypatch.delenv("FG_FUSED_MLP_WGRAD")
     calls = len(spy)
-    with_knob = _module_step(m_dev, xd, od, cots)
+    with_knob = module_step(m_dev, xd, od, cots)
     assert "fg_mlp_param_grads_p" not in spy[calls:] and "fg_mlp_param_grads" not in spy[calls:]
     monkeypatch.delenv("FG_FUSED_MLP_WGRAD_PRECISION")
-    without = _module_step(m_dev, xd, od, cots)
+    without = module_step(m_dev, xd, od, cots)
     for k in without:
         assert torch.equal(with_knob[k], without[k]), k

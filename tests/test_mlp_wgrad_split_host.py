@@ -6,7 +6,6 @@ arithmetic of the contract emulated on the CPU (tests/mlp_split_common.py) again
 The emulation's measured errors (``max|a-b| / max|b|`` of the trunk weight gradients over the emulated split chain's arrays,
 1024 rows, against the float64 run of the whole network): three terms 1.2e-5 .. 1.7e-5, two terms 1.7e-3 .. 2.7e-3."""
 import ctypes
-import os
 import re
 import subprocess
 
@@ -17,62 +16,42 @@ from freegaussian_amd import _lib
 from freegaussian_amd import deform as D
 from freegaussian_amd import ops
 from helpers import REL_TOL, rel_err
+from mlp_common import PTR, addr, desc, grads, header_text
 from mlp_split_common import ROWS, case, emulate, product, trunk_weight_grads
 from mlp_train_common import head_rows
 
 OK, INVALID, WORKSPACE, UNSUPPORTED = 0, -1, -3, -4
-PTR, BIG = 4096, 1 << 40  # an address nobody reads (every call below is refused before a launch); a workspace that would do
-ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+BIG = 1 << 40  # a workspace that would do (every call below is refused before a launch)
 FP32, BF16X3 = _lib.MLP_FP32, _lib.MLP_BF16X3
 
 
-def _desc(precision=0, mode=_lib.MLP_PLAIN, A=21, rows=(3, 3, 4, 3)):
-    d = _lib.MlpDesc()
-    d.size, d.mode, d.depth, d.width, d.multires, d.aux_width = ctypes.sizeof(_lib.MlpDesc), mode, 8, 256, 10, A
-    d.n_heads, d.precision = len(rows), precision
-    for i, r in enumerate(rows):
-        d.head_rows[i], d.head_weight[i], d.head_bias[i] = r, PTR, PTR
-    for i in range(8):
-        d.weight[i], d.bias[i] = PTR, PTR
-    return d
-
-
-def _grads(weight=range(8), bias=range(8), head_weight=range(4), head_bias=range(4)):
-    g = _lib.MlpGrads()
-    g.size = ctypes.sizeof(_lib.MlpGrads)
-    for name, which in (("weight", weight), ("bias", bias), ("head_weight", head_weight), ("head_bias", head_bias)):
-        for i in which:
-            getattr(g, name)[i] = PTR
-    return g
-
-
-def _addr(s):
-    return ctypes.addressof(s) if s is not None else None
+def _desc(precision=0, **kw):
+    return desc(precision=precision, **kw)
 
 
 def _pg(n, d, wprec, enc=PTR, acts=PTR, g_pre=PTR, g_heads=PTR, out="all", ws=PTR, ws_bytes=0):
-    out = _grads() if isinstance(out, str) else out
-    return _lib.load().fg_mlp_param_grads_p(n, _addr(d), enc, acts, g_pre, g_heads, _addr(out), wprec, ws, ws_bytes, None)
+    out = grads() if isinstance(out, str) else out
+    return _lib.load().fg_mlp_param_grads_p(n, addr(d), enc, acts, g_pre, g_heads, addr(out), wprec, ws, ws_bytes, None)
 
 
 def _pg_old(n, d, enc=PTR, acts=PTR, g_pre=PTR, g_heads=PTR, out="all", ws=PTR, ws_bytes=0):
-    out = _grads() if isinstance(out, str) else out
-    return _lib.load().fg_mlp_param_grads(n, _addr(d), enc, acts, g_pre, g_heads, _addr(out), ws, ws_bytes, None)
+    out = grads() if isinstance(out, str) else out
+    return _lib.load().fg_mlp_param_grads(n, addr(d), enc, acts, g_pre, g_heads, addr(out), ws, ws_bytes, None)
 
 
 def _tb(n, d, wprec, g_heads=PTR, enc=PTR, acts=PTR, g_enc=PTR, out="all", chunk=0, ws=PTR, ws_bytes=0):
-    out = _grads() if isinstance(out, str) else out
-    return _lib.load().fg_mlp_train_bwd_p(n, _addr(d), g_heads, enc, acts, g_enc, _addr(out), chunk, wprec, ws, ws_bytes, None)
+    out = grads() if isinstance(out, str) else out
+    return _lib.load().fg_mlp_train_bwd_p(n, addr(d), g_heads, enc, acts, g_enc, addr(out), chunk, wprec, ws, ws_bytes, None)
 
 
 def _tb_old(n, d, g_heads=PTR, enc=PTR, acts=PTR, g_enc=PTR, out="all", chunk=0, ws=PTR, ws_bytes=0):
-    out = _grads() if isinstance(out, str) else out
-    return _lib.load().fg_mlp_train_bwd(n, _addr(d), g_heads, enc, acts, g_enc, _addr(out), chunk, ws, ws_bytes, None)
+    out = grads() if isinstance(out, str) else out
+    return _lib.load().fg_mlp_train_bwd(n, addr(d), g_heads, enc, acts, g_enc, addr(out), chunk, ws, ws_bytes, None)
 
 
 # ---- the symbols --------------------------------------------------------------------------------------------------------
 def test_header_binding_and_library_agree_on_the_three_symbols():
-    text = open(os.path.join(ROOT, "include", "fgraster.h")).read()
+    text = header_text()
     code = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     assert re.search(r"int fg_mlp_wgrad_precision_supported\(int32_t precision\);", code)
     assert re.search(r"int fg_mlp_param_grads_p\(int64_t N, const fg_mlp_desc\* desc, const float\* enc, const float\* acts, "
@@ -124,8 +103,8 @@ def test_the_word_is_validated_before_anything_else(call):
 def test_param_grads_p_gives_the_old_calls_codes():
     """Every refusal of tests/test_mlp_wgrad_host.py, for both values of the word, beside the old call's own answer."""
     none = ((), (), (), ())
-    only = lambda **kw: _grads(**{**dict(zip(("weight", "bias", "head_weight", "head_bias"), none)), **kw})  # noqa: E731
-    short_d, short_g = _desc(), _grads()
+    only = lambda **kw: grads(**{**dict(zip(("weight", "bias", "head_weight", "head_bias"), none)), **kw})  # noqa: E731
+    short_d, short_g = _desc(), grads()
     short_d.size -= 8
     short_g.size -= 8
     need = int(_lib.load().fg_mlp_param_grads_workspace_bytes(100))
@@ -138,9 +117,9 @@ def test_param_grads_p_gives_the_old_calls_codes():
         (dict(n=100, d=short_d), INVALID),
         (dict(n=100, d=_desc(), out=None, ws_bytes=BIG), INVALID),
         (dict(n=100, d=_desc(), out=short_g, ws_bytes=BIG), INVALID),
-        (dict(n=100, d=_desc(), enc=None, acts=None, g_pre=None, g_heads=None, out=_grads(*none), ws=None), OK),
-        (dict(n=100, d=_desc(), enc=None, out=_grads(weight=(0,)), ws_bytes=BIG), INVALID),
-        (dict(n=100, d=_desc(), enc=None, out=_grads(weight=(1, 2, 3, 4, 6, 7))), WORKSPACE),
+        (dict(n=100, d=_desc(), enc=None, acts=None, g_pre=None, g_heads=None, out=grads(*none), ws=None), OK),
+        (dict(n=100, d=_desc(), enc=None, out=grads(weight=(0,)), ws_bytes=BIG), INVALID),
+        (dict(n=100, d=_desc(), enc=None, out=grads(weight=(1, 2, 3, 4, 6, 7))), WORKSPACE),
         (dict(n=100, d=_desc(), acts=None, out=only(weight=(5,)), ws_bytes=BIG), INVALID),
         (dict(n=100, d=_desc(), g_pre=None, out=only(bias=(3,)), ws_bytes=BIG), INVALID),
         (dict(n=100, d=_desc(), g_heads=None, out=only(head_bias=(1,)), ws_bytes=BIG), INVALID),
@@ -162,7 +141,7 @@ def test_param_grads_p_gives_the_old_calls_codes():
 
 def test_train_bwd_p_gives_the_old_calls_codes():
     none = ((), (), (), ())
-    short_g = _grads()
+    short_g = grads()
     short_g.size -= 8
     no_weight = _desc()
     no_weight.weight[3] = None
@@ -176,7 +155,7 @@ def test_train_bwd_p_gives_the_old_calls_codes():
         (dict(n=100, d=no_weight, ws_bytes=BIG), INVALID),
         (dict(n=100, d=_desc(), out=None, ws_bytes=BIG), INVALID),
         (dict(n=100, d=_desc(), out=short_g, ws_bytes=BIG), INVALID),
-        (dict(n=100, d=_desc(), g_heads=None, enc=None, acts=None, g_enc=None, out=_grads(*none), ws=None), OK),
+        (dict(n=100, d=_desc(), g_heads=None, enc=None, acts=None, g_enc=None, out=grads(*none), ws=None), OK),
         (dict(n=100, d=_desc(), g_heads=None, ws_bytes=BIG), INVALID),
         (dict(n=100, d=_desc(), acts=None, ws_bytes=BIG), INVALID),
         (dict(n=100, d=_desc(), enc=None, ws_bytes=BIG), INVALID),
