@@ -132,10 +132,15 @@ SIGNATURES = {
     "fg_bilagrid_slice_fwd": (c_int, [c_int, c_int, c_int, c_int, c_int, P, P, P, P]),  # (H, W, GX, GY, GL, grid, rgb, out, stream)
     # (H, W, GX, GY, GL, grid, rgb, v_out, v_rgb, v_grid, workspace, bytes, stream)
     "fg_bilagrid_slice_bwd": (c_int, [c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P, c_size_t, P]),
+    # the iterated colour-correction fit of the metrics, on the device (csrc/color_correct.hip)
+    "fg_color_correct_workspace_bytes": (c_size_t, [c_int64, c_int]),  # (P, num_iters)
+    # (P, img, ref, num_iters, eps, out, warps, rank, workspace, bytes, stream)
+    "fg_color_correct": (c_int, [c_int64, P, P, c_int, c_double, P, P, P, P, c_size_t, P]),
 }  # fmt: skip
 
 # test hooks, not declared in the public header
-_EXTRA = {"fg_debug_wave_reduce16": (c_int, [P, P, P]), "fg_debug_knn_grid": (c_int, [c_int64, P, c_int, P, P])}
+_EXTRA = {"fg_debug_wave_reduce16": (c_int, [P, P, P]), "fg_debug_knn_grid": (c_int, [c_int64, P, c_int, P, P]),
+          "fg_debug_color_correct_solve": (c_int, [P, P, P, P])}  # (G[10,10], r[10], w[10], rank[1]): host float64
 
 ABI_VERSION = 14
 ABI_MINOR = 1  # FG_ABI_MINOR: the least the binding needs (symbols added without raising FG_ABI_VERSION)
@@ -146,6 +151,7 @@ MLP_SE3, MLP_PLAIN = 0, 1  # FG_MLP_SE3, FG_MLP_PLAIN
 MLP_FP32, MLP_BF16X3 = 0, 1  # FG_MLP_FP32, FG_MLP_BF16X3: fg_mlp_desc::precision
 MLP_WGRAD_MAX_SLAB, MLP_WGRAD_MIN_SPLIT = 4096, 512  # FG_MLP_WGRAD_MAX_SLAB, FG_MLP_WGRAD_MIN_SPLIT
 MLP_TRAIN_BWD_CHUNK_SLABS = 16  # FG_MLP_TRAIN_BWD_CHUNK_SLABS
+COLOR_CORRECT_MAX_ITERS = 8  # FG_COLOR_CORRECT_MAX_ITERS
 
 
 def mlp_enc_width(aux_width: int) -> int:

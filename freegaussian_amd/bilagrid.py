@@ -15,8 +15,10 @@ Torch ops by default: an image-sized ``grid_sample`` plus a 3x4 multiply per pix
 default.  ``FG_FUSED_BILAGRID=1`` (opt-in) sends ``apply_to_render`` -- the slice of a whole rendered image, the one use on
 the training path -- through ``ops.bilagrid_apply`` instead (csrc/bilagrid.hip: one streaming launch forward, the grid
 gradient as a gather with a fixed order of addition, no per-pixel matrices in memory; measured in
-profiles/bilagrid_fused.md).  ``slice`` at free coordinates, ``color_correct`` and ``total_variation_loss`` are torch ops
-either way."""
+profiles/bilagrid_fused.md).  ``FG_FUSED_COLOR_CORRECT=1`` (opt-in) sends ``color_correct`` -- the metric-side fit, whose
+torch statement copies fifteen float64 feature matrices to the host per image -- through ``ops.color_correct`` instead
+(csrc/color_correct.hip: the normal equations summed on the device, measured in profiles/color_correct_fused.md).  ``slice``
+at free coordinates and ``total_variation_loss`` are torch ops either way."""
 from __future__ import annotations
 
 import os
@@ -134,12 +136,49 @@ def apply_to_render(bil_grids: BilateralGrid, rgb: torch.Tensor, cam_idx: int, H
     return slice(bil_grids, grid_xy, rgb, torch.tensor([int(cam_idx)], device=dev, dtype=torch.long))["rgb"]
 
 
+def fused_color_correct() -> bool:
+    """``FG_FUSED_COLOR_CORRECT`` (opt-in; read here and nowhere else, on the host, on every call): unset or ``0`` = the torch
+    ops, ``1`` = the fused fit where it applies.  Anything else is an error, not a silent default."""
+    knob = os.environ.get("FG_FUSED_COLOR_CORRECT", "0")
+    if knob not in ("0", "1"):
+        raise ValueError(f"FG_FUSED_COLOR_CORRECT wants 0 or 1, got {knob!r}")
+    return knob == "1"
+
+
+def fused_color_correct_applies(img: torch.Tensor, ref: torch.Tensor, num_iters, eps) -> bool:
+    """Does ``color_correct`` take the fused call for this pair?  Only with the knob set, CUDA float32 tensors of one shape
+    on one device, 3 channels, arguments in the range the library takes, and nothing that wants a gradient."""
+    if not fused_color_correct():
+        return False
+    if not (img.is_cuda and ref.is_cuda and img.device == ref.device and img.dtype == torch.float32 and ref.dtype == torch.float32):
+        return False
+    if img.dim() < 1 or img.shape != ref.shape or img.shape[-1] != 3 or img.numel() == 0:
+        return False
+    if torch.is_grad_enabled() and (img.requires_grad or ref.requires_grad):
+        return False
+    from . import ops
+
+    return ops.color_correct_supported(img.numel(), num_iters, eps)
+
+
 def color_correct(img: torch.Tensor, ref: torch.Tensor, num_iters: int = 5, eps: float = 0.5 / 255) -> torch.Tensor:
     """Warp ``img`` to match the colours of ``ref`` with a per-channel quadratic colour transform fitted by least
     squares on the pixels that are unclipped in both, re-fitted ``num_iters`` times (the metric-side correction of the
-    bilateral-grid paper, after mip-NeRF 360's)."""
+    bilateral-grid paper, after mip-NeRF 360's).
+
+    With ``FG_FUSED_COLOR_CORRECT=1`` and tensors the fused call takes (``fused_color_correct_applies``):
+    ``ops.color_correct``, the same iteration with each fit solved from its float64 normal equations on the device (the
+    contract is in include/fgraster.h).  The two agree within the parity bar where every fit has full rank.  They DIFFER
+    where the feature matrix has exactly zero columns (an image channel that is 0 everywhere): there the default driver of
+    ``torch.linalg.lstsq`` below (gelsy) reports rank 1 and returns something that is not a least-squares solution, while
+    the fused path returns a least-squares fit (zero weights on the zero columns).  On a grey image (r = g = b) the
+    fits are rank 3 and then near-deficient, and no two solvers agree: no parity is claimed there."""
     if img.shape[-1] != ref.shape[-1]:
         raise ValueError(f"img's {img.shape[-1]} and ref's {ref.shape[-1]} channels must match")
+    if fused_color_correct_applies(img, ref, num_iters, eps):
+        from . import ops
+
+        return ops.color_correct(img, ref, num_iters=num_iters, eps=eps)
     C = img.shape[-1]
     x = img.reshape(-1, C)
     y = ref.reshape(-1, C)

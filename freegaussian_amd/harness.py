@@ -148,3 +148,47 @@ def train_step(model: FreeGaussianModel, opts, camera: Camera, gt_image: torch.T
         if gt is None:
             gt = model.composite_with_background(model.get_gt_img(gt_image), out["background"])
         return {"loss": float(loss), "psnr": float(psnr(out["rgb"], gt)), "gaussian_count": model.num_points}
+
+
+def eval_image(model: FreeGaussianModel, camera: Camera, batch: Dict[str, torch.Tensor]):
+    """(freegaussian_pipeline.py:85-100, get_eval_image_metrics_and_images) one evaluation view: eval mode, the render of
+    ``camera`` through ``get_outputs_for_camera``, ``model.get_image_metrics_and_images`` against ``batch`` ({"image": ...}),
+    ``num_rays`` added, training mode again.  Returns (metrics, images)."""
+    model.eval()
+    outputs = model.get_outputs_for_camera(camera)
+    metrics, images = model.get_image_metrics_and_images(outputs, batch)
+    assert "num_rays" not in metrics
+    metrics["num_rays"] = int(camera.height) * int(camera.width)
+    model.train()
+    return metrics, images
+
+
+def average_image_metrics(model: FreeGaussianModel, views, get_std: bool = False) -> Dict[str, float]:
+    """(freegaussian_pipeline.py:103-172, get_average_image_metrics, without the image writing and the progress bar) the
+    mean over ``views`` -- an iterable of (camera, batch) -- of ``model.get_image_metrics_and_images``, with
+    ``num_rays_per_sec`` and ``fps`` from the wall clock around render plus metrics as the reference takes them; ``get_std``
+    adds a ``<key>_std`` (torch.std_mean: the unbiased one) per key.  Eval mode inside, training mode afterwards."""
+    from time import time
+
+    model.eval()
+    per_view = []
+    for camera, batch in views:
+        start = time()
+        outputs = model.get_outputs_for_camera(camera)
+        num_rays = int(camera.height) * int(camera.width)
+        metrics, _ = model.get_image_metrics_and_images(outputs, batch)  # (its float() reads wait for the GPU)
+        assert "num_rays_per_sec" not in metrics and "fps" not in metrics
+        metrics["num_rays_per_sec"] = num_rays / max(time() - start, 1e-12)
+        metrics["fps"] = metrics["num_rays_per_sec"] / num_rays
+        per_view.append(metrics)
+    assert per_view, "no views to evaluate"
+    out: Dict[str, float] = {}
+    for key in per_view[0]:
+        vals = torch.tensor([m[key] for m in per_view])
+        if get_std:
+            std, mean = torch.std_mean(vals)
+            out[key], out[f"{key}_std"] = float(mean), float(std)
+        else:
+            out[key] = float(torch.mean(vals))
+    model.train()
+    return out

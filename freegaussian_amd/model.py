@@ -291,6 +291,31 @@ class FreeGaussianModel(nn.Module):
         metrics["gaussian_count"] = self.num_points
         return metrics
 
+    @torch.no_grad()
+    def get_image_metrics_and_images(self, outputs, batch):
+        """(:1005-1051) the evaluation metrics of one rendered image against its composited ground truth, as Python floats,
+        and the side-by-side image: ({"psnr", "ssim"[, "cc_psnr", "cc_ssim"]}, {"img": [H, 2W, 3]}).  PSNR as
+        ``get_metrics_dict`` computes it; SSIM through ``harness.l1_and_ssim`` (the fused kernel on the GPU, ``harness.ssim``
+        on the host: the definition of the reference's pytorch_msssim callable); the colour-corrected pair with
+        ``config.color_corrected_metrics``, through ``bilagrid.color_correct`` (``FG_FUSED_COLOR_CORRECT`` decides its path).
+        **LPIPS is not mirrored**: the reference's third metric needs the ``lpips`` / ``torchmetrics`` packages and the
+        weights of a trained network, none of which this project ships; the ``lpips`` and ``cc_lpips`` keys are absent,
+        not faked."""
+        from .harness import l1_and_ssim
+
+        gt_rgb = self.composite_with_background(self.get_gt_img(batch["image"]), outputs["background"])
+        predicted_rgb = outputs["rgb"].detach()
+        combined_rgb = torch.cat([gt_rgb, predicted_rgb], dim=1)
+        mse = torch.nn.functional.mse_loss(predicted_rgb, gt_rgb)
+        metrics = {"psnr": float((-10.0 * torch.log10(mse)).item()), "ssim": float(l1_and_ssim(predicted_rgb, gt_rgb)[1])}
+        if self.config.color_corrected_metrics:  # (:1024-1026, :1040-1047)
+            from .bilagrid import color_correct
+
+            cc_rgb = color_correct(predicted_rgb, gt_rgb)
+            metrics["cc_psnr"] = float((-10.0 * torch.log10(torch.nn.functional.mse_loss(cc_rgb, gt_rgb))).item())
+            metrics["cc_ssim"] = float(l1_and_ssim(cc_rgb, gt_rgb)[1])
+        return metrics, {"img": combined_rgb}
+
     def get_loss_dict(self, outputs, batch, metrics_dict=None):
         """(:944-990) main loss (1 - ssim_lambda) L1 + ssim_lambda (1 - SSIM) on the composited ground truth, the
         optional mask (both images blacked out), the optional scale-ratio regulariser on every 10th step, and while

@@ -1261,6 +1261,47 @@ def bilagrid_apply(grids: torch.Tensor, cam_idx: int, rgb: torch.Tensor) -> torc
     return _BilagridApply.apply(_f32(grids, "grids"), cam_idx, _f32(rgb, "rgb"))
 
 
+def color_correct_supported(numel: int, num_iters, eps) -> bool:
+    """Does ``color_correct`` take ``numel // 3`` pixels with these arguments?  The library's own range (its query says) and
+    the header's 0 < eps < 0.5."""
+    if isinstance(num_iters, bool) or not isinstance(num_iters, int) or not isinstance(eps, (int, float)):
+        return False
+    if not (1 <= num_iters <= _lib.COLOR_CORRECT_MAX_ITERS and 0.0 < float(eps) < 0.5) or numel < 3:
+        return False
+    return _lib.load().fg_color_correct_workspace_bytes(numel // 3, num_iters) > 0
+
+
+@torch.no_grad()
+def color_correct(img: torch.Tensor, ref: torch.Tensor, num_iters: int = 5, eps: float = 0.5 / 255, return_info: bool = False):
+    """``img`` [..., 3] warped to the colours of ``ref`` (same shape): what ``bilagrid.color_correct`` states in torch ops, as
+    ``num_iters + 1`` passes over the image and ``num_iters`` 10 x 10 solves on the device (csrc/color_correct.hip; the
+    contract is in include/fgraster.h).  Nothing is read back: the call is asynchronous on the current stream.  No
+    gradient.  ``return_info``: also ``{"warps": [num_iters,10,3] float32, "rank": [num_iters,3] int32}`` as device tensors
+    (rank = the eigenvalues each fit kept; -1 where a weight is not finite -- the output then carries the NaN)."""
+    if img.dim() < 1 or img.shape[-1] != 3 or img.shape != ref.shape or img.numel() == 0:
+        raise ValueError(f"two [...,3] images of one shape expected, got {tuple(img.shape)} and {tuple(ref.shape)}")
+    if not (img.is_cuda and ref.is_cuda):
+        raise _lib.FgRasterError("color_correct runs on the GPU only (bilagrid.color_correct is the torch statement of it)")
+    if img.dtype != torch.float32 or ref.dtype != torch.float32 or img.device != ref.device:
+        raise ValueError(f"float32 tensors on one device expected, got {img.dtype} on {img.device} and {ref.dtype} on {ref.device}")
+    if not color_correct_supported(img.numel(), num_iters, eps):
+        raise ValueError(f"num_iters {num_iters!r} / eps {eps!r} / {img.numel() // 3} pixels outside what the fused colour correction takes "
+                         f"(1 .. {_lib.COLOR_CORRECT_MAX_ITERS} iterations, 0 < eps < 0.5)")  # fmt: skip
+    x, y = img.detach().contiguous(), ref.detach().contiguous()
+    P = x.numel() // 3
+    out = torch.empty_like(x)
+    warps = rank = None
+    if return_info:
+        warps = torch.empty(num_iters, 10, 3, dtype=torch.float32, device=x.device)
+        rank = torch.empty(num_iters, 3, dtype=torch.int32, device=x.device)
+    n_ws = int(_lib.load().fg_color_correct_workspace_bytes(P, num_iters))
+    ws = torch.empty(n_ws, dtype=torch.uint8, device=x.device)
+    _call("fg_color_correct", P, _ptr(x), _ptr(y), num_iters, float(eps), _ptr(out), _ptr(warps), _ptr(rank), _ptr(ws), n_ws,
+          _stream(), stage="fg_color_correct")  # fmt: skip
+    out = out.reshape(img.shape)
+    return (out, {"warps": warps, "rank": rank}) if return_info else out
+
+
 @torch.no_grad()
 def isect_keys(tile_keys, flatten_ids, depths):
     """Reference-style 64-bit keys (tile << 32 | depth bits) of the sorted list."""

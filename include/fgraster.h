@@ -51,7 +51,9 @@ typedef void* fg_stream_t;
  * computes in fp32.  Likewise BY NAME: fg_mlp_wgrad_precision_supported, fg_mlp_param_grads_p and fg_mlp_train_bwd_p -- a
  * library without them forms the weight gradients in exact fp32 through fg_mlp_param_grads / fg_mlp_train_bwd.  Likewise BY
  * NAME: fg_bilagrid_supported, fg_bilagrid_bwd_workspace_bytes, fg_bilagrid_slice_fwd and fg_bilagrid_slice_bwd -- a library
- * without them has no fused bilateral-grid slice, and the host keeps its torch statement of it.) */
+ * without them has no fused bilateral-grid slice, and the host keeps its torch statement of it.  Likewise BY NAME:
+ * fg_color_correct_workspace_bytes and fg_color_correct -- a library without them has no fused colour correction of the
+ * metrics, and the host keeps its torch statement of it.) */
 #define FG_COUNT_OUT_WORDS 16 /* int64 words of a count_out block (fg_stbin_count, fg_step_io): ABI 9 */
 
 int fg_abi_version(void);
@@ -1087,6 +1089,51 @@ int fg_bilagrid_slice_fwd(int H, int W, int GX, int GY, int GL, const float* gri
                           fg_stream_t stream);
 int fg_bilagrid_slice_bwd(int H, int W, int GX, int GY, int GL, const float* grid, const float* rgb, const float* v_out,
                           float* v_rgb, float* v_grid, void* workspace, size_t workspace_bytes, fg_stream_t stream);
+
+/* ---- CC colour correction of the metrics (found BY NAME, see FG_ABI_MINOR): `img` warped to the colours of `ref` by a
+ * per-channel quadratic colour transform, fitted by least squares on the pixels unclipped in both and re-fitted num_iters
+ * times (csrc/color_correct.hip; freegaussian_amd/bilagrid.py color_correct is the torch statement), with no host round trip.
+ *   img, ref, out [P, 3] float32;  warps [num_iters, 10, 3] float32 and rank [num_iters, 3] int32: either may be null.
+ *   lo = (float)eps,  hi = (float)(1.0 - eps),  unclipped(z) = z >= lo && z <= hi  (fp32 comparisons: what torch does with a
+ *   float32 tensor and a Python scalar; tests/test_color_correct_host.py decides it against the torch path).
+ *   x_0 = img,  mask0[p, c] = unclipped(img[p, c]).  Iteration k = 0 .. num_iters - 1:
+ *     a(x) = [x0 x0, x0 x1, x0 x2, x1 x1, x1 x2, x2 x2, x0, x1, x2, 1]: the quadratic terms are fp32 products, widened to
+ *            float64 afterwards (torch forms the feature matrix in fp32 before .double());
+ *     per channel c, over the pixels with  m = mask0[p, c] && unclipped(x_k[p, c]) && unclipped(ref[p, c]):
+ *            G_c = sum a a^T,  r_c = sum a ref[p, c],  products and sums in float64;
+ *     w_c  = D^-1/2 pinv(D^-1/2 G_c D^-1/2) D^-1/2 r_c,  D = diag(G_c): the pseudo-inverse through the eigen-decomposition
+ *            (cyclic Jacobi, float64) of the unit-diagonal Gram, eigenvalues at or below FG_COLOR_CORRECT_RCOND times the
+ *            largest dropped.  A zero diagonal (a zero feature column) gives w_i = 0; G_c = 0 (no unmasked pixel) gives
+ *            w_c = 0.  w_c is stored as float32 -> warps[k, :, c];  rank[k, c] = the eigenvalues kept, -1 where a weight is
+ *            not finite (the device cannot assert as the torch path does: out then carries the NaN).
+ *     x_{k+1} = clamp(a(x_k) . [w_0 w_1 w_2], 0, 1) for EVERY pixel, fp32 accumulation in feature order.
+ *   out = x_{num_iters}.
+ *   Where G_c has full rank, w_c is the least-squares fit.  Where it has not, w_c is a least-squares fit -- the one of
+ *   least norm in the column-scaled variables D^1/2 w -- with the fitted values every least-squares solution has on the
+ *   unmasked pixels.  torch.linalg.lstsq's default driver on the device-to-host path of the torch statement (gelsy) returns
+ *   something that is NOT a least-squares solution where the feature matrix has exactly zero columns (an image channel that
+ *   is 0 everywhere): the two paths differ there, and this one is the fit.
+ *   No atomics: a workgroup sums a chunk of pixels on the float64 matrix instruction and writes one partial block; the
+ *   solve launch adds the blocks in a fixed order.  Two runs are bit for bit equal.  No intermediate image: pass k
+ *   recomputes x_k from img through the k warps already solved, so the call makes num_iters + 1 passes over the image and
+ *   reads only img and ref.
+ *   A chunk is FG_COLOR_CORRECT_CHUNK_PIXELS pixels while that makes at most FG_COLOR_CORRECT_MAX_CHUNKS chunks; beyond, it is
+ *   ceil(P / FG_COLOR_CORRECT_MAX_CHUNKS) rounded up to a multiple of 256.  fg_color_correct_workspace_bytes = 2048 +
+ *   min(ceil(P / FG_COLOR_CORRECT_CHUNK_PIXELS), FG_COLOR_CORRECT_MAX_CHUNKS) * 3 * 128 * 8: pure, monotone in P, and 0 for
+ *   anything unsupported.  workspace: 16-byte aligned.
+ *   Supported: 1 <= P <= 16384 * 16384, 1 <= num_iters <= FG_COLOR_CORRECT_MAX_ITERS, 0 < eps < 0.5.
+ *   FG_ERR_INVALID_ARG: a null img / ref / out, an output (out, warps, rank) that overlaps an input, another output or the
+ *   workspace, a workspace that overlaps an input, a null or misaligned workspace;  FG_ERR_UNSUPPORTED: P, num_iters or eps
+ *   outside the range above;  FG_ERR_WORKSPACE: workspace_bytes below the query.  All before any launch.  Byte offsets
+ *   are 64-bit.  Asynchronous (no host read anywhere), capturable in a graph, no state, no environment.
+ *   Measured (profiles/color_correct_fused.md). */
+#define FG_COLOR_CORRECT_MAX_ITERS 8
+#define FG_COLOR_CORRECT_CHUNK_PIXELS 4096
+#define FG_COLOR_CORRECT_MAX_CHUNKS 2048
+#define FG_COLOR_CORRECT_RCOND 1e-12
+size_t fg_color_correct_workspace_bytes(int64_t P, int num_iters);
+int fg_color_correct(int64_t P, const float* img, const float* ref, int num_iters, double eps, float* out, float* warps,
+                     int32_t* rank, void* workspace, size_t workspace_bytes, fg_stream_t stream);
 
 #ifdef __cplusplus
 }
