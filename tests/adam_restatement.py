@@ -13,12 +13,14 @@ test; nothing of the package under test is imported here.
     MUTANTS             wrong restatements (float64, CPU only: they prove that the bound has teeth)
 
 ELEMENT DISTANCE.  |x - x64| / denominator.  m' = m + w1 (g - m) cancels where g is close to m; p' is p plus an update that
-is far below p's own rounding when the learning rate is small.
+is far below p's own rounding when the learning rate is small.  tests/parity_common.py has the protocol.
 """
 import math
 from typing import Dict, Optional, Tuple
 
 import torch
+
+import parity_common as P
 
 # Floor of the fp32 yardstick E32.  The other suites floor theirs at 16 * 2^-24: their rows are sums of hundreds of terms.
 # Here an output is an elementwise expression of two to ten roundings, the fp32 restatement is often exact to the last
@@ -100,43 +102,11 @@ def regime_tensor(n: int, seed: int = 0) -> Tuple[torch.Tensor, torch.Tensor, to
     return p.contiguous(), g.contiguous(), m.contiguous(), v.contiguous(), regime
 
 
-def element_distance(x, x64, den) -> torch.Tensor:
-    """|x - x64| / den per element, float64; 0 where the difference is exactly zero, inf where x is not finite or only the
-    denominator is zero."""
-    x, x64, den = (t.detach().cpu().double().reshape(-1) for t in (x, x64, den))
-    diff = (x - x64).abs()
-    d = torch.where(diff == 0, torch.zeros_like(diff), torch.where(den > 0, diff / den, torch.full_like(diff, math.inf)))
-    return torch.where(torch.isfinite(x), d, torch.full_like(d, math.inf))
-
-
-def distances(out, out64, den) -> Dict[str, torch.Tensor]:
-    return {k: element_distance(x, x64, den[k]) for k, x, x64 in zip(OUTPUTS, out, out64)}
-
-
-def yardstick(regime: torch.Tensor, d32: Dict[str, torch.Tensor]) -> Dict[Tuple[str, str], float]:
-    """E32 per (regime, output): the largest element distance of the fp32 restatement over the regime's elements, floored."""
-    out = {}
-    for i, name in enumerate(REGIMES):
-        sel = regime == i
-        if bool(sel.any()):
-            for k in OUTPUTS:
-                out[(name, k)] = max(float(d32[k][sel].max()), FLOOR)
-    return out
-
-
-def worst_ratios(regime: torch.Tensor, d: Dict[str, torch.Tensor], e32) -> Dict[Tuple[str, str], Tuple[float, int]]:
-    """Per (regime, output): (largest d / E32, the element)."""
-    out = {}
-    for (name, k), e in e32.items():
-        masked = torch.where(regime == REGIMES.index(name), d[k], torch.full_like(d[k], -1.0))
-        at = int(masked.argmax())
-        out[(name, k)] = (float(masked[at]) / e, at)
-    return out
-
-
 def reference(p, g, m, v, regime, lr, step, beta1=BETA1, beta2=BETA2, eps=EPS):
-    """-> (out64, denominators, E32 per (regime, output)) of one update of the given pre-state."""
+    """-> (out64, denominators, E32[output][regime]) of one update of the given pre-state."""
     out64 = update(p, g, m, v, lr, beta1, beta2, eps, step, torch.float64)
     out32 = update(p, g, m, v, lr, beta1, beta2, eps, step, torch.float32)
     den = denominators(p, g, m, v, out64, lr, beta1, beta2, eps, step)
-    return out64, den, yardstick(regime, distances(out32, out64, den))
+    masks = P.masks_of_index(regime, REGIMES)
+    d32 = {k: P.distance(x32, x64, den[k]) for k, x32, x64 in zip(OUTPUTS, out32, out64)}
+    return out64, den, {k: P.yardstick(masks, d32[k], FLOOR) for k in OUTPUTS}

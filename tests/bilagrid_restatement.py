@@ -8,7 +8,7 @@ autograd of apply_to_render to 3e-7 (the weights' own rounding).
 
     case(...), forward, backward, clear_of_knife_edges     what tests/test_bilagrid_fused_*.py use: the array-wide bar
 
-PER ELEMENT (tests/test_bilagrid_elements_*.py), following tests/loss_restatement.py:
+PER ELEMENT (tests/test_bilagrid_elements_*.py), by the protocol of tests/parity_common.py:
 
     restate(grid, rgb, v_out, dtype)   out, v_rgb, v_grid in float64 or float32 (plain numpy, CPU) -- beside each its
                            ABSOLUTE ACCUMULATION A, every term by magnitude:
@@ -19,16 +19,16 @@ PER ELEMENT (tests/test_bilagrid_elements_*.py), following tests/loss_restatemen
                            t = p (n-1) / (S-1) - cell from ONE division: t is exactly 0 on a node and exactly 1 on the last
                            pixel, in either dtype, so which nodes a pixel reaches does not depend on rounding.  The
                            float64 variant takes the fp32 inputs exactly.
-    regime_case(...)       inputs, both restatements, the regime masks of pixels and grid nodes, E32 per (array, regime)
-    element_distance       |x - x64| / A64; a node no pixel reaches has A = 0 and must be exactly 0.0
-    yardstick              E32(regime, array): the largest distance of the fp32 restatement over the regime's elements,
-                           floored at 16 * 2^-24
+    regime_case(...)       inputs, both restatements, the regime masks of pixels and grid nodes, E32 per (array, regime);
+                           a node no pixel reaches has A = 0 and must be exactly 0.0
     MUTANTS                wrong restatements (float64, CPU only: they prove that the bound has teeth)
 """
 import functools
 from typing import Optional
 
 import numpy as np
+
+import parity_common as P
 
 LUMA = np.array([np.float32(0.299), np.float32(0.587), np.float32(0.114)], dtype=np.float64)
 
@@ -411,36 +411,6 @@ def node_regimes(reach, reach_big):
     return {k: m[k] for k in NODE_REGIMES if m[k].any()}
 
 
-def element_distance(x, x64, a64):
-    """|x - x64| / A64 per element, float64; 0 where both the difference and the accumulation are exactly zero, inf where
-    only the accumulation is (or where x is not finite)."""
-    x, x64, a64 = (np.asarray(a, dtype=np.float64) for a in (x, x64, a64))
-    diff = np.abs(x - x64)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        d = np.where(a64 > 0, diff / a64, np.where(diff == 0, 0.0, np.inf))
-    return np.where(np.isfinite(x), d, np.inf)
-
-
-def _of(mask, d):
-    """The elements of d ([H,W,3] for a pixel mask [H,W], [12,GL,GY,GX] for a node mask [GL,GY,GX]) under the mask."""
-    return d[mask] if d.shape[:2] == mask.shape else d[:, mask]
-
-
-def yardstick(masks, d32):
-    """E32 per regime: the largest element distance of the fp32 restatement over the regime's elements, floored."""
-    return {name: max(float(_of(mask, d32).max()), FLOOR) for name, mask in masks.items()}
-
-
-def worst_ratios(masks, d, e32):
-    """Per regime: (largest d / E32, where)."""
-    out = {}
-    for name, mask in masks.items():
-        full = mask[..., None] if d.shape[:2] == mask.shape else mask[None]
-        at = int(np.where(full, d, -1.0).argmax())
-        out[name] = (float(d.reshape(-1)[at]) / e32[name], tuple(int(i) for i in np.unravel_index(at, d.shape)))
-    return out
-
-
 @functools.lru_cache(maxsize=None)
 def regime_case(H, W, GX, GY, GL, num=1, cam=0, kind="noise", seed=0):
     """One shape of SHAPES: inputs (``existing``: those of ``case``), the float64 restatement (r64), the regime masks of pixels
@@ -456,7 +426,7 @@ def regime_case(H, W, GX, GY, GL, num=1, cam=0, kind="noise", seed=0):
     pix = pixel_regimes(rgb, H, W, GX, GY, GL, kind == "coherent")
     nod = node_regimes(r64["reach"], r64["reach_big"])
     masks = {"out": pix, "v_rgb": pix, "v_grid": nod}
-    e32 = {a: yardstick(masks[a], element_distance(r32[a], r64[a], r64[a + "_acc"])) for a in ARRAYS}
+    e32 = {a: P.yardstick(masks[a], P.distance(r32[a], r64[a], r64[a + "_acc"]), FLOOR) for a in ARRAYS}
     res = {"grids": grids, "rgb": rgb, "v_out": v_out, "placed": placed, "cam": cam, "r64": r64, "r32": r32, "masks": masks, "e32": e32,
            "tag": f"{H}x{W} ({GX},{GY},{GL})" + ("" if kind == "noise" else " " + kind)}  # fmt: skip
     for d in (res, r64, r32, pix, nod):

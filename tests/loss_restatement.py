@@ -11,12 +11,12 @@ image of labelled blocks.  A helper, not a test; nothing of the package under te
     MUTANTS                wrong restatements (float64, CPU only: they prove that the bound has teeth)
 
 ELEMENT DISTANCE.  |g - g64| / A64.  The gradient of a flat pixel is a sum that cancels: on the white-equal block |g64| is
-about 1e-7 while the terms are about 2e3 x 7e-5.  Cancellation acts at the scale of A, not of |g|.
+about 1e-7 while the terms are about 2e3 x 7e-5.  Cancellation acts at the scale of A, not of |g|.  tests/parity_common.py
+has the protocol.
 
 The float64 variant takes the fp32 inputs (images, window taps, cotangents) exactly; the fp32 variant rounds the two
 divisors to float as the kernel does.
 """
-import math
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -187,48 +187,3 @@ def gradients(pred, gt, dtype, mutant: Optional[str] = None, groups=GROUPS, w2d=
     """-> (forward, {group: (grad, A)}) of the restatement in ``dtype``."""
     fwd = forward(pred, gt, dtype, mutant, w2d)
     return fwd, {g: backward(pred, gt, fwd, *COTANGENTS[g], dtype, mutant, w2d) for g in groups}
-
-
-# ---------------------------------------------------------------------------------------------------------------------
-# distances and yardsticks
-
-
-def element_distance(g: torch.Tensor, g64: torch.Tensor, a64: torch.Tensor) -> torch.Tensor:
-    """|g - g64| / A64 per element, float64; 0 where both the difference and the accumulation are exactly zero, inf where
-    only the accumulation is (or where g is not finite)."""
-    g, g64, a64 = (t.detach().cpu().double() for t in (g, g64, a64))
-    diff = (g - g64).abs()
-    d = torch.where(a64 > 0, diff / a64, torch.where(diff == 0, torch.zeros_like(diff), torch.full_like(diff, math.inf)))
-    return torch.where(torch.isfinite(g), d, torch.full_like(d, math.inf))
-
-
-def yardstick(regime: torch.Tensor, d32: torch.Tensor) -> Dict[str, float]:
-    """E32 per regime: the largest element distance of the fp32 restatement over the regime's elements, floored.  ``regime``
-    [H,W] (or [Hm,Wm]) against ``d32`` [H,W,C] (or [C,Hm,Wm]: channel first)."""
-    out = {}
-    for i, name in enumerate(REGIMES):
-        sel = regime == i
-        if bool(sel.any()):
-            out[name] = max(float(_of_regime(d32, sel).max()), FLOOR)
-    return out
-
-
-def _of_regime(d: torch.Tensor, sel: torch.Tensor) -> torch.Tensor:
-    return d[sel] if d.shape[:2] == sel.shape else d[:, sel]
-
-
-def worst_ratios(regime: torch.Tensor, d: torch.Tensor, e32: Dict[str, float]) -> Dict[str, Tuple[float, Tuple[int, ...]]]:
-    """Per regime: (largest d / E32, where)."""
-    out = {}
-    for i, name in enumerate(REGIMES):
-        sel = regime == i
-        if not bool(sel.any()):
-            continue
-        masked = torch.where(sel[..., None] if d.shape[:2] == sel.shape else sel[None], d, torch.full_like(d, -1.0))
-        at = int(masked.argmax())
-        out[name] = (float(masked.reshape(-1)[at]) / e32[name], tuple(int(v) for v in torch.unravel_index(torch.tensor(at), d.shape)))
-    return out
-
-
-def scalar_distance(s, s64, acc64) -> float:
-    return abs(float(s) - float(s64)) / float(acc64)

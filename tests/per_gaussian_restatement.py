@@ -33,8 +33,9 @@ NEAR = 0.01
 
 # The GPU bound is F * E32(regime, group, tensor).  Set from the MI355X run recorded in profiles/per_gaussian_row_parity.md:
 # 4 x the worst recorded ratio (HIP row distance) / E32 = 4 x 3.87, rounded up to a power of two; capped by the host test's
-# mutant assertion (every mutant is at least 4 * F * E32 away on the rows it concerns: F <= 81 on this scene).
-F = 16.0
+# mutant assertion (every mutant is at least 4 * F * E32 away on the rows it concerns: F <= 81 on this scene).  None: record
+# only.  The row distance of this family is |g - g64|_2 / |g64|_2 (tests/parity_common.py has the protocol).
+F: Optional[float] = 16.0
 
 CULLED = ("behind", "offscreen")
 FORMS = ("plain", "raw", "raw_delta")
@@ -398,7 +399,7 @@ def to_gradient_record(v_record: torch.Tensor) -> torch.Tensor:
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# gradients and distances
+# gradients
 
 
 def gradients(scene: RegimeScene, path: dict, dtype, groups=None, mutant=None, pose: bool = False, seed: int = 0):
@@ -419,30 +420,6 @@ def gradients(scene: RegimeScene, path: dict, dtype, groups=None, mutant=None, p
         gs = torch.autograd.grad(loss, list(wrt.values()), retain_graph=True, allow_unused=True)
         res[group] = {k: (torch.zeros_like(t) if g is None else g) for (k, t), g in zip(wrt.items(), gs)}
     return {k: v.detach() for k, v in outs.items()}, res
-
-
-def row_distance(g: torch.Tensor, g64: torch.Tensor) -> torch.Tensor:
-    """[N] float64: |g - g64|_2 / |g64|_2 over each row; NaN on the rows whose float64 gradient is exactly zero."""
-    g, g64 = g.detach().cpu().double().flatten(1) if g.dim() > 1 else g.detach().cpu().double()[:, None], \
-        g64.double().flatten(1) if g64.dim() > 1 else g64.double()[:, None]  # fmt: skip
-    n64 = g64.norm(dim=1)
-    return torch.where(n64 > 0, (g - g64).norm(dim=1) / n64, torch.full_like(n64, float("nan")))
-
-
-def zero_rows(g64: torch.Tensor) -> torch.Tensor:
-    return ~((g64.flatten(1) if g64.dim() > 1 else g64[:, None]) != 0).any(dim=1)
-
-
-def yardstick(labels: List[str], g32: torch.Tensor, g64: torch.Tensor) -> Dict[str, float]:
-    """E32 per regime: the largest per-row distance of the fp32 restatement's gradient from the float64 one over the
-    regime's rows (rows with a zero float64 gradient aside), floored at 16 * 2^-24."""
-    d = row_distance(g32, g64)
-    out = {}
-    for name in dict.fromkeys(labels):
-        rows = torch.tensor([l == name for l in labels])
-        v = d[rows & ~torch.isnan(d)]
-        out[name] = max(float(v.max()) if v.numel() else 0.0, FLOOR)
-    return out
 
 
 def vector_distance(g: torch.Tensor, g64: torch.Tensor) -> float:

@@ -13,7 +13,7 @@ test is imported here.  Written from ``oracle.raster_oracle`` (``_tile_terms``, 
 ROW DISTANCE.  |g - g64|_2 / |A64|_2 over a row's columns, A the absolute accumulation of the same tensor (for ``means2d``
 that is absgrad itself).  A gradient row is a signed sum over pixels that cancels, and the kernel's float atomics arrive in
 a varying order: both act at the scale of A, not of |g|.  With |g64| as the denominator the yardstick would be decided by
-whichever row happens to cancel best.
+whichever row happens to cancel best.  tests/parity_common.py has the protocol.
 
 LISTS.  The raster takes its lists as given: they are built with ``O.isect_tiles`` / ``O.isect_offsets`` from radii chosen
 per regime (generous for most; the deep, wall and occluded rows' boxes stay inside their one tile) and the deep tile's list
@@ -37,6 +37,7 @@ from typing import Dict, List, Optional
 
 import torch
 
+import parity_common as P
 from oracle import raster_oracle as O
 
 WIDTH, HEIGHT, TILE = 72, 40, 16
@@ -411,49 +412,20 @@ def gradients(scene: RegimeScene, channels: int, dtype, kept: torch.Tensor, muta
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# distances and yardsticks
-
-
-def row_distance(g: torch.Tensor, g64: torch.Tensor, a64: torch.Tensor) -> torch.Tensor:
-    """[N] float64: |g - g64|_2 / |A64|_2 over each row; NaN on the rows whose accumulation is exactly zero."""
-    g, g64, a64 = (x.detach().cpu().double().reshape(x.shape[0], -1) for x in (g, g64, a64))
-    den = a64.norm(dim=1)
-    return torch.where(den > 0, (g - g64).norm(dim=1) / den, torch.full_like(den, float("nan")))
-
-
-def zero_rows(g64: torch.Tensor) -> torch.Tensor:
-    return ~(g64.reshape(g64.shape[0], -1) != 0).any(dim=1)
-
-
-def yardstick(labels: List[str], g32, g64, a64) -> Dict[str, float]:
-    """E32 per regime: the largest row distance of the fp32 restatement from the float64 one over the regime's rows (rows
-    with a zero float64 gradient aside), floored at 16 * 2^-24."""
-    d = row_distance(g32, g64, a64)
-    live = ~zero_rows(g64) & ~torch.isnan(d)
-    out = {}
-    for name in dict.fromkeys(labels):
-        rows = torch.tensor([l == name for l in labels]) & live
-        out[name] = max(float(d[rows].max()) if bool(rows.any()) else 0.0, FLOOR)
-    return out
+# the forward's distances
 
 
 def forward_distance(fwd, fwd64) -> Dict[str, torch.Tensor]:
-    """-> render [H,W]: |r - r64|_inf / sum_i w_i |c_i|_inf (NaN where nothing contributes: there r64 is exactly 0);
-    alpha [H,W]: |a - a64| (absolute: alpha is formed as 1 - T)."""
+    """-> render [H,W]: |r - r64|_inf / sum_i w_i |c_i|_inf (where nothing contributes r64 is exactly 0: 0 if r is too, else
+    inf); alpha [H,W]: |a - a64| (absolute: alpha is formed as 1 - T)."""
     r, a = fwd["render"].detach().cpu().double(), fwd["alpha"].detach().cpu().double().reshape(fwd64["alpha"].shape)
-    err = (r - fwd64["render"]).abs().max(dim=-1).values
-    w = fwd64["weight"]
-    return dict(render=torch.where(w > 0, err / w, torch.full_like(w, float("nan"))), alpha=(a - fwd64["alpha"]).abs())
+    err = (r - fwd64["render"]).abs().max(dim=-1).values  # (the largest channel's error is what the weight sum bounds)
+    return dict(render=P.distance(err, torch.zeros_like(err), fwd64["weight"]),
+                alpha=P.distance(a, fwd64["alpha"], torch.ones_like(a)))  # fmt: skip
 
 
-def forward_yardstick(fwd32, fwd64, kept) -> Dict[str, Dict[str, float]]:
-    """E32 of render and alpha per pixel class, over the kept pixels, floored like the rows'."""
-    d = forward_distance(fwd32, fwd64)
-    cls = pixel_class()
-    out = {}
-    for what, v in d.items():
-        out[what] = {}
-        for i, name in enumerate(PIXEL_CLASSES):
-            sel = kept & (cls == i) & ~torch.isnan(v)
-            out[what][name] = max(float(v[sel].max()) if bool(sel.any()) else 0.0, FLOOR)
-    return out
+def pixel_masks(fwd64, kept) -> Dict[str, Dict[str, torch.Tensor]]:
+    """{output: {pixel class: [H,W] bool}}: the kept pixels of each class -- for the render those something contributes to
+    (the others must be exactly zero, which the GPU test asserts, and take no part in the class's maximum)."""
+    cls = P.masks_of_index(pixel_class(), PIXEL_CLASSES)
+    return dict(render=P.restrict(cls, kept & (fwd64["weight"] > 0)), alpha=P.restrict(cls, kept))

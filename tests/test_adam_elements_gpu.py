@@ -3,9 +3,8 @@ float64 restatement of tests/adam_restatement.py on its regime tensor:
 
     |x_hip - x64| / denominator  <=  F * E32(regime, output)
 
-E32 = the largest such distance of the fp32 restatement (CPU, plain torch) over the regime's elements of the same tensor,
-floored.  F (adam_restatement.F) = 4 x the worst ratio recorded on an MI355X, rounded up to a power of two:
-profiles/loss_adam_flow_parity.md has the table; the host test proves that each wrong restatement is at least 4 * F * E32 away.
+E32 over the regime's elements of the same tensor.  tests/parity_common.py has the protocol (E32, the floor, F); F, FLOOR and
+the three denominators are adam_restatement's, the recorded table is in profiles/loss_adam_flow_parity.md.
 
     FusedAdam.step()    -> fg_adam_step_multi, at sizes around the float4 boundary and at and past the 2048-workgroup cap of
                         one tensor (2 097 152 floats: beyond it the grid-stride loop runs, and the tail under a capped grid),
@@ -20,16 +19,16 @@ profiles/loss_adam_flow_parity.md.
 """
 import ctypes
 import functools
-import json
 import sys
 
 import pytest
 import torch
 
 import adam_restatement as A
-import helpers
+import parity_common as P
 from freegaussian_amd import _lib
 from freegaussian_amd.optim import FusedAdam, _AdamTensor, step_all
+from parity_common import need_gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -38,33 +37,18 @@ CAP = 2048 * 256 * 4  # floats one tensor's 2048 workgroups cover in one pass of
 SIZES = [1, 2, 3, 4, 5, 1023, 1024 * 4 + 3, CAP - 1, CAP, CAP + 5, 3 * CAP + 7]
 
 
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests selected but no GPU is visible (no CPU fallback exists)")
-    _lib.load()
-
-
 @functools.lru_cache(maxsize=2)
 def _tensor(n, seed=0):
     return A.regime_tensor(n, seed)
-
-
-def _bound(ratio):
-    return A.F is None or ratio <= A.F  # (F unset: the recording run F is set from)
 
 
 def _check(tag, pre, regime, lr, step, out, failures):
     """One tensor's three outputs against float64, per element.  Every ratio is recorded before anything is asserted."""
     p, g, m, v = pre
     out64, den, e32 = A.reference(p, g, m, v, regime, lr, step)
-    d = A.distances(out, out64, den)
-    for (name, k), (ratio, at) in A.worst_ratios(regime, d, e32).items():
-        helpers._record(f"ratio|{tag}|{k}|{name}", ratio)
-        helpers._record(f"e32|{tag}|{k}|{name}", e32[(name, k)])
-        if not _bound(ratio):
-            failures.append(f"{tag} {k}' {name}: element {at} of {p.numel()} is {ratio * e32[(name, k)]:.3e} of its denominator from "
-                            f"float64 = {ratio:.1f} x E32 ({e32[(name, k)]:.3e}); the bound is {A.F:g} x")  # fmt: skip
+    masks = P.masks_of_index(regime, A.REGIMES)
+    for k, x, x64 in zip(A.OUTPUTS, out, out64):
+        P.check(f"{tag}|{k}|{{regime}}", masks, P.distance(x.reshape(-1), x64, den[k]), e32[k], A.F, failures)
     # fresh state, zero gradient: exactly p, m' = v' = 0
     z = regime == A.REGIMES.index("fresh_zero_grad")
     if not (torch.equal(out[0].cpu().reshape(-1)[z], p[z]) and bool((out[1].cpu().reshape(-1)[z] == 0).all())
@@ -186,20 +170,14 @@ def _report(path):
     smallest E32 met); then the worst ratio per output of every size (over its steps and learning rates) and of every
     ``step_all`` batch (over its tensors)."""
     ratio, e32, per_group = {}, {}, {}
-    with open(path) as f:
-        for line in f:
-            r = json.loads(line)
-            kind, *key = r["kind"].split("|")
-            if kind not in ("ratio", "e32") or "test_adam_elements_gpu" not in r.get("test", ""):
-                continue
-            tag, k, name = key
-            if kind == "ratio":
-                ratio[(k, name)] = max(ratio.get((k, name), 0.0), r["value"])
-                parts = tag.split("-")  # step-n5-t1-lr..., step_all-16-i3, fg_adam_step-n100003
-                group = f"{parts[0]} {parts[1].lstrip('n')}"
-                per_group[(group, k)] = max(per_group.get((group, k), 0.0), r["value"])
-            else:
-                e32[(k, name)] = min(e32.get((k, name), float("inf")), r["value"])
+    cell_ratio, cell_e32 = P.read_records(path, "test_adam_elements_gpu")
+    for (tag, k, name), value in cell_ratio.items():
+        ratio[(k, name)] = max(ratio.get((k, name), 0.0), value)
+        parts = tag.split("-")  # step-n5-t1-lr..., step_all-16-i3, fg_adam_step-n100003
+        group = f"{parts[0]} {parts[1].lstrip('n')}"
+        per_group[(group, k)] = max(per_group.get((group, k), 0.0), value)
+    for (tag, k, name), value in cell_e32.items():
+        e32[(k, name)] = min(e32.get((k, name), float("inf")), value)
     worst = max(ratio, key=ratio.get)
     print(f"Adam: worst ratio {ratio[worst]:.2f} at {worst[0]}', {worst[1]}; {len(dict.fromkeys(g for g, _ in per_group))} sizes and batches.\n")
     print("| output | " + " | ".join(A.REGIMES) + " |\n|---|" + "---|" * len(A.REGIMES))

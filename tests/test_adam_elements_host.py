@@ -1,12 +1,13 @@
 """The Adam restatement (tests/adam_restatement.py) and its regime tensor, checked on the CPU: the float64 restatement is
 ``torch.optim.Adam(foreach=False)`` in float64 over three steps, every regime is what it is named for, the fp32 yardstick
 E32 is finite per (regime, output) at every (step, lr), and the per-element bound the GPU test applies (F x E32, relative
-to the output's denominator) catches each wrong restatement on some regime."""
+to the output's denominator; tests/parity_common.py has the protocol) catches each wrong restatement on some regime."""
 import functools
 
 import torch
 
 import adam_restatement as A
+import parity_common as P
 
 N = 7 * 4096
 
@@ -32,9 +33,9 @@ def test_float64_restatement_is_torch_adam_in_float64():
             st = opt.state[x]
             # (p' is rounded once more, to a float64 ulp of p: 2^-52 |p| is 4e-9 of the 2^-24 |p| its denominator counts)
             den["p"] = den["p"] + 2.0**-52 * p.abs() / 1e-12
-            d = A.distances((x.detach(), st["exp_avg"], st["exp_avg_sq"]), out, den)
-            for k in A.OUTPUTS:
-                assert float(d[k].max()) <= 1e-12, (lr, t, k, float(d[k].max()))
+            for k, got, want in zip(A.OUTPUTS, (x.detach(), st["exp_avg"], st["exp_avg_sq"]), out):
+                d = P.distance(got, want, den[k])
+                assert float(d.max()) <= 1e-12, (lr, t, k, float(d.max()))
             p, m_, v_ = out
 
 
@@ -76,9 +77,9 @@ def test_yardsticks_are_floored_and_finite():
     for step in A.STEPS:
         for lr in A.LRS:
             _, den, e32 = A.reference(p, g, m, v, regime, lr, step)
-            assert set(e32) == {(r, k) for r in A.REGIMES for k in A.OUTPUTS}
+            assert {(r, k) for k in e32 for r in e32[k]} == {(r, k) for r in A.REGIMES for k in A.OUTPUTS}
             assert all(bool((d >= 0).all()) for d in den.values())
-            for (name, k), e in e32.items():
+            for name, k, e in ((name, k, e) for k in e32 for name, e in e32[k].items()):
                 # p': the last rounding alone is up to half an ulp of p, which the denominator counts as 2^-24 |p|
                 assert A.FLOOR <= e <= (1.0 if k == "p" else (0.02 if name == "tiny_grad" else 1e-6)), (step, lr, name, k, e)
 
@@ -103,10 +104,10 @@ def mutant_caps():
         for step in steps:
             for lr in A.LRS:
                 out64, den, e32 = A.reference(p, g, m, v, regime, lr, step)
-                d = A.distances(A.update(p, g, m, v, lr, A.BETA1, A.BETA2, A.EPS, step, torch.float64, mutant), out64, den)
-                ratios = d[k][regime == A.REGIMES.index(name)] / e32[(name, k)]
-                q = max(-(-3 * ratios.numel() // 4), 1)
-                out[(mutant, name, k, step, lr)] = float(torch.sort(ratios, descending=True).values[q - 1]) / 4
+                i = A.OUTPUTS.index(k)
+                xm = A.update(p, g, m, v, lr, A.BETA1, A.BETA2, A.EPS, step, torch.float64, mutant)[i]
+                ratios = P.distance(xm, out64[i], den[k])[regime == A.REGIMES.index(name)] / e32[k][name]
+                out[(mutant, name, k, step, lr)] = P.three_quarter_cap(ratios)
     return out
 
 

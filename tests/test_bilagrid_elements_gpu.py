@@ -16,10 +16,8 @@ Shapes, (H x W, grid X, Y, L) -- a row of the slice is cut into 256-pixel segmen
 (tests/test_bilagrid_elements_host.py asserts, from the integer maps, that each shape holds what its line says.)
 
 PER ELEMENT:  |x_hip - x64| / A64  <=  F * E32(regime, array), no element left out, under every regime the element carries.
-A = the element's absolute accumulation (every term by magnitude), E32 = the largest such distance of the fp32 restatement
-(CPU, plain numpy) over the regime's elements, floored at 16 * 2^-24.  F (bilagrid_restatement.F) = 4 x the worst ratio
-recorded on an MI355X, rounded up to a power of two: profiles/bilagrid_parity.md has the table; the host test proves that
-every wrong restatement is at least 4 * F * E32 away on three quarters of the elements it concerns.
+tests/parity_common.py has the protocol (A, E32, the floor, F); the fp32 restatement is plain numpy, F and FLOOR are
+bilagrid_restatement's, the recorded table is in profiles/bilagrid_parity.md.
 EXACT: a node no pixel reaches, and the blocks of the other cameras, are 0.0; every output is finite; a second forward and
 backward gives the same bits; either gradient asked for alone gives the bits of the joint call.
 
@@ -27,7 +25,6 @@ backward gives the same bits; either gradient asked for alone gives the bits of 
 the table of profiles/bilagrid_parity.md.
 """
 import functools
-import json
 import sys
 
 import numpy as np
@@ -35,20 +32,14 @@ import pytest
 import torch
 
 import bilagrid_restatement as R
-import helpers
-from freegaussian_amd import _lib, ops
+import parity_common as P
+from freegaussian_amd import ops
+from parity_common import need_gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
 IDS = ["%dx%d-%d-%d-%d-%s" % (s[0], s[1], s[2], s[3], s[4], s[7]) for s in R.SHAPES]
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests selected but no GPU is visible (no CPU fallback exists)")
-    _lib.load()
 
 
 def _t(a):
@@ -69,10 +60,6 @@ def _run(shape, want_rgb=True, want_grids=True):
 _first = functools.lru_cache(maxsize=None)(_run)  # the joint call, once per shape: what the other calls are compared with
 
 
-def _bound(ratio):
-    return R.F is None or ratio <= R.F  # (F unset: the recording run F is set from)
-
-
 def _same_bits(a, b):
     return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
 
@@ -87,14 +74,8 @@ def test_every_element(shape):
         r64, masks, e32 = c["r64"], c["masks"][name], c["e32"][name]
         assert hip[name].shape == r64[name].shape and hip[name].dtype == np.float32
         # (every element carries a regime: tests/test_bilagrid_elements_host.py asserts it)
-        d =R.element_distance(hip[name], r64[name], r64[name + "_acc"])
-        for regime, (ratio, at) in R.worst_ratios(masks, d, e32).items():
-            helpers._record(f"ratio|{c['tag']}|{name}|{regime}", ratio)
-            helpers._record(f"e32|{c['tag']}|{name}|{regime}", e32[regime])
-            if not _bound(ratio):
-                failures.append(f"{c['tag']} {name} {regime}: element {at} is {float(hip[name][at])!r} for {float(r64[name][at])!r}, "
-                                f"{ratio * e32[regime]:.3e} of its accumulation from float64 = {ratio:.1f} x E32 ({e32[regime]:.3e}); "
-                                f"the bound is {R.F:g} x")  # fmt: skip
+        d = P.distance(hip[name], r64[name], r64[name + "_acc"])
+        P.check(f"{c['tag']}|{name}|{{regime}}", masks, d, e32, R.F, failures)
     for name, a in hip.items():
         assert bool(np.isfinite(a).all()), f"{name}: {int((~np.isfinite(a)).sum())} elements are not finite"
     unreached = c["r64"]["reach"] == 0
@@ -126,14 +107,7 @@ def test_either_gradient_alone_gives_the_bits_of_the_joint_call(shape):
 
 def _report(path):
     """Markdown of a run's records (FG_PARITY_REPORT): per shape and array, the HIP ratio and (E32) of every regime."""
-    ratio, e32 = {}, {}
-    with open(path) as f:
-        for line in f:
-            r = json.loads(line)
-            kind, *key = r["kind"].split("|")
-            if kind in ("ratio", "e32") and "test_bilagrid_elements_gpu" in r.get("test", ""):
-                d = ratio if kind == "ratio" else e32
-                d[tuple(key)] = max(d.get(tuple(key), 0.0), r["value"])
+    ratio, e32 = P.read_records(path, "test_bilagrid_elements_gpu")
     worst = max(ratio, key=ratio.get)
     print(f"Bilateral-grid slice: worst ratio {ratio[worst]:.2f} at {' | '.join(worst)}; {len(ratio)} cells.\n")
     for arrays, cols in ((("out", "v_rgb"), R.PIXEL_REGIMES), (("v_grid",), R.NODE_REGIMES)):

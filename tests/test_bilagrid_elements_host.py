@@ -3,7 +3,8 @@ CPU: the float64 restatement is torch's float64 autograd of ``bilagrid.apply_to_
 each element's accumulation; every shape of the GPU test holds what its line there says (asserted from the integer maps
 restated in Python, and from the library's workspace query, which answers without a GPU); the integer maps partition
 every axis and the floor of the fp32 quotient is the integer cell at every cell boundary of every supported size; every
-regime has elements; and the bound the GPU test applies catches each wrong restatement."""
+regime has elements; and the bound the GPU test applies (tests/parity_common.py has the protocol) catches each wrong
+restatement."""
 import functools
 
 import numpy as np
@@ -11,6 +12,7 @@ import pytest
 import torch
 
 import bilagrid_restatement as R
+import parity_common as P
 from freegaussian_amd import _lib, bilagrid
 from freegaussian_amd.bilagrid import BilateralGrid
 
@@ -50,7 +52,7 @@ def test_float64_restatement_is_torch_autograd_per_element(monkeypatch, shape):
         # a node that only a pixel ON a node could reach: torch may hold the pixel a rounding below the node and give the
         # next node a weight of 1e-16; the restatement's weight there is exactly 0 (A = 0): compare those at the scale of u
         reached = acc > 0
-        d = R.element_distance(got[name][reached], r64[name][reached], acc[reached])
+        d = P.distance(got[name][reached], r64[name][reached], acc[reached])
         print(f"{c['tag']} {name}: float64 restatement against torch, worst element {d.max():.2e} of its accumulation")
         assert float(d.max()) <= TORCH_BOUND, (name, float(d.max()))
         assert float(np.abs(got[name][~reached]).max(initial=0.0)) <= TORCH_BOUND * float(np.abs(c["v_out"]).max() * W * H)
@@ -234,10 +236,8 @@ def mutant_cells(factor):
                     for x0, x1, lo, _ in R.segments(W, GX):
                         cols[x0:x1] = lo > 0
                     sel = sel & cols[None, :, None]
-                ratios = (R.element_distance(rm[name], r64[name], r64[name + "_acc"]) / _smallest_e32(c, name))[sel]
-                k = max(-(-3 * ratios.size // 4), 1)
-                cap = float(np.sort(ratios)[::-1][k - 1]) / 4 if ratios.size else 0.0
-                out[(mutant, c["tag"], name)] = (int((ratios >= 4 * factor).sum()), ratios.size, cap)
+                ratios = (P.distance(rm[name], r64[name], r64[name + "_acc"]) / _smallest_e32(c, name))[sel]
+                out[(mutant, c["tag"], name)] = (int((ratios >= 4 * factor).sum()), ratios.size, P.three_quarter_cap(ratios))
     return out
 
 

@@ -6,29 +6,29 @@ labelled by regime: ``means2d`` at the principal point / far off-screen / generi
     every output (u_gs, u_cam) and every gradient (means2d, depths, vel), per row:
         |x_hip - x64|_2 / |A64|_2  <=  F * E32(regime, tensor)
     A = the absolute accumulation of the row's terms (``_accumulations``: the same sums with every term by magnitude),
-    E32 = the largest such distance of the same oracle in fp32 (CPU) over the regime's rows, floored at 16 * 2^-24;
+    E32 from the same oracle in fp32 (CPU) over the regime's rows (tests/parity_common.py has the protocol);
     wherever ``radii <= 0``: u_gs, u_cam and all three gradients are exactly 0 -- rows whose inputs hold NaN included.
 ``ops.camera_flow`` and ``ops.reprojection_flow`` per pixel on a 37 x 19 map (703 pixels: not a multiple of 256), the same
 rule; pixels of infinite depth give exactly 0.  ``ops.reprojection_flow`` takes the 3 x 4 motion M rounded to fp32, the float64
 reference composes it in double from the fp32 poses: M's rounding is counted against the kernel (it is within the bound).
 
-F = 4 x the worst ratio recorded on an MI355X, rounded up to a power of two: profiles/loss_adam_flow_parity.md has the table.
+The recorded table is in profiles/loss_adam_flow_parity.md.
 
 ``PYTHONPATH=. python tests/test_flow_rows_gpu.py REPORT.jsonl`` turns the records of a run under FG_PARITY_REPORT into the table of
 profiles/loss_adam_flow_parity.md.
 """
 import functools
-import json
 import math
 import sys
 
 import pytest
 import torch
 
-import helpers
-from freegaussian_amd import _lib, ops
+import parity_common as P
+from freegaussian_amd import ops
 from freegaussian_amd import flow as FL
 from oracle import raster_oracle as O
+from parity_common import need_gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -44,13 +44,6 @@ VELOC, OMEGA = torch.tensor([0.02, -0.01, 0.03]), torch.tensor([0.004, 0.01, -0.
 POSITIONS, DEPTHS, MOTIONS = ("principal", "offscreen", "generic"), (1e-3, 1.0, 1e3), ("still", "moving")
 REGIMES = tuple(f"{a}/Z={z:g}/{m}" for a in POSITIONS for z in DEPTHS for m in MOTIONS)
 TENSORS = ("u_gs", "u_cam", "v_means2d", "v_depths", "v_vel")
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests selected but no GPU is visible (no CPU fallback exists)")
-    _lib.load()
 
 
 @functools.lru_cache(maxsize=None)
@@ -101,46 +94,13 @@ def _accumulations():
     return acc
 
 
-def row_distance(x, x64, a64):
-    """[rows] float64: |x - x64|_2 / |A64|_2; 0 where the difference is exactly zero, inf where x is not finite or only the
-    accumulation is zero."""
-    x, x64, a64 = (t.detach().cpu().double().reshape(t.shape[0], -1) for t in (x, x64, a64))
-    diff, den = (x - x64).norm(dim=1), a64.norm(dim=1)
-    d = torch.where(diff == 0, torch.zeros_like(diff), torch.where(den > 0, diff / den, torch.full_like(diff, math.inf)))
-    return torch.where(torch.isfinite(x).all(dim=1), d, torch.full_like(d, math.inf))
-
-
 @functools.lru_cache(maxsize=None)
 def _reference():
     """(float64 oracle, accumulations, E32[tensor][regime]); computed once."""
     r64, r32, acc = _oracle(torch.float64), _oracle(torch.float32), _accumulations()
-    regime = _inputs()[5]
-    e32 = {}
-    for t in TENSORS:
-        d = row_distance(r32[t], r64[t], acc[t])
-        e32[t] = {name: max(float(d[regime == i].max()), FLOOR) for i, name in enumerate(REGIMES)}
+    masks = P.masks_of_index(_inputs()[5], REGIMES)
+    e32 = {t: P.yardstick(masks, P.distance(r32[t], r64[t], acc[t], rows=True), FLOOR) for t in TENSORS}
     return r64, acc, e32
-
-
-def _bound(ratio):
-    return F is None or ratio <= F  # (F unset: the recording run F is set from)
-
-
-def _check(tag, t, x, x64, a64, regime, e32, rows, failures):
-    """The rows ``rows`` (bool) of one tensor against float64.  Every ratio is recorded before anything is asserted."""
-    d = row_distance(x, x64, a64)
-    for i, name in enumerate(REGIMES):
-        sel = rows & (regime == i)
-        if not bool(sel.any()):
-            continue
-        masked = torch.where(sel, d, torch.full_like(d, -1.0))
-        at = int(masked.argmax())
-        ratio = float(masked[at]) / e32[name]
-        helpers._record(f"ratio|{tag}|{t}|{name}", ratio)
-        helpers._record(f"e32|{tag}|{t}|{name}", e32[name])
-        if not _bound(ratio):
-            failures.append(f"{tag} {t} {name}: row {at} is {float(masked[at]):.3e} of its accumulation from float64 = {ratio:.1f} x "
-                            f"E32 ({e32[name]:.3e}); the bound is {F:g} x")  # fmt: skip
 
 
 @pytest.mark.parametrize("masked", [False, True], ids=["all-rows", "radii"])
@@ -166,7 +126,9 @@ def test_every_row_of_gaussian_flow(masked):
         culled = hip[t][~live]
         if not bool((culled == 0).all()):  # (NaN != 0)
             failures.append(f"{t}: {int((culled != 0).any(dim=1).sum())} culled rows are not exactly zero")
-        _check("radii" if masked else "all-rows", t, hip[t], r64[t], acc[t], regime, e32[t], live, failures)
+        masks = P.restrict(P.masks_of_index(regime, REGIMES), live)
+        tag = "radii" if masked else "all-rows"
+        P.check(f"{tag}|{t}|{{regime}}", masks, P.distance(hip[t], r64[t], acc[t], rows=True), e32[t], F, failures)
     # a still Gaussian has no flow of its own, whatever the rounding
     still = live & (regime % 2 == 0)
     assert bool((hip["u_gs"][still] == 0).all())
@@ -190,16 +152,9 @@ def _check_pixels(tag, f, f64, a64, f32, inf, failures):
     assert f.shape == (H_MAP, W_MAP, 2)
     assert bool((f[inf] == 0).all()), f"{tag}: a pixel of infinite depth is not exactly zero"
     flat = lambda t: t.reshape(-1, 2)  # noqa: E731
-    e32 = max(float(row_distance(flat(f32), flat(f64), flat(a64))[~inf.reshape(-1)].max()), FLOOR)
-    d = row_distance(flat(f), flat(f64), flat(a64))
-    d = torch.where(inf.reshape(-1), torch.full_like(d, -1.0), d)
-    at = int(d.argmax())
-    ratio = float(d[at]) / e32
-    helpers._record(f"ratio|{tag}|flow|finite", ratio)
-    helpers._record(f"e32|{tag}|flow|finite", e32)
-    if not _bound(ratio):
-        failures.append(f"{tag}: pixel {divmod(at, W_MAP)} is {float(d[at]):.3e} of its accumulation from float64 = {ratio:.1f} x E32 "
-                        f"({e32:.3e}); the bound is {F:g} x")  # fmt: skip
+    finite = {"finite": ~inf.reshape(-1)}  # (the one regime of a map: its pixels of finite depth, row-major)
+    e32 = P.yardstick(finite, P.distance(flat(f32), flat(f64), flat(a64), rows=True), FLOOR)
+    P.check(f"{tag}|flow|{{regime}}", finite, P.distance(flat(f), flat(f64), flat(a64), rows=True), e32, F, failures)
 
 
 def test_every_pixel_of_camera_flow():
@@ -239,14 +194,7 @@ def test_every_pixel_of_reprojection_flow():
 
 def _report(path):
     """Markdown of a run's records (FG_PARITY_REPORT): per call and tensor x regime, the HIP ratio and (E32)."""
-    ratio, e32 = {}, {}
-    with open(path) as f:
-        for line in f:
-            r = json.loads(line)
-            kind, *key = r["kind"].split("|")
-            if kind in ("ratio", "e32") and "test_flow_rows_gpu" in r.get("test", ""):
-                d = ratio if kind == "ratio" else e32
-                d[tuple(key)] = max(d.get(tuple(key), 0.0), r["value"])
+    ratio, e32 = P.read_records(path, "test_flow_rows_gpu")
     worst = max(ratio, key=ratio.get)
     print(f"Flow: worst ratio {ratio[worst]:.2f} at {' | '.join(worst)}; {len(ratio)} cells.\n")
     print("| regime | " + " | ".join(f"{tag} {t}" for tag in ("all-rows", "radii") for t in TENSORS) + " |\n|---|" + "---|" * (2 * len(TENSORS)))

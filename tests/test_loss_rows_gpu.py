@@ -14,37 +14,28 @@ GROUP "l1" (the SSIM value unused: its cotangent arrives as None): every element
     float32(v) * float32(1 / (HWC)) * sign(pred - gt).
 THE THREE MAPS (fg_l1_ssim_fwd called directly): per map pixel, each against its own accumulation, F * E32(regime, map).
 THE TWO VALUES: within F x the fp32 restatement's own (floored) distance from float64; bit-identical on repetition.
-A = the element's absolute accumulation (every term by magnitude), E32 = the largest such distance of the fp32 restatement
-(CPU, plain torch) over the regime's elements, floored at 16 * 2^-24.  F (loss_restatement.F) = 4 x the worst ratio recorded
-on an MI355X, rounded up to a power of two: profiles/loss_adam_flow_parity.md has the table; the host test proves that every
-wrong restatement is at least 4 * F * E32 away on three quarters of the elements it concerns.
+tests/parity_common.py has the protocol (A, E32, the floor, F); F and FLOOR are loss_restatement's, the recorded table is in
+profiles/loss_adam_flow_parity.md.
 
 ``PYTHONPATH=. python tests/test_loss_rows_gpu.py REPORT.jsonl`` turns the records of a run under FG_PARITY_REPORT into the table of
 profiles/loss_adam_flow_parity.md.
 """
 import functools
-import json
 import sys
 
 import pytest
 import torch
 
-import helpers
 import loss_restatement as L
+import parity_common as P
 from freegaussian_amd import _lib, ops
+from parity_common import need_gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
 # (H, W, C, first regime of the image)
 CASES = [(58, 106, 1, 0), (58, 106, 3, 0), (58, 106, 4, 0), (53, 75, 3, 1), (11, 11, 3, 0), (12, 43, 3, 5)]
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests selected but no GPU is visible (no CPU fallback exists)")
-    _lib.load()
 
 
 @functools.lru_cache(maxsize=None)
@@ -54,15 +45,11 @@ def _reference(H, W, C, first):
     pred, gt = pred[..., :C].contiguous(), gt[..., :C].contiguous()
     f32, r32 = L.gradients(pred, gt, torch.float32)
     f64, r64 = L.gradients(pred, gt, torch.float64)
-    e32 = {g: L.yardstick(regime, L.element_distance(r32[g][0], *r64[g])) for g in L.GROUPS}
-    mreg = L.map_regime(regime)
-    e32_maps = {k: L.yardstick(mreg, L.element_distance(f32["maps"][k], f64["maps"][k], f64["acc"][k])) for k in L.MAPS}
-    e32_val = {k: max(L.scalar_distance(f32[k], f64[k], f64[k + "_acc"]), L.FLOOR) for k in ("l1", "ssim")}
-    return pred, gt, regime, f64, r64, e32, e32_maps, e32_val
-
-
-def _bound(ratio):
-    return L.F is None or ratio <= L.F  # (F unset: the recording run F is set from)
+    masks, map_masks = P.masks_of_index(regime, L.REGIMES), P.masks_of_index(L.map_regime(regime), L.REGIMES)
+    e32 = {g: P.yardstick(masks, P.distance(r32[g][0], *r64[g]), L.FLOOR) for g in L.GROUPS}
+    e32_maps = {k: P.yardstick(map_masks, P.distance(f32["maps"][k], f64["maps"][k], f64["acc"][k]), L.FLOOR) for k in L.MAPS}
+    e32_val = {k: max(float(P.distance(f32[k], f64[k], f64[k + "_acc"])), L.FLOOR) for k in ("l1", "ssim")}
+    return pred, gt, masks, map_masks, f64, r64, e32, e32_maps, e32_val
 
 
 def _run_hip(pred, gt, group):
@@ -76,19 +63,9 @@ def _run_hip(pred, gt, group):
     return l1.detach().cpu(), ss.detach().cpu(), x.grad.cpu()
 
 
-def _check(tag, what, regime, d, e32, failures):
-    """Every ratio is recorded before anything is asserted."""
-    for name, (ratio, at) in L.worst_ratios(regime, d, e32).items():
-        helpers._record(f"ratio|{tag}|{what}|{name}", ratio)
-        helpers._record(f"e32|{tag}|{what}|{name}", e32[name])
-        if not _bound(ratio):
-            failures.append(f"{tag} {what} {name}: element {at} is {ratio * e32[name]:.3e} of its accumulation from float64 = "
-                            f"{ratio:.1f} x E32 ({e32[name]:.3e}); the bound is {L.F:g} x")  # fmt: skip
-
-
 @pytest.mark.parametrize("H,W,C,first", CASES)
 def test_every_element(H, W, C, first):
-    pred, gt, regime, f64, r64, e32, _, e32_val = _reference(H, W, C, first)
+    pred, gt, masks, _, f64, r64, e32, _, e32_val = _reference(H, W, C, first)
     tag = f"{H}x{W}x{C}"
     failures = []
     values = []
@@ -105,22 +82,19 @@ def test_every_element(H, W, C, first):
                 failures.append(f"{tag} l1: {len(bad)} elements are not float32(v) * float32(1 / HWC) * sign, first {bad[0].tolist()}: "
                                 f"{float(g[tuple(bad[0])])!r} for {float(want[tuple(bad[0])])!r}")  # fmt: skip
             continue
-        _check(tag, group, regime, L.element_distance(g, *r64[group]), e32[group], failures)
+        P.check(f"{tag}|{group}|{{regime}}", masks, P.distance(g, *r64[group]), e32[group], L.F, failures)
     for l1, ss in values[1:]:
         assert torch.equal(l1, values[0][0]) and torch.equal(ss, values[0][1]), "the two values differ between two calls"
     for k, s in zip(("l1", "ssim"), values[0]):
-        ratio = L.scalar_distance(s, f64[k], f64[k + "_acc"]) / e32_val[k]
-        helpers._record(f"ratio|{tag}|value|{k}", ratio)
-        helpers._record(f"e32|{tag}|value|{k}", e32_val[k])
-        if not _bound(ratio):
-            failures.append(f"{tag} value {k}: {float(s)!r} for {float(f64[k])!r} = {ratio:.1f} x E32 ({e32_val[k]:.3e}); the bound is {L.F:g} x")
+        ratio = float(P.distance(s, f64[k], f64[k + "_acc"])) / e32_val[k]
+        P.check_cell(f"{tag}|value|{k}", ratio, e32_val[k], L.F, failures, f"{float(s)!r} for {float(f64[k])!r}")
     assert not failures, "\n".join(failures)
 
 
 @pytest.mark.parametrize("H,W,C,first", CASES)
 def test_every_map_pixel(H, W, C, first):
     """fg_l1_ssim_fwd through ``_lib`` directly: the three saved maps D_mu (total), D_xx, D_xy."""
-    pred, gt, regime, f64, _, _, e32_maps, _ = _reference(H, W, C, first)
+    pred, gt, _, map_masks, f64, _, _, e32_maps, _ = _reference(H, W, C, first)
     lib = _lib.load()
     x, y = pred.to(DEV), gt.to(DEV)
     n_ws = int(lib.fg_l1_ssim_workspace_floats(H, W, C))
@@ -136,9 +110,9 @@ def test_every_map_pixel(H, W, C, first):
     l1, ss = ops.l1_ssim(x, y)
     assert torch.equal(out.cpu(), torch.stack([l1, ss]).cpu())
     failures = []
-    mreg = L.map_regime(regime)
     for i, k in enumerate(L.MAPS):
-        _check(f"{H}x{W}x{C}", f"map {k}", mreg, L.element_distance(maps[i], f64["maps"][k], f64["acc"][k]), e32_maps[k], failures)
+        d = P.distance(maps[i], f64["maps"][k], f64["acc"][k])
+        P.check(f"{H}x{W}x{C}|map {k}|{{regime}}", map_masks, d, e32_maps[k], L.F, failures)
     assert not failures, "\n".join(failures)
 
 
@@ -163,14 +137,7 @@ def test_wrapper_inputs():
 
 def _report(path):
     """Markdown of a run's records (FG_PARITY_REPORT): per case, (group / map / value) x regime, the HIP ratio and (E32)."""
-    ratio, e32 = {}, {}
-    with open(path) as f:
-        for line in f:
-            r = json.loads(line)
-            kind, *key = r["kind"].split("|")
-            if kind in ("ratio", "e32") and "test_loss_rows_gpu" in r.get("test", ""):
-                d = ratio if kind == "ratio" else e32
-                d[tuple(key)] = max(d.get(tuple(key), 0.0), r["value"])
+    ratio, e32 = P.read_records(path, "test_loss_rows_gpu")
     worst = max(ratio, key=ratio.get)
     print(f"Loss: worst ratio {ratio[worst]:.2f} at {' | '.join(worst)}; {len(ratio)} cells.\n")
     cols = list(L.REGIMES) + ["l1", "ssim"]

@@ -2,7 +2,7 @@
 is autograd through ``harness.ssim`` in float64, the fp32 one is ``harness.ssim`` in fp32 to within the fp32 yardstick, every
 regime is what it is named for, the sign ties are exact, and the per-element bound the GPU test applies (F x the fp32
 restatement's own distance from float64, per regime and cotangent group, relative to the element's absolute accumulation)
-catches each wrong restatement.
+catches each wrong restatement.  tests/parity_common.py has the protocol.
 
 ``harness.ssim`` builds its 11 x 11 window in fp32 (exp, sum and outer product rounded to float); the kernel holds the taps
 normalised in double and rounded once.  The two windows differ by an fp32 ulp per tap, 1e-7 of the gradient: the comparison
@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import loss_restatement as L
+import parity_common as P
 from freegaussian_amd import harness
 
 H0, W0 = L.SHAPES[0]
@@ -47,7 +48,7 @@ def test_float64_restatement_is_autograd_through_the_torch_statement(C):
     for group in L.GROUPS:
         l1, ss, g = _harness(torch.float64, C, group)
         assert abs(float(fwd["l1"]) - float(l1)) <= 1e-12 * float(l1) and abs(float(fwd["ssim"]) - float(ss)) <= 1e-12
-        d = L.element_distance(res[group][0], g, res[group][1])
+        d = P.distance(res[group][0], g, res[group][1])
         assert float(d.max()) <= 1e-12, (group, float(d.max()))
 
 
@@ -55,13 +56,13 @@ def test_float64_restatement_is_autograd_through_the_torch_statement(C):
 def test_fp32_restatement_is_the_torch_statement_in_fp32(C):
     """Two plain fp32 statements of one formula (the sums of the windows in another order): the torch statement lies within
     4 x the restatement's own floored yardstick of float64, per regime, relative to A."""
-    _, _, regime = _image()
+    masks = P.masks_of_index(_image()[2], L.REGIMES)
     _, r64 = _grads(torch.float64, None, C, True)
     _, r32 = _grads(torch.float32, None, C, True)
     for group in L.GROUPS:
-        e32 = L.yardstick(regime, L.element_distance(r32[group][0], *r64[group]))
-        d = L.element_distance(_harness(torch.float32, C, group)[2], *r64[group])
-        for name, (ratio, at) in L.worst_ratios(regime, d, e32).items():
+        e32 = P.yardstick(masks, P.distance(r32[group][0], *r64[group]), L.FLOOR)
+        d = P.distance(_harness(torch.float32, C, group)[2], *r64[group])
+        for name, (ratio, at) in P.worst_ratios(masks, d, e32).items():
             print(f"C={C} {group} {name}: harness fp32 at {ratio:.2f} x E32 ({e32[name]:.2e})")
             assert ratio <= 4.0, (group, name, ratio, at)
 
@@ -121,18 +122,19 @@ def test_sign_ties_are_exact():
 
 
 def test_yardsticks_are_floored_and_finite():
-    _, _, regime = _image()
+    regime = _image()[2]
+    masks, map_masks = P.masks_of_index(regime, L.REGIMES), P.masks_of_index(L.map_regime(regime), L.REGIMES)
     for C in (1, 3, 4):
         f32, r32 = _grads(torch.float32, None, C)
         f64, r64 = _grads(torch.float64, None, C)
         for group in L.GROUPS:
             assert bool(torch.isfinite(r64[group][0]).all()) and bool((r64[group][1] >= 0).all())
-            e32 = L.yardstick(regime, L.element_distance(r32[group][0], *r64[group]))
+            e32 = P.yardstick(masks, P.distance(r32[group][0], *r64[group]), L.FLOOR)
             assert set(e32) == set(L.REGIMES)
             for name, e in e32.items():
                 assert L.FLOOR <= e < 1e-2, (C, group, name, e)
         for k in L.MAPS:
-            e32 = L.yardstick(L.map_regime(regime), L.element_distance(f32["maps"][k], f64["maps"][k], f64["acc"][k]))
+            e32 = P.yardstick(map_masks, P.distance(f32["maps"][k], f64["maps"][k], f64["acc"][k]), L.FLOOR)
             for name, e in e32.items():
                 assert L.FLOOR <= e < 1e-2, (C, k, name, e)
 
@@ -168,8 +170,8 @@ def mutant_cells(factor):
     for mutant, groups, regimes, extra in MUTANT_CASES:
         _, rm = _grads(torch.float64, mutant)
         for group in groups:
-            e32 = L.yardstick(regime, L.element_distance(r32[group][0], *r64[group]))
-            d = L.element_distance(rm[group][0], *r64[group])
+            e32 = P.yardstick(P.masks_of_index(regime, L.REGIMES), P.distance(r32[group][0], *r64[group]), L.FLOOR)
+            d = P.distance(rm[group][0], *r64[group])
             for name in regimes:
                 sel = (regime == L.REGIMES.index(name))[..., None].expand_as(d)
                 if extra:
@@ -177,9 +179,7 @@ def mutant_cells(factor):
                 if name == "step":  # (two columns either side of the edge: further out the block is flat)
                     sel = sel & cond["near_edge"]
                 ratios = d[sel] / e32[name]
-                k = max(-(-3 * ratios.numel() // 4), 1)
-                cap = float(torch.sort(ratios, descending=True).values[k - 1]) / 4 if ratios.numel() else 0.0
-                out[(mutant, group, name)] = (int((ratios >= 4 * factor).sum()), ratios.numel(), cap)
+                out[(mutant, group, name)] = (int((ratios >= 4 * factor).sum()), ratios.numel(), P.three_quarter_cap(ratios))
     return out
 
 
@@ -205,10 +205,10 @@ def test_mutants_are_caught_by_the_element_bound():
     assert L.F is None or L.F <= cap
     pred, gt, _ = _image()
     f32, f64 = L.forward(pred[..., :3], gt[..., :3], torch.float32), L.forward(pred[..., :3], gt[..., :3], torch.float64)
-    e32 = max(L.scalar_distance(f32["ssim"], f64["ssim"], f64["ssim_acc"]), L.FLOOR)
+    e32 = max(float(P.distance(f32["ssim"], f64["ssim"], f64["ssim_acc"])), L.FLOOR)
     for mutant in ("last_map_column_dropped", "ssim_mean_over_hwc", "c2_not_squared", "window_not_normalised"):
         fm = L.forward(pred[..., :3], gt[..., :3], torch.float64, mutant)
-        ratio = L.scalar_distance(fm["ssim"], f64["ssim"], f64["ssim_acc"]) / e32
+        ratio = float(P.distance(fm["ssim"], f64["ssim"], f64["ssim_acc"])) / e32
         print(f"{mutant}: the SSIM value is {ratio:.1f} x E32 ({e32:.2e}) away")
         assert ratio >= 4 * factor, (mutant, ratio)
     # where the true gradient is exactly zero (tied pixels, l1 group) the sign mutant's is not

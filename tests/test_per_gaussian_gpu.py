@@ -5,12 +5,11 @@ the float64 restatement, one cotangent group at a time.
 BACKWARD, per row, for every input tensor and every cotangent group:
     a row whose float64 gradient is exactly zero is zero on the GPU (no NaN, no denormal noise; the sign of a zero aside);
     every other row:  |g_hip - g64|_2 / |g64|_2  <=  F * E32(regime, group, tensor)
-E32 = the largest such distance of the fp32 restatement (CPU, plain torch) over the regime's rows, floored at 16 * 2^-24:
-what fp32 arithmetic can do on that regime (1e-6 on most; 5e-4 on the compensation gradient of the clamped rows, where the
-blur is nothing against the covariance and the three terms cancel).  F (per_gaussian_restatement.F) = 4 x the worst ratio
-recorded on an MI355X, rounded up to a power of two: profiles/per_gaussian_row_parity.md has the table; the host test
-proves that every autograd-level mutant of the restatement is at least 4 * F * E32 away.  NO row is left out:
-tests/test_per_gaussian_host.py asserts that no row is within 1e-3 of a branch boundary.
+tests/parity_common.py has the protocol (E32, the floor, F); here the denominator is the float64 row itself.  E32 is 1e-6 on
+most regimes and 5e-4 on the compensation gradient of the clamped rows, where the blur is nothing against the covariance and
+the three terms cancel.  F and FLOOR are per_gaussian_restatement's, the recorded table is in
+profiles/per_gaussian_row_parity.md; the host test proves that every autograd-level mutant of the restatement is at least
+4 * F * E32 away.  NO row is left out: tests/test_per_gaussian_host.py asserts that no row is within 1e-3 of a branch boundary.
 
 The cotangents reach the kernel as in production: ``(out * cotangent).sum()``, outputs a group does not drive get no gradient
 (``v_depths`` / ``v_conics`` arrive as None), and the record's cotangent passes a stand-in for the raster backward (``_RecordTap``)
@@ -24,29 +23,22 @@ own row distance from float64.  Record rows: by that rule in both forms; slots b
 profiles/per_gaussian_row_parity.md.
 """
 import functools
-import json
 import sys
 
 import pytest
 import torch
 
-import helpers
+import parity_common as P
 import per_gaussian_restatement as R
-from freegaussian_amd import _lib, ops
+from freegaussian_amd import ops
 from oracle import raster_oracle as O
+from parity_common import need_gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
 SEED = 0  # (tests/test_per_gaussian_host.py checks this scene's margins)
 TILE = 16
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests selected but no GPU is visible (no CPU fallback exists)")
-    _lib.load()
 
 
 @functools.lru_cache(maxsize=None)
@@ -60,8 +52,12 @@ def _reference(path_name, pose=False):
     sc = _scene()
     o32, g32 = R.gradients(sc, R.PATHS[path_name], torch.float32, pose=pose)
     o64, g64 = R.gradients(sc, R.PATHS[path_name], torch.float64, pose=pose)
-    e32 = {g: {t: R.yardstick(sc.labels, g32[g][t], g64[g][t]) for t in g64[g] if t != "viewmat"} for g in g64}
+    e32 = {g: {t: _row_e32(sc.labels, g32[g][t], g64[g][t]) for t in g64[g] if t != "viewmat"} for g in g64}
     return o32, g32, o64, g64, e32
+
+
+def _row_e32(labels, x32, x64):
+    return P.yardstick(P.live_row_masks(labels, x64), P.distance(x32, x64, x64.abs(), rows=True), R.FLOOR)
 
 
 class _RecordTap(torch.autograd.Function):
@@ -115,24 +111,11 @@ def _run_hip(scene, path, groups=None, pose=False, index=None):
 def _check_rows(tag, labels, what, x, x32_e, x64, failures):
     """One tensor's rows against float64: the exact-zero rule, then F * E32 per regime (``x32_e``: regime -> E32).  Every
     ratio is recorded before anything is asserted."""
-    zero = R.zero_rows(x64)
-    flat = x.flatten(1) if x.dim() > 1 else x[:, None]
-    wrong = zero & (flat != 0).any(dim=1)  # (NaN != 0)
+    wrong = P.exact_zero_rule(x, x64)
     if bool(wrong.any()):
         failures.append(f"{tag} {what}: rows {wrong.nonzero().flatten().tolist()[:8]} are not zero where float64 is")
-    d = R.row_distance(x, x64)
-    for regime in dict.fromkeys(labels):
-        rows = torch.tensor([l == regime for l in labels]) & ~zero
-        if not bool(rows.any()):
-            continue
-        worst = d[rows].max() if not bool(torch.isnan(d[rows]).any()) else torch.tensor(float("inf"))
-        ratio = float(worst) / x32_e[regime]
-        helpers._record(f"ratio|{tag}|{regime}|{what}", ratio)
-        helpers._record(f"e32|{tag}|{regime}|{what}", x32_e[regime])
-        if not ratio <= R.F:
-            row = int(torch.where(rows, torch.nan_to_num(d, nan=float("inf")), torch.tensor(-1.0, dtype=d.dtype)).argmax())
-            failures.append(f"{tag} {what} {regime}: row {row} is {float(worst):.3e} from float64 = {ratio:.1f} x E32 "
-                            f"({x32_e[regime]:.3e}); the bound is {R.F:g} x")  # fmt: skip
+    d = P.distance(x, x64, x64.abs(), rows=True)
+    P.check(f"{tag}|{{regime}}|{what}", P.live_row_masks(labels, x64), d, x32_e, R.F, failures)
 
 
 def _check_backward(tag, scene, path_name, hip, failures, index=None):
@@ -149,7 +132,7 @@ def _check_backward(tag, scene, path_name, hip, failures, index=None):
 def _output_yardstick(path_name):
     sc = _scene()
     o32, _, o64, _, _ = _reference(path_name)
-    return {k: R.yardstick(sc.labels, o32[k], o64[k]) for k in ("means2d", "depths", "conics", "record")}
+    return {k: _row_e32(sc.labels, o32[k], o64[k]) for k in ("means2d", "depths", "conics", "record")}
 
 
 def _check_forward(tag, scene, path_name, outs, failures, index=None):
@@ -259,10 +242,7 @@ def test_pose_gradient(path_name):
         reached += 1
         e32 = max(R.vector_distance(v32, v64), R.FLOOR)
         ratio = R.vector_distance(v, v64) / e32
-        helpers._record(f"ratio|{path_name}|pose|{group}|viewmat", ratio)
-        helpers._record(f"e32|{path_name}|pose|{group}|viewmat", e32)
-        if not ratio <= R.F:
-            failures.append(f"{path_name} {group}: pose gradient {ratio:.1f} x E32 ({e32:.3e}) from float64; the bound is {R.F:g} x")
+        P.check_cell(f"{path_name}|pose|{group}|viewmat", ratio, e32, R.F, failures, "the pose gradient")
     assert reached >= 4
     _check_backward(f"pose|{path_name}", sc, path_name, hip, failures)
     assert not failures, "\n".join(failures)
@@ -271,16 +251,9 @@ def test_pose_gradient(path_name):
 def _report(path):
     """Markdown of a run's records (FG_PARITY_REPORT): per path of the full-scene test, (group / tensor) x regime, the
     worst HIP ratio and (E32); one line per other test."""
-    ratio, e32 = {}, {}
-    with open(path) as f:
-        for line in f:
-            r = json.loads(line)
-            kind, *key = r["kind"].split("|")
-            if kind in ("ratio", "e32"):
-                if key[0] not in R.PATHS:  # (N=..|path, dead-..|path, pose|path)
-                    key = [f"{key[0]} {key[1]}"] + key[2:]
-                d = ratio if kind == "ratio" else e32
-                d[tuple(key)] = max(d.get(tuple(key), 0.0), r["value"])
+    # (N=..|path, dead-..|path, pose|path: one field)
+    ratio, e32 = ({k if k[0] in R.PATHS else (f"{k[0]} {k[1]}",) + k[2:]: v for k, v in d.items()}
+                  for d in P.read_records(path, "test_per_gaussian_gpu"))  # fmt: skip
     worst = max(ratio, key=ratio.get)
     print(f"Worst ratio {ratio[worst]:.2f} at {' | '.join(worst)}; {len(ratio)} (test, path, regime, group, tensor) cells.\n")
     regimes = list(R.VISIBLE_REGIMES) + ["pose"]  # (pose: the 12 numbers of the camera-pose gradient, rows "<group> / viewmat")

@@ -1,12 +1,14 @@
 """The per-Gaussian stage's restatement (tests/per_gaussian_restatement.py) and the regime scene, checked on the CPU: the
 restatement is the pinned oracle's projection, every regime is what it is named for, no row sits near a branch boundary,
 and the row-wise bound the GPU test applies (F x the fp32 restatement's own row distance from float64, per regime, cotangent
-group and input tensor) is tight enough to catch each autograd-level mutant of the restatement."""
+group and input tensor; tests/parity_common.py has the protocol) is tight enough to catch each autograd-level mutant of the
+restatement."""
 import functools
 
 import pytest
 import torch
 
+import parity_common as P
 import per_gaussian_restatement as R
 from oracle import raster_oracle as O
 
@@ -121,13 +123,17 @@ def test_no_row_is_near_a_branch_boundary(form):
     assert bool(torch.isfinite(m["cull"][_scene().rows(*R.CULLED)]).all())
 
 
+def _row_e32(x32, x64):
+    return P.yardstick(P.live_row_masks(_scene().labels, x64), P.distance(x32, x64, x64.abs(), rows=True), R.FLOOR)
+
+
 def test_yardstick_is_floored_and_finite():
     for path_name in R.PATHS:
         _, g32 = _grads(path_name, torch.float32)
         _, g64 = _grads(path_name, torch.float64)
         for group in g64:
             for tensor in g64[group]:
-                for regime, e in R.yardstick(_scene().labels, g32[group][tensor], g64[group][tensor]).items():
+                for regime, e in _row_e32(g32[group][tensor], g64[group][tensor]).items():
                     assert R.FLOOR <= e < 1e-2, (path_name, group, tensor, regime, e)
 
 
@@ -141,13 +147,13 @@ def test_exact_zero_rows_stay_exactly_zero_in_fp32():
         _, g64 = _grads(path_name, torch.float64)
         for group in g64:
             for tensor in g64[group]:
-                z = R.zero_rows(g64[group][tensor])
+                z = P.zero_rows(g64[group][tensor])
                 if not (tensor == "extra" and group in ("extra", "all")):  # (a record slot's pass-through gradient)
                     assert bool(z[culled].all()), (path_name, group, tensor)
                 assert bool((g32[group][tensor][z] == 0).all()), (path_name, group, tensor)
         for tensor in ("quats", "scales" if R.PATHS[path_name]["form"] == "plain" else "log_scales"):
-            assert bool(R.zero_rows(g64["means2d"][tensor]).all())
-            assert not bool(R.zero_rows(g64["conics_out"][tensor]).all())
+            assert bool(P.zero_rows(g64["means2d"][tensor]).all())
+            assert not bool(P.zero_rows(g64["conics_out"][tensor]).all())
 
 
 # (mutant, path, cotangent groups that drive it, input tensors it reaches, regimes it concerns)
@@ -180,6 +186,7 @@ def test_mutants_are_caught_by_the_row_bound(mutant, path_name, groups, tensors,
     float64 gradient is at least 4 * F * E32 from the true one (or non-zero where the true one is exactly zero): the GPU
     bound F * E32 has teeth (and this caps F).  The mutant's forward is the restatement's."""
     sc = _scene()
+    factor = 1.0 if R.F is None else R.F
     o64, g64 = _grads(path_name, torch.float64)
     _, g32 = _grads(path_name, torch.float32)
     om, gm = _grads(path_name, torch.float64, mutant)
@@ -187,21 +194,21 @@ def test_mutants_are_caught_by_the_row_bound(mutant, path_name, groups, tensors,
         assert torch.equal(o64[k], om[k]), k
     for group in groups:
         for tensor in tensors:
-            e32 = R.yardstick(sc.labels, g32[group][tensor], g64[group][tensor])
-            d = R.row_distance(gm[group][tensor], g64[group][tensor])
+            e32 = _row_e32(g32[group][tensor], g64[group][tensor])
+            d = P.distance(gm[group][tensor], g64[group][tensor], g64[group][tensor].abs(), rows=True)
             for regime in regimes:
                 rows = sc.rows(regime)
                 # a row whose true gradient is exactly zero (all three channels clamped: no colour gradient at all) falls
                 # to the exact-zero rule if the mutant's is not zero; if it is zero too the mutant does not reach the row
-                zero = R.zero_rows(g64[group][tensor])[rows]
+                zero = P.zero_rows(g64[group][tensor])[rows]
                 assert int(zero.sum()) * 2 < len(rows), (group, tensor, regime)
                 if mutant == "sh_mask":
-                    assert not bool(R.zero_rows(gm[group][tensor])[rows][zero].any())
+                    assert not bool(P.zero_rows(gm[group][tensor])[rows][zero].any())
                 dr = d[rows][~zero]
-                assert not bool(torch.isnan(dr).any())
+                assert bool(torch.isfinite(dr).all())
                 print(f"{mutant} {path_name} {group} {tensor} {regime}: min row distance {float(dr.min()):.3e}, "
-                      f"E32 {e32[regime]:.3e}, ratio {float(dr.min()) / e32[regime]:.0f} (needs {4 * R.F:.0f})")  # fmt: skip
-                assert float(dr.min()) >= 4 * R.F * e32[regime], (group, tensor, regime)
+                      f"E32 {e32[regime]:.3e}, ratio {float(dr.min()) / e32[regime]:.0f} (needs {4 * factor:.0f})")  # fmt: skip
+                assert float(dr.min()) >= 4 * factor * e32[regime], (group, tensor, regime)
 
 
 def test_clamp_mutant_is_invisible_to_pooled_cotangents_and_touches_no_other_row():
@@ -213,7 +220,7 @@ def test_clamp_mutant_is_invisible_to_pooled_cotangents_and_touches_no_other_row
     _, gm = _grads("plain-sh3-aa-rows", torch.float64, "clamp_derivative")
     clamped = sc.rows("clamp_x", "clamp_y", "clamp_xy")
     others = sc.rows(*[k for k in R.VISIBLE_REGIMES if not k.startswith("clamp")])
-    d_all = R.row_distance(gm["all"]["means"], g64["all"]["means"])
-    d_con = R.row_distance(gm["conics_out"]["means"], g64["conics_out"]["means"])
+    d_all = P.distance(gm["all"]["means"], g64["all"]["means"], g64["all"]["means"].abs(), rows=True)
+    d_con = P.distance(gm["conics_out"]["means"], g64["conics_out"]["means"], g64["conics_out"]["means"].abs(), rows=True)
     assert float(d_con[others].max()) == 0.0 and float(d_all[others].max()) == 0.0
     assert float(d_all[clamped].median()) * 100 < float(d_con[clamped].median())

@@ -9,37 +9,27 @@ FORWARD, on every kept pixel (tests/test_raster_rows_host.py: 99 % of them; the 
 BACKWARD, per cotangent group (render / alpha / both), per tensor (means2d, absgrad, conics, features, opacities):
     a row whose float64 gradient is exactly zero is zero on the GPU (faint rows, rows behind the wall, ...);
     every other row:  |g_hip - g64|_2 / |A64|_2  <=  F * E32(regime, group, tensor)
-A = the row's absolute accumulation (every per-pixel term by magnitude), E32 = the largest such distance of the fp32
-restatement (CPU, plain torch) over the regime's rows, floored at 16 * 2^-24.  F (raster_restatement.F) = 4 x the worst ratio
-recorded on an MI355X, rounded up to a power of two: profiles/raster_row_parity.md has the table; the host test proves
-that every wrong restatement is at least 4 * F * E32 away on three quarters of the rows it concerns.  Each backward runs
-twice (the order of its float atomics differs) and both runs are held to the bound; the forward is bit-identical across
-all of them.
+tests/parity_common.py has the protocol (A, E32, the floor, F); F and FLOOR are raster_restatement's, the recorded table is
+in profiles/raster_row_parity.md.  Each backward runs twice (the order of its float atomics differs) and both runs are held
+to the bound; the forward is bit-identical across all of them.
 
 ``python tests/test_raster_rows_gpu.py REPORT.jsonl`` turns the records of a run under FG_PARITY_REPORT into the tables of
 profiles/raster_row_parity.md.
 """
 import functools
-import json
 import sys
 
 import pytest
 import torch
 
-import helpers
+import parity_common as P
 import raster_restatement as R
-from freegaussian_amd import _lib, ops
+from freegaussian_amd import ops
+from parity_common import need_gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests selected but no GPU is visible (no CPU fallback exists)")
-    _lib.load()
 
 
 @functools.lru_cache(maxsize=None)
@@ -58,8 +48,17 @@ def _reference(channels):
     sc, kept = _scene(), _kept()
     f32, g32 = R.gradients(sc, channels, torch.float32, kept)
     f64, g64 = R.gradients(sc, channels, torch.float64, kept)
-    e32 = {g: {t: R.yardstick(sc.labels, g32[g][0][t], g64[g][0][t], g64[g][1][t]) for t in R.TENSORS} for g in R.GROUPS}
-    return f64, g64, R.forward_yardstick(f32, f64, kept), e32
+    e32 = {g: {t: _row_e32(sc.labels, g32[g][0][t], g64[g][0][t], g64[g][1][t]) for t in R.TENSORS} for g in R.GROUPS}
+    return f64, g64, _forward_e32(f32, f64, kept), e32
+
+
+def _row_e32(labels, x32, x64, a64):
+    return P.yardstick(P.live_row_masks(labels, x64), P.distance(x32, x64, a64, rows=True), R.FLOOR)
+
+
+def _forward_e32(f32, f64, kept):
+    d, masks = R.forward_distance(f32, f64), R.pixel_masks(f64, kept)
+    return {what: P.yardstick(masks[what], d[what], R.FLOOR) for what in d}
 
 
 def _run_hip(scene, channels, policy, kept, groups=R.GROUPS, repeats=2):
@@ -93,10 +92,6 @@ def _run_hip(scene, channels, policy, kept, groups=R.GROUPS, repeats=2):
     return fwd, res
 
 
-def _bound(ratio):
-    return R.F is None or ratio <= R.F  # (F unset: the recording run F is set from)
-
-
 def _check_forward(tag, fwd, f64, e32, kept, failures):
     if not torch.equal(fwd["last_ids"][kept], f64["last_ids"][kept]):
         bad = ((fwd["last_ids"] != f64["last_ids"]) & kept).nonzero()
@@ -105,43 +100,21 @@ def _check_forward(tag, fwd, f64, e32, kept, failures):
     nothing = kept & (f64["weight"] == 0)
     if bool((fwd["render"][nothing] != 0).any()):
         failures.append(f"{tag}: render is not zero on pixels nothing contributes to")
-    cls = R.pixel_class()
+    masks = R.pixel_masks(f64, kept)
     for what, v in d.items():
-        for i, name in enumerate(R.PIXEL_CLASSES):
-            sel = kept & (cls == i) & ~torch.isnan(v)
-            if not bool(sel.any()):
-                continue
-            worst = float(v[sel].max()) if bool(torch.isfinite(v[sel]).all()) else float("inf")
-            ratio = worst / e32[what][name]
-            helpers._record(f"ratio|{tag}|forward|{what}|{name}", ratio)
-            helpers._record(f"e32|{tag}|forward|{what}|{name}", e32[what][name])
-            if not _bound(ratio):
-                failures.append(f"{tag} forward {what} {name}: {worst:.3e} from float64 = {ratio:.1f} x E32 ({e32[what][name]:.3e}); "
-                                f"the bound is {R.F:g} x")  # fmt: skip
+        P.check(f"{tag}|forward|{what}|{{regime}}", masks[what], v, e32[what], R.F, failures)
 
 
 def _check_rows(tag, labels, group, tensor, x, x64, a64, e32, failures):
     """One tensor's rows against float64: the exact-zero rule, then F * E32 per regime.  Every ratio is recorded before
     anything is asserted."""
     assert x.shape == x64.shape, (tag, tensor, x.shape, x64.shape)
-    zero = R.zero_rows(x64)
-    wrong = zero & (x != 0).any(dim=1)  # (NaN != 0)
+    wrong = P.exact_zero_rule(x, x64)
     if bool(wrong.any()):
         failures.append(f"{tag} {group} {tensor}: rows {wrong.nonzero().flatten().tolist()[:8]} "
                         f"({sorted(set(labels[int(i)] for i in wrong.nonzero().flatten()))}) are not zero where float64 is")  # fmt: skip
-    d = R.row_distance(x, x64, a64)
-    for regime in dict.fromkeys(labels):
-        rows = torch.tensor([l == regime for l in labels]) & ~zero
-        if not bool(rows.any()):
-            continue
-        worst = d[rows].max() if bool(torch.isfinite(d[rows]).all()) else torch.tensor(float("inf"))
-        ratio = float(worst) / e32[regime]
-        helpers._record(f"ratio|{tag}|{group}|{tensor}|{regime}", ratio)
-        helpers._record(f"e32|{tag}|{group}|{tensor}|{regime}", e32[regime])
-        if not _bound(ratio):
-            row = int(torch.where(rows, torch.nan_to_num(d, nan=float("inf")), torch.tensor(-1.0, dtype=d.dtype)).argmax())
-            failures.append(f"{tag} {group} {tensor} {regime}: row {row} is {float(worst):.3e} of its accumulation from float64 = "
-                            f"{ratio:.1f} x E32 ({e32[regime]:.3e}); the bound is {R.F:g} x")  # fmt: skip
+    d = P.distance(x, x64, a64, rows=True)
+    P.check(f"{tag}|{group}|{tensor}|{{regime}}", P.live_row_masks(labels, x64), d, e32, R.F, failures)
 
 
 def _check_full_scene(tag, channels, policy, failures):
@@ -210,10 +183,10 @@ def _check_sub_scene(tag, sc, failures):
     f32, g32 = R.gradients(sc, 3, torch.float32, kept)
     f64, g64 = R.gradients(sc, 3, torch.float64, kept)
     fwd, res = _run_hip(sc, 3, {}, kept)
-    _check_forward(tag, fwd, f64, R.forward_yardstick(f32, f64, kept), kept, failures)
+    _check_forward(tag, fwd, f64, _forward_e32(f32, f64, kept), kept, failures)
     for (group, rep), grads in res.items():
         for tensor in R.TENSORS:
-            e32 = R.yardstick(sc.labels, g32[group][0][tensor], g64[group][0][tensor], g64[group][1][tensor])
+            e32 = _row_e32(sc.labels, g32[group][0][tensor], g64[group][0][tensor], g64[group][1][tensor])
             _check_rows(tag, sc.labels, group, tensor, grads[tensor], g64[group][0][tensor], g64[group][1][tensor], e32, failures)
     return fwd, res, f64
 
@@ -238,7 +211,7 @@ def test_sub_scenes():
     # one single splat
     one = full.take(full.rows("plain")[:1])
     fwd, res, f64 = _check_sub_scene("one-splat", one, failures)
-    assert float(f64["alpha"].max()) > 0.2 and not bool(R.zero_rows(res[("both", 0)]["means2d"]).any())
+    assert float(f64["alpha"].max()) > 0.2 and not bool(P.zero_rows(res[("both", 0)]["means2d"]).any())
     # N >= 1 rows and every list empty: images all zero, every gradient exactly zero
     for n in (1, 70):
         sc = full.take(torch.arange(n)).without_lists()
@@ -254,14 +227,7 @@ def test_sub_scenes():
 def _report(path):
     """Markdown of a run's records (FG_PARITY_REPORT): per test case, (group / tensor) x regime and (output) x pixel class,
     the worst HIP ratio over both backward runs and (E32)."""
-    ratio, e32 = {}, {}
-    with open(path) as f:
-        for line in f:
-            r = json.loads(line)
-            kind, *key = r["kind"].split("|")
-            if kind in ("ratio", "e32"):
-                d = ratio if kind == "ratio" else e32
-                d[tuple(key)] = max(d.get(tuple(key), 0.0), r["value"])
+    ratio, e32 = P.read_records(path, "test_raster_rows_gpu")
     worst = max(ratio, key=ratio.get)
     print(f"Worst ratio {ratio[worst]:.2f} at {' | '.join(worst)}; {len(ratio)} (case, group, tensor, regime) cells.\n")
     tags = list(dict.fromkeys(k[0] for k in ratio))

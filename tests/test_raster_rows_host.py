@@ -2,12 +2,14 @@
 restatement is the pinned oracle's ``rasterize`` / ``rasterize_backward(alpha_out=)``, every regime is what it is named for,
 the pixels left out for sitting on a decision threshold are few and cost no row more than a fifth of its footprint, fp32 and
 float64 take the same decisions on every pixel that is kept, and the row-wise bound the GPU test applies (F x the fp32
-restatement's own row distance from float64, per regime, cotangent group and tensor) catches each wrong restatement."""
+restatement's own row distance from float64, per regime, cotangent group and tensor; tests/parity_common.py has the
+protocol) catches each wrong restatement."""
 import functools
 
 import pytest
 import torch
 
+import parity_common as P
 import raster_restatement as R
 from oracle import raster_oracle as O
 
@@ -79,7 +81,7 @@ def test_census_every_regime_is_what_it_is_named_for():
         assert bool((total[rows] == 0).all())
         for group in R.GROUPS:
             for tensor in R.TENSORS:
-                assert bool(R.zero_rows(g64[group][0][tensor])[rows].all()), (name, group, tensor)
+                assert bool(P.zero_rows(g64[group][0][tensor])[rows].all()), (name, group, tensor)
     assert bool((sc.opacities[sc.rows("faint")] < O.ALPHA_SKIP).all())
     # every other regime has rows that contribute; barely: a few pixels each
     for name in R.COUNTS:
@@ -168,17 +170,20 @@ def test_yardsticks_are_floored_and_finite():
     for channels in (1, 3, 4, 8):
         f32, g32 = _grads(torch.float32, None, channels)
         f64, g64 = _grads(torch.float64, None, channels)
-        for what, per_class in R.forward_yardstick(f32, f64, _margins()["kept"]).items():
-            for cls, e in per_class.items():
+        d, masks = R.forward_distance(f32, f64), R.pixel_masks(f64, _margins()["kept"])
+        for what in d:
+            assert set(masks[what]) == set(R.PIXEL_CLASSES)
+            for cls, e in P.yardstick(masks[what], d[what], R.FLOOR).items():
                 assert R.FLOOR <= e < 1e-4, (channels, what, cls, e)
         for group in R.GROUPS:
             grads, accum = g64[group]
             for tensor in R.TENSORS:
                 assert bool(torch.isfinite(grads[tensor]).all()) and bool((accum[tensor] >= 0).all())
                 # a row is exactly zero where its accumulation is
-                assert bool(R.zero_rows(grads[tensor])[R.zero_rows(accum[tensor])].all())
-                assert bool((g32[group][0][tensor][R.zero_rows(grads[tensor])] == 0).all()), (group, tensor)
-                for regime, e in R.yardstick(_scene().labels, g32[group][0][tensor], grads[tensor], accum[tensor]).items():
+                assert bool(P.zero_rows(grads[tensor])[P.zero_rows(accum[tensor])].all())
+                assert bool((g32[group][0][tensor][P.zero_rows(grads[tensor])] == 0).all()), (group, tensor)
+                d32 = P.distance(g32[group][0][tensor], grads[tensor], accum[tensor], rows=True)
+                for regime, e in P.yardstick(P.live_row_masks(_scene().labels, grads[tensor]), d32, R.FLOOR).items():
                     assert R.FLOOR <= e < 1e-3, (channels, group, tensor, regime, e)
 
 
@@ -211,9 +216,9 @@ def mutant_shares(factor):
         for group in groups:
             for tensor in tensors:
                 ref, acc = g64[group][0][tensor], g64[group][1][tensor]
-                e32 = R.yardstick(sc.labels, g32[group][0][tensor], ref, acc)
-                d = R.row_distance(gm[group][0][tensor], ref, acc)
-                zero, zero_m = R.zero_rows(ref), R.zero_rows(gm[group][0][tensor])
+                e32 = P.yardstick(P.live_row_masks(sc.labels, ref), P.distance(g32[group][0][tensor], ref, acc, rows=True), R.FLOOR)
+                d = P.distance(gm[group][0][tensor], ref, acc, rows=True)
+                zero, zero_m = P.zero_rows(ref), P.zero_rows(gm[group][0][tensor])
                 for regime in regimes:
                     rows = sc.rows(regime)
                     rows = rows[~(zero[rows] & zero_m[rows])]
@@ -221,10 +226,7 @@ def mutant_shares(factor):
                         continue  # (no colour gradient without v_render)
                     caught = torch.where(zero[rows], ~zero_m[rows], d[rows] >= 4 * factor * e32[regime])
                     ratios = torch.where(zero[rows], torch.full_like(d[rows], float("inf")), d[rows] / e32[regime])
-                    # the largest F at which three quarters of the rows are still caught
-                    k = max(int(-(-3 * len(rows) // 4)), 1)
-                    cap = float(torch.sort(ratios, descending=True).values[k - 1]) / 4 if len(rows) else 0.0
-                    out[(mutant, group, tensor, regime)] = (int(caught.sum()), len(rows), cap)
+                    out[(mutant, group, tensor, regime)] = (int(caught.sum()), len(rows), P.three_quarter_cap(ratios))
     return out
 
 
@@ -263,8 +265,8 @@ def test_mutants_are_caught_by_the_row_bound():
         for tensor in R.TENSORS:
             if group == "alpha" and tensor == "features":
                 continue  # (no colour gradient without v_render)
-            zero = R.zero_rows(g64[group][0][tensor])
+            zero = P.zero_rows(g64[group][0][tensor])
             for regime in ("wall", "occluded"):
                 rows = sc.rows(regime)
                 rows = rows[zero[rows]]
-                assert len(rows) >= 4 and not bool(R.zero_rows(gm[group][0][tensor])[rows].any()), (group, tensor, regime)
+                assert len(rows) >= 4 and not bool(P.zero_rows(gm[group][0][tensor])[rows].any()), (group, tensor, regime)
