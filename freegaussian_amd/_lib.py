@@ -136,6 +136,10 @@ SIGNATURES = {
     "fg_color_correct_workspace_bytes": (c_size_t, [c_int64, c_int]),  # (P, num_iters)
     # (P, img, ref, num_iters, eps, out, warps, rank, workspace, bytes, stream)
     "fg_color_correct": (c_int, [c_int64, P, P, c_int, c_double, P, P, P, P, c_size_t, P]),
+    # the SE(3) exponential of the (w, v) heads applied to points (csrc/se3_apply.hip); strides in floats
+    "fg_se3_apply_fwd": (c_int, [c_int64, P, c_int64, P, c_int64, P, P, P]),  # (N, w, w_stride, v, v_stride, pts, out, stream)
+    # (N, w, w_stride, v, v_stride, pts, g_out, g_w, gw_stride, g_v, gv_stride, g_pts, stream)
+    "fg_se3_apply_bwd": (c_int, [c_int64, P, c_int64, P, c_int64, P, P, P, c_int64, P, c_int64, P, P]),
 }  # fmt: skip
 
 # test hooks, not declared in the public header

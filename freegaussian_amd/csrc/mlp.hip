@@ -45,6 +45,7 @@
 
 #include "fg_common.h"
 #include "mlp_internal.h"
+#include "se3_math.h"
 
 namespace {
 
@@ -243,27 +244,9 @@ __device__ __forceinline__ void mlp_gemm_in(f32x16 (&acc)[2], const float* a, in
   }
 }
 
-// exp_se3 of (w / |w| + 1e-5, v / |w| + 1e-5; |w|) in the arithmetic of utils.exp_se3, and the transform of x
+// exp_se3 of (w / |w| + 1e-5, v / |w| + 1e-5; |w|) and the transform of x (se3_math.h: the arithmetic of utils.exp_se3)
 __device__ __forceinline__ void mlp_se3_row(const float* hd, const float* x, int64_t row, const MlpArgs& p) {
-  const float theta = sqrtf(hd[0] * hd[0] + hd[1] * hd[1] + hd[2] * hd[2]);
-  const float w0 = hd[0] / theta + 1e-5f, w1 = hd[1] / theta + 1e-5f, w2 = hd[2] / theta + 1e-5f;
-  const float v[3] = {hd[3] / theta + 1e-5f, hd[4] / theta + 1e-5f, hd[5] / theta + 1e-5f};
-  const float Wm[3][3] = {{0.f, -w2, w1}, {w2, 0.f, -w0}, {-w1, w0, 0.f}};
-  float W2[3][3];
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) W2[i][j] = Wm[i][0] * Wm[0][j] + Wm[i][1] * Wm[1][j] + Wm[i][2] * Wm[2][j];
-  float s, c;
-  sincosf(theta, &s, &c);
-  float T[3][4];
-  for (int i = 0; i < 3; ++i) {
-    float G[3];
-    for (int j = 0; j < 3; ++j) {
-      const float eye = i == j ? 1.f : 0.f;
-      T[i][j] = eye + s * Wm[i][j] + (1.f - c) * W2[i][j];
-      G[j] = theta * eye + (1.f - c) * Wm[i][j] + (theta - s) * W2[i][j];
-    }
-    T[i][3] = G[0] * v[0] + G[1] * v[1] + G[2] * v[2];
-  }
+  FG_SE3_EXP(hd, T)
   if (float* d = p.out[0]) {
     d += row * 16;
     for (int i = 0; i < 3; ++i)
@@ -274,8 +257,8 @@ __device__ __forceinline__ void mlp_se3_row(const float* hd, const float* x, int
     for (int j = 0; j < 4; ++j) d[row * 4 + j] = hd[6 + j];
   if (float* d = p.out[2])
     for (int j = 0; j < 3; ++j) d[row * 3 + j] = hd[10 + j];
-  if (float* d = p.out[3])  // (the homogeneous coordinate of a rigid transform is exactly 1: no divide)
-    for (int i = 0; i < 3; ++i) d[row * 3 + i] = T[i][0] * x[0] + T[i][1] * x[1] + T[i][2] * x[2] + T[i][3];
+  if (float* d = p.out[3])
+    for (int i = 0; i < 3; ++i) d[row * 3 + i] = FG_SE3_POINT(T, x, i);
 }
 
 // what the training forward stores besides (fg_mlp_train_fwd)

@@ -172,6 +172,18 @@ def fused_wgrad_precision() -> str:
     return knob
 
 
+def fused_se3() -> bool:
+    """Whether the means are moved by one ``ops.se3_apply`` call in place of ``_se3`` + ``utils.transform_points``:
+    ``FG_FUSED_SE3`` (opt-in; read here and nowhere else, on the host, on every call) -- unset or "0": the torch ops; "1": the
+    fused op, forward and backward (profiles/se3_apply_fused.md).  Anything else is a ``ValueError``: a typo must not train
+    silently on the other path.  The callers (model.py) add their own conditions: CUDA float32 tensors, and a call that
+    ``deformed_points`` has not already taken."""
+    knob = os.environ.get("FG_FUSED_SE3", "0")
+    if knob not in ("0", "1"):
+        raise ValueError(f"FG_FUSED_SE3 wants 0 or 1, got {knob!r}")
+    return knob == "1"
+
+
 def fused_train_applies(module: nn.Module, x: torch.Tensor, other: torch.Tensor) -> bool:
     """Whether a taped ``module(x, other)`` runs as one ``ops.mlp_train`` call (``fused_train_mode``)."""
     return fused_train_mode(module, x, other) != ""
@@ -265,9 +277,10 @@ class FreeGaussianDeformableModel(nn.Module):
         _, rot, scale, pts = self._fused(x, t, (False, None, None, None))
         return pts, rot, scale
 
-    def forward(self, x: torch.Tensor, t: torch.Tensor):
-        if fused_applies(self, x, t):
-            return tuple(self._fused(x, t, (None, None, None, False))[:3])
+    def heads(self, x: torch.Tensor, t: torch.Tensor):
+        """The raw heads ``(w [N,3], v [N,3], d_rotation [N,4], d_scaling [N,3])`` of a call that is NOT a fused gradient-free
+        forward (``fused_applies``: that one goes from the positions to the transforms inside its kernel): through
+        ``ops.mlp_train`` where ``fused_train_mode`` says so, else the torch ops."""
         mode = fused_train_mode(self, x, t)
         if mode:
             from . import ops
@@ -277,15 +290,20 @@ class FreeGaussianDeformableModel(nn.Module):
             if self.is_blender:
                 aux = self.timenet(aux)
             heads = (self.branch_w, self.branch_v, self.gaussian_rotation, self.gaussian_scaling)
-            w, v, rot, scale = ops.mlp_train(x, aux, self.linear, heads, **_train_keywords(mode)).split((3, 3, 4, 3), dim=-1)
-            return self._se3(w, v), rot, scale
+            return ops.mlp_train(x, aux, self.linear, heads, **_train_keywords(mode)).split((3, 3, 4, 3), dim=-1)
         t_emb = positional_encoding(t, self.t_multires)
         if self.is_blender:
             t_emb = self.timenet(t_emb)
         inp = torch.cat([positional_encoding(x, self.multires), t_emb], dim=-1)
         h = _run_trunk(self.linear, inp, self.skip_at)
         w, v = _linear(self.branch_w, h), _linear(self.branch_v, h)
-        return self._se3(w, v), _linear(self.gaussian_rotation, h), _linear(self.gaussian_scaling, h)
+        return w, v, _linear(self.gaussian_rotation, h), _linear(self.gaussian_scaling, h)
+
+    def forward(self, x: torch.Tensor, t: torch.Tensor):
+        if fused_applies(self, x, t):
+            return tuple(self._fused(x, t, (None, None, None, False))[:3])
+        w, v, rot, scale = self.heads(x, t)
+        return self._se3(w, v), rot, scale
 
     @staticmethod
     def _se3(w: torch.Tensor, v: torch.Tensor) -> torch.Tensor:

@@ -19,7 +19,7 @@ from typing import Dict, List, Optional, Union
 import torch
 from torch import nn
 
-from .deform import FreeGaussianControllableModel, FreeGaussianDeformableModel, fused_applies
+from .deform import FreeGaussianControllableModel, FreeGaussianDeformableModel, fused_applies, fused_se3
 from .rasterization import num_sh_bases, rasterization
 from .utils import get_viewmat, knn_mean_distance, random_quat_tensor, resize_image, transform_points
 
@@ -133,6 +133,20 @@ def _pose_slot():
 # Per-step bookkeeping attributes (plain tensors / ints, never Parameters or sub-modules) are set past
 # nn.Module.__setattr__, whose parameter / buffer / module checks cost ~5 us a time, six times a step.
 _plain_set = object.__setattr__
+
+
+def _se3_fused_for(pts: torch.Tensor, times: torch.Tensor) -> bool:
+    """Whether the deformation's heads move ``pts`` through ``ops.se3_apply``: ``FG_FUSED_SE3=1`` (``deform.fused_se3``) and
+    CUDA float32 tensors, at least one row.  Taped or not."""
+    if not fused_se3():
+        return False
+    return pts.is_cuda and times.is_cuda and pts.dtype == times.dtype == torch.float32 and pts.dim() == 2 and pts.shape[0] >= 1
+
+
+def _se3_apply(w: torch.Tensor, v: torch.Tensor, pts: torch.Tensor) -> torch.Tensor:
+    from . import ops
+
+    return ops.se3_apply(w, v, pts)
 
 
 class FreeGaussianModel(nn.Module):
@@ -524,6 +538,11 @@ class FreeGaussianModel(nn.Module):
             if not torch.is_grad_enabled() and fused_applies(self.deform, pts, times):
                 # (no gradient wanted: the fused forward applies the transform itself and never writes [N,4,4])
                 means, d_rotation, d_scaling = self.deform.deformed_points(pts.detach(), times)
+            elif _se3_fused_for(pts, times):
+                # (FG_FUSED_SE3=1: the heads to the moved means in one launch, and one in the backward; pts is the
+                #  undetached parameter, so its gradient arrives as it does below)
+                w, v, d_rotation, d_scaling = self.deform.heads(pts.detach(), times)
+                means = _se3_apply(w, v, pts)
             else:
                 d_xyz, d_rotation, d_scaling = self.deform(pts.detach(), times)
                 means = transform_points(d_xyz, pts)  # (:840-843; not torch.bmm: utils.small_bmm)
@@ -618,6 +637,9 @@ class FreeGaussianControlModel(FreeGaussianModel):
                     t = t.to(self.device).expand(pts.shape[0], -1)
                     if fused_applies(self.deform, pts, t):
                         return self.deform.deformed_points(pts, t)[0]
+                    if _se3_fused_for(pts, t):
+                        w, v, _, _ = self.deform.heads(pts, t)
+                        return _se3_apply(w, v, pts)
                     T, _, _ = self.deform(pts, t)
                     return transform_points(T, pts)
 

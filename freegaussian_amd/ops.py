@@ -1261,6 +1261,65 @@ def bilagrid_apply(grids: torch.Tensor, cam_idx: int, rgb: torch.Tensor) -> torc
     return _BilagridApply.apply(_f32(grids, "grids"), cam_idx, _f32(rgb, "rgb"))
 
 
+def _rows3(t: torch.Tensor) -> torch.Tensor:
+    """An [N,3] float32 tensor whose rows are 3 consecutive floats a fixed number (>= 3) of floats apart, as it is -- a
+    contiguous one, or three columns of a wider row block such as ``mlp_train``'s [N,13] heads; anything else: a copy."""
+    if t.stride(1) == 1 and (t.shape[0] <= 1 or t.stride(0) >= 3):
+        return t
+    return t.contiguous()
+
+
+def _row_stride(t: torch.Tensor) -> int:
+    return t.stride(0) if t.shape[0] > 1 else 3
+
+
+class _Se3Apply(torch.autograd.Function):
+    """exp_se3 of the (w, v) heads applied to points (csrc/se3_apply.hip): saves its three inputs only (36 B a row); the
+    backward recomputes the transform and forms the gradients that are asked for."""
+
+    @staticmethod
+    def forward(ctx, w, v, pts):
+        N = pts.shape[0]
+        out = torch.empty_like(pts)
+        _call("fg_se3_apply_fwd", N, _ptr(w), _row_stride(w), _ptr(v), _row_stride(v), _ptr(pts), _ptr(out), _stream(),
+              stage="fg_se3_apply_fwd")  # fmt: skip
+        ctx.save_for_backward(w, v, pts)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_out):
+        w, v, pts = ctx.saved_tensors
+        want = ctx.needs_input_grad
+        if not any(want):
+            return None, None, None
+        g_out = _f32(g_out, "g_out")
+        g_w, g_v, g_pts = (torch.empty_like(pts) if k else None for k in want)
+        _call("fg_se3_apply_bwd", pts.shape[0], _ptr(w), _row_stride(w), _ptr(v), _row_stride(v), _ptr(pts), _ptr(g_out),
+              _ptr(g_w), 3, _ptr(g_v), 3, _ptr(g_pts), _stream(), stage="fg_se3_apply_bwd")  # fmt: skip
+        return g_w, g_v, g_pts
+
+
+def se3_apply(w: torch.Tensor, v: torch.Tensor, pts: torch.Tensor) -> torch.Tensor:
+    """The deformation net's heads ``w``, ``v`` [N,3] applied to ``pts`` [N,3] -> [N,3]: what
+    ``utils.transform_points(FreeGaussianDeformableModel._se3(w, v), pts)`` states in torch ops, as one launch forward and one
+    backward, with no [N,4,4] array in between (the contract is in include/fgraster.h).  ``w`` and ``v`` are read in place
+    where they are contiguous or columns of one row block (the [N,13] output of ``mlp_train``).  Differentiable with respect
+    to all three; the backward forms the gradients that are wanted and is stable at small ``|w|``
+    (profiles/se3_apply_parity.md).  No host synchronisation, nothing allocated outside torch's allocator: capturable."""
+    for name, t in (("w", w), ("v", v), ("pts", pts)):
+        if t.dim() != 2 or t.shape[1] != 3 or t.shape[0] != pts.shape[0]:
+            raise ValueError(f"w, v, pts [N,3] expected, got {tuple(w.shape)}, {tuple(v.shape)}, {tuple(pts.shape)}")
+        if not t.is_cuda:
+            raise _lib.FgRasterError(f"se3_apply runs on the GPU only ({name} is a CPU tensor; deform._se3 + utils.transform_points "
+                                     "is the torch statement of it)")  # fmt: skip
+        if t.dtype != torch.float32 or t.device != pts.device:
+            raise ValueError(f"float32 tensors on one device expected, got {name}: {t.dtype} on {t.device}")
+    if pts.shape[0] == 0:  # (nothing to launch; the result still hangs on its inputs)
+        return pts + (w + v) * 0.0
+    return _Se3Apply.apply(_rows3(w), _rows3(v), pts.contiguous())
+
+
 def color_correct_supported(numel: int, num_iters, eps) -> bool:
     """Does ``color_correct`` take ``numel // 3`` pixels with these arguments?  The library's own range (its query says) and
     the header's 0 < eps < 0.5."""

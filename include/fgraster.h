@@ -53,7 +53,8 @@ typedef void* fg_stream_t;
  * NAME: fg_bilagrid_supported, fg_bilagrid_bwd_workspace_bytes, fg_bilagrid_slice_fwd and fg_bilagrid_slice_bwd -- a library
  * without them has no fused bilateral-grid slice, and the host keeps its torch statement of it.  Likewise BY NAME:
  * fg_color_correct_workspace_bytes and fg_color_correct -- a library without them has no fused colour correction of the
- * metrics, and the host keeps its torch statement of it.) */
+ * metrics, and the host keeps its torch statement of it.  Likewise BY NAME: fg_se3_apply_fwd and fg_se3_apply_bwd -- a library
+ * without them has no fused SE(3) transform of the means, and the host keeps its torch statement of it.) */
 #define FG_COUNT_OUT_WORDS 16 /* int64 words of a count_out block (fg_stbin_count, fg_step_io): ABI 9 */
 
 int fg_abi_version(void);
@@ -1134,6 +1135,36 @@ int fg_bilagrid_slice_bwd(int H, int W, int GX, int GY, int GL, const float* gri
 size_t fg_color_correct_workspace_bytes(int64_t P, int num_iters);
 int fg_color_correct(int64_t P, const float* img, const float* ref, int num_iters, double eps, float* out, float* warps,
                      int32_t* rank, void* workspace, size_t workspace_bytes, fg_stream_t stream);
+
+/* ---- SE the SE(3) exponential of the deformation net's (w, v) heads applied to points (found BY NAME, see FG_ABI_MINOR),
+ * forward and backward, one streaming launch each (csrc/se3_apply.hip, csrc/se3_math.h; freegaussian_amd/deform.py _se3 +
+ * utils.exp_se3 + utils.transform_points are the torch statement).  All fp32.  Per row r < N:
+ *   theta = |w_r|,  ws = w_r / theta + 1e-5,  vs = v_r / theta + 1e-5  (the offsets are constants of the function),
+ *   W = hat(ws),  R = I + sin(theta) W + (1 - cos theta) W^2,  G = theta I + (1 - cos theta) W + (theta - sin theta) W^2,
+ *   out_r = R pts_r + G vs     in the arithmetic of utils.exp_se3; the homogeneous coordinate is exactly 1: no divide.
+ *   w, v    rows of 3 floats, w_stride / v_stride floats apart (>= 3): two contiguous [N,3] arrays (stride 3), or columns 0..2
+ *           and 3..5 of the fused MLP's [N,13] head block read in place (stride 13).  They may overlap each other.
+ *   pts, out, g_out, g_pts   contiguous [N,3].
+ *   g_w, g_v   rows of 3 floats, gw_stride / gv_stride floats apart (>= 3; looked at only where the pointer is not null).
+ * fg_se3_apply_fwd writes out and nothing else.  fg_se3_apply_bwd recomputes everything from w, v, pts (the forward saves
+ * nothing) and writes the exact derivative of the function above:  g_w, g_v, g_pts = d(sum g_out . out) / d(w, v, pts),
+ * evaluated in fp32 in forms that do not cancel at small theta (profiles/se3_apply_parity.md).  Any of g_w / g_v / g_pts may
+ * be null: that gradient is neither computed nor written (all null: nothing is launched).
+ *   Rows are independent: a row with w = 0 gives non-finite values in its own outputs, as the torch ops do, and touches no
+ *   other row.  No atomics, no workspace: two runs are bit for bit equal.
+ *   Aliasing: an output must not overlap an input or another output, by the span from its first to its last float -- except
+ *   that g_w and g_v may be columns of one row block: equal strides, at least 3 floats and at most stride - 3 floats apart.
+ *   FG_ERR_INVALID_ARG: N < 0, a null w / v / pts / out / g_out, a stride below 3, an output that overlaps as above;
+ *   FG_ERR_UNSUPPORTED: N > FG_SE3_MAX_ROWS or a stride above FG_SE3_MAX_STRIDE.  N == 0 is FG_OK with no launch (after the
+ *   null, sign and stride checks).  All before any launch.  Row and byte offsets are 64-bit.  Asynchronous, capturable in a
+ *   graph, no state, no environment.  Measured (profiles/se3_apply_fused.md). */
+#define FG_SE3_MAX_ROWS ((int64_t)1 << 38)
+#define FG_SE3_MAX_STRIDE ((int64_t)1 << 16)
+int fg_se3_apply_fwd(int64_t N, const float* w, int64_t w_stride, const float* v, int64_t v_stride, const float* pts, float* out,
+                     fg_stream_t stream);
+int fg_se3_apply_bwd(int64_t N, const float* w, int64_t w_stride, const float* v, int64_t v_stride, const float* pts,
+                     const float* g_out, float* g_w, int64_t gw_stride, float* g_v, int64_t gv_stride, float* g_pts,
+                     fg_stream_t stream);
 
 #ifdef __cplusplus
 }
