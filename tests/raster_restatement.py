@@ -9,6 +9,8 @@ test is imported here.  Written from ``oracle.raster_oracle`` (``_tile_terms``, 
     backward(...)        the five gradients and, beside each, its ABSOLUTE ACCUMULATION (every per-pixel term by magnitude)
     cotangents(...)      one cotangent group at a time (render / alpha / both), zero on excluded pixels
     MUTANTS              wrong restatements (float64, CPU only: they prove that the bound has teeth)
+    composite_scene, epilogue, epilogue_backward, EPILOGUE_CASES, epilogue_gradients
+                         the post-composite folded into the kernels (``Composite``: background, clamp, clamp mask)
 
 ROW DISTANCE.  |g - g64|_2 / |A64|_2 over a row's columns, A the absolute accumulation of the same tensor (for ``means2d``
 that is absgrad itself).  A gradient row is a signed sum over pixels that cancels, and the kernel's float atomics arrive in
@@ -26,13 +28,19 @@ MUTANTS (``mutant=`` of ``composite`` / ``backward``):
     suffix_includes_self    the suffix sum S_i includes the entry's own term
     conic_b_halved          the conic-b gradient is halved
     absgrad_abs_of_sum      absgrad is |sum over a tile's pixels| instead of the sum of magnitudes
+of ``epilogue`` / ``epilogue_backward``:
+    blocked_channel_passes_gradient          a channel clamped at a bound keeps its cotangent
+    background_missing_from_alpha_gradient   the alpha cotangent lacks - sum_c v[c] * background[c]
+    mask_bit_of_next_channel                 channel c is blocked by the mask bit of channel c + 1
+    clamp_reaches_channel_n_clamp            the clamp (and its mask bit) covers channel n_clamp as well
 
 EXCLUDED PIXELS.  A pixel one of whose decisions (alpha against 1/255 and 0.999, sigma against 0, T against 1e-4) lies within
 rounding of its threshold may legitimately take the other branch under another exp(): it is excluded -- not compared in the
 forward, and its cotangents are zero.  The backward is linear in every pixel's cotangents, so an excluded pixel drops out
-of every gradient on both sides, whatever the kernel did there.
+of every gradient on both sides, whatever the kernel did there.  The composite epilogue adds one decision, a clamped channel's
+value against 0 and against 1: a pixel within CLAMP_MARGIN (absolute) of either is excluded in the same way.
 """
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from typing import Dict, List, Optional
 
 import torch
@@ -48,6 +56,7 @@ FLOOR = 16 * 2.0**-24  # floor of the fp32 yardstick E32
 ALPHA_MARGIN = 1e-4  # relative distance of opacity * exp(-sigma) from 1/255 and from 0.999
 SIGMA_MARGIN = 1e-4  # absolute distance of sigma from 0
 T_MARGIN = 1e-3  # relative distance of T from 1e-4
+CLAMP_MARGIN = 1e-4  # absolute distance of a clamped channel's value from 0 and from 1 (the composite epilogue)
 SEED = 2  # the scene the tests use (tests/test_raster_rows_host.py checks its exclusions)
 
 # The GPU bound is F * E32(regime, group, tensor) -- E32(pixel class) in the forward.  Set from the MI355X run recorded in
@@ -62,7 +71,9 @@ PIXEL_CLASSES = ("partial", "deep", "wall", "other")
 COUNTS = dict(plain=40, opaque=12, faint=12, barely=12, subpixel=12, huge=6, needle=12, edge=12, deep=300, wall=14,
               occluded=8, indefinite=6)  # fmt: skip
 DENSE_REGIMES = ("plain", "opaque", "needle", "edge", "indefinite")  # (left out of the deep tile's list)
-MUTANTS = ("clamp_passes_gradient", "stop_entry_composited", "suffix_includes_self", "conic_b_halved", "absgrad_abs_of_sum")
+MUTANTS = ("clamp_passes_gradient", "stop_entry_composited", "suffix_includes_self", "conic_b_halved", "absgrad_abs_of_sum",
+           "blocked_channel_passes_gradient", "background_missing_from_alpha_gradient", "mask_bit_of_next_channel",
+           "clamp_reaches_channel_n_clamp")  # fmt: skip
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -429,3 +440,131 @@ def pixel_masks(fwd64, kept) -> Dict[str, Dict[str, torch.Tensor]]:
     (the others must be exactly zero, which the GPU test asserts, and take no part in the class's maximum)."""
     cls = P.masks_of_index(pixel_class(), PIXEL_CLASSES)
     return dict(render=P.restrict(cls, kept & (fwd64["weight"] > 0)), alpha=P.restrict(cls, kept))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the composite epilogue (``Composite`` in csrc/raster.hip: fg_raster_composite_fwd / _bwd)
+
+
+def composite_scene(scene: Optional[RegimeScene] = None) -> RegimeScene:
+    """The sibling of ``scene`` (the regime scene of SEED) the epilogue cases run on: the same rows and the same lists, the
+    colours c (U(0,1): over a background in [0,1] they never leave [0,1]) mapped to 2 c in channel 0, 1.75 c in channels 1 and 2
+    and 2 c - 1 (signed, as flow and depth residuals are) in channels 3-7, so that a bound is crossed on a good share of the
+    pixels but never on most.  (2 c in channels 1 and 2 as well: 73 % of the pixels above 1 over a white background, beyond what
+    tests/test_raster_rows_host.py allows; this seed's channel 0 is the darkest.)"""
+    scene = regime_scene(SEED) if scene is None else scene
+    c = scene.colours.double()
+    return replace(scene, colours=torch.cat([2.0 * c[:, :1], 1.75 * c[:, 1:3], 2.0 * c[:, 3:] - 1.0], 1).float().contiguous())
+
+
+def background_in(background, dtype) -> Optional[torch.Tensor]:
+    """The background as the kernels get it -- fp32 values -- in ``dtype``; None stays None."""
+    return None if background is None else torch.as_tensor(background, dtype=torch.float32).to(dtype)
+
+
+def epilogue(fwd, background, n_clamp: int, dtype, mutant: Optional[str] = None, exact_channels=()):
+    """``fwd``: what ``composite`` returned.  -> out [H,W,C] = render + (1 - alpha) * background, its first ``n_clamp`` channels
+    clamped to [0,1]; blocked [H,W,C] bool: the clamped channel's value lies STRICTLY outside [0,1] (torch.clamp's gradient
+    rule: it passes at the bounds themselves); bound_distance [H,W]: the smallest min(|v|, |v - 1|) over the clamped channels
+    before clamping, inf without any -- ``exact_channels``: channels left out of it, whose value sits ON a bound by
+    construction (colours and background identically zero: 0 in every arithmetic); weight [H,W]: what an unblocked channel's
+    error is measured by, sum_i w_i |c_i|_inf + (1 - alpha) |background|_inf."""
+    render, alpha = fwd["render"].to(dtype), fwd["alpha"].to(dtype)
+    C = render.shape[-1]
+    om = 1.0 - alpha
+    out = render.clone()
+    weight = fwd["weight"].to(dtype).clone()
+    if background is not None:
+        bg = background_in(background, dtype)
+        out = out + om[..., None] * bg
+        weight = weight + om * bg.abs().max()
+    if mutant == "clamp_reaches_channel_n_clamp":
+        n_clamp = min(n_clamp + 1, C)
+    blocked = torch.zeros_like(out, dtype=torch.bool)
+    bound_distance = torch.full(alpha.shape, float("inf"), dtype=dtype)
+    if n_clamp > 0:
+        v = out[..., :n_clamp]
+        blocked[..., :n_clamp] = (v < 0) | (v > 1)
+        near = torch.minimum(v.abs(), (v - 1.0).abs())
+        for c in exact_channels:
+            near[..., c] = float("inf")
+        bound_distance = near.min(dim=-1).values
+        out[..., :n_clamp] = v.clamp(0.0, 1.0)
+    return dict(out=out, blocked=blocked, bound_distance=bound_distance, weight=weight)
+
+
+def epilogue_backward(v_out, v_alpha, blocked, background, mutant: Optional[str] = None):
+    """-> (v_render_eff, v_alpha_eff), which feed ``backward`` unchanged: the blocked channels' cotangents zeroed, and
+    v_alpha - sum_c v_render_eff[c] * background[c] (d/d alpha of (1 - alpha) * background)."""
+    if mutant == "mask_bit_of_next_channel":  # channel c reads bit c + 1 (the last one a bit nobody set)
+        blocked = torch.cat([blocked[..., 1:], torch.zeros_like(blocked[..., :1])], -1)
+    if mutant == "blocked_channel_passes_gradient":
+        blocked = torch.zeros_like(blocked)
+    v_render = torch.where(blocked, torch.zeros_like(v_out), v_out)
+    if background is None or mutant == "background_missing_from_alpha_gradient":
+        return v_render, v_alpha.clone()
+    return v_render, v_alpha - (v_render * background_in(background, v_out.dtype)).sum(-1)
+
+
+@dataclass(frozen=True)
+class EpilogueCase:
+    name: str
+    channels: int
+    background: Optional[tuple]
+    n_clamp: int
+
+
+EPILOGUE_CASES = (
+    EpilogueCase("model-rgb", 3, (1.0, 0.25, 0.0), 3),  # the model's path; background components exactly at both bounds
+    EpilogueCase("model-rgbd", 4, (1.0, 1.0, 1.0, 0.0), 3),  # RGB+ED: the depth channel unclamped and signed
+    EpilogueCase("bg-only", 3, (0.2, 0.3, 0.4), 0),  # no mask: only the alpha-cotangent term
+    EpilogueCase("clamp-only", 3, None, 3),  # mask without a background
+    EpilogueCase("flow-6", 6, (0.5, 0.5, 0.5, 0.0, 0.0, 0.0), 3),  # three unclamped signed channels behind the mask
+    EpilogueCase("all-8", 8, (0.25,) * 8, 8),  # all eight mask bits; channels 3-7 are blocked below 0
+    EpilogueCase("one", 1, (0.25,), 1),  # a single channel
+)
+CASE = {c.name: c for c in EPILOGUE_CASES}
+# THE BOUND ITSELF: channel 0 of every row is 0 and so is its background -- the value is 0 in every arithmetic, ON the bound,
+# where the clamp passes the gradient (``bound_scene``; channel 0 is an ``exact_channels`` entry: it excludes no pixel)
+BOUND_CASE = EpilogueCase("bound", 3, (0.0, 0.25, 1.0), 3)
+
+
+def bound_scene(scene: RegimeScene) -> RegimeScene:
+    colours = scene.colours.clone()
+    colours[:, 0] = 0.0
+    return replace(scene, colours=colours)
+
+
+def epilogue_gradients(scene: RegimeScene, case: EpilogueCase, dtype, kept: torch.Tensor, mutant: Optional[str] = None,
+                       groups=GROUPS, exact_channels=()):  # fmt: skip
+    """One forward of the restatement with the case's epilogue in ``dtype`` and one backward per group.
+    -> (forward, epilogue, compared, {group: (grads, accum)}).  ``compared`` [H,W] bool: ``kept`` and farther than CLAMP_MARGIN
+    from either bound in FLOAT64 (the same pixels whatever ``dtype`` or ``mutant``); the cotangents are zero elsewhere.
+    ``accum`` is ``backward``'s with every cotangent by magnitude: |v_render_eff| and |v_alpha| + sum_c |v_render_eff[c] *
+    background[c]| -- the alpha cotangent the walk sees is itself a sum that cancels."""
+    fwd = composite(scene, case.channels, dtype)
+    ep = epilogue(fwd, case.background, case.n_clamp, dtype, mutant, exact_channels)
+    if dtype == torch.float64 and mutant is None:
+        near = ep["bound_distance"]
+    else:
+        near = epilogue(composite(scene, case.channels, torch.float64), case.background, case.n_clamp, torch.float64,
+                        exact_channels=exact_channels)["bound_distance"]  # fmt: skip
+    compared = kept & (near > CLAMP_MARGIN)
+    bg = background_in(case.background, dtype)
+    res = {}
+    for group in groups:
+        vo, va = cotangents(case.channels, group, compared)
+        vo, va = vo.to(dtype), va.to(dtype)
+        vr_eff, va_eff = epilogue_backward(vo, va, ep["blocked"], bg, mutant)
+        grads, _ = backward(scene, case.channels, vr_eff, va_eff, fwd["alpha"], dtype)
+        va_abs = va.abs() if bg is None else va.abs() + (vr_eff * bg).abs().sum(-1)
+        _, accum = backward(scene, case.channels, vr_eff.abs(), va_abs, fwd["alpha"], dtype)
+        res[group] = (grads, accum)
+    return fwd, ep, compared, res
+
+
+def epilogue_forward_distance(out, ep64) -> torch.Tensor:
+    """[H,W]: the largest |out - out64| / weight over a pixel's UNBLOCKED channels (a blocked channel is exactly 0 or 1: the
+    GPU test asserts that; it takes no part here).  0 where every channel is blocked."""
+    d = P.distance(out.detach().cpu().double(), ep64["out"], ep64["weight"][..., None].expand_as(ep64["out"]))
+    return torch.where(ep64["blocked"], torch.zeros_like(d), d).max(dim=-1).values

@@ -3,7 +3,10 @@ restatement is the pinned oracle's ``rasterize`` / ``rasterize_backward(alpha_ou
 the pixels left out for sitting on a decision threshold are few and cost no row more than a fifth of its footprint, fp32 and
 float64 take the same decisions on every pixel that is kept, and the row-wise bound the GPU test applies (F x the fp32
 restatement's own row distance from float64, per regime, cotangent group and tensor; tests/parity_common.py has the
-protocol) catches each wrong restatement."""
+protocol) catches each wrong restatement.  The composite epilogue (``R.epilogue`` / ``R.epilogue_backward``, the named cases of
+``R.EPILOGUE_CASES`` on ``R.composite_scene``): the pair is autograd's clamp(render + (1 - alpha) * bg, 0, 1) exactly, fp32 and
+float64 agree on the mask, few pixels are left out, every clamped channel is blocked on a good share of the pixels and open on
+most, and its four mutants are caught in the same way."""
 import functools
 
 import pytest
@@ -29,6 +32,17 @@ def _margins():
 @functools.lru_cache(maxsize=None)
 def _grads(dtype, mutant=None, channels=C):
     return R.gradients(_scene(), channels, dtype, _margins()["kept"], mutant=mutant)
+
+
+@functools.lru_cache(maxsize=None)
+def _composite_scene():
+    return R.composite_scene(_scene())
+
+
+@functools.lru_cache(maxsize=None)
+def _epilogue(case, dtype, mutant=None):
+    """(forward, epilogue, compared, {group: (grads, accum)}) of a named epilogue case on the composite scene."""
+    return R.epilogue_gradients(_composite_scene(), R.CASE[case], dtype, _margins()["kept"], mutant=mutant)
 
 
 def _tile_pixels(tile):
@@ -190,29 +204,52 @@ def test_yardsticks_are_floored_and_finite():
 LIVE = tuple(k for k in R.COUNTS if k not in ("faint", "occluded"))
 GEOMETRY = ("means2d", "absgrad", "conics", "opacities")
 # (mutant, cotangent groups that drive it, tensors it reaches, regimes it concerns)
+NOT_WALL = tuple(k for k in LIVE if k != "wall")
+MANY_PIXELS = tuple(k for k in LIVE if k not in ("barely", "subpixel"))
+# (mutant, cotangent groups that drive it, tensors it reaches, regimes it concerns, epilogue case or None: the plain raster)
 MUTANT_CASES = [
     # the clamped pixel of an opaque row is the one its mean sits in: dx, dy ~ 0.03 sigma there and the position and
     # shape gradients through it vanish; the opacity gradient does not
-    ("clamp_passes_gradient", R.GROUPS, ("opacities",), ("opaque",)),
+    ("clamp_passes_gradient", R.GROUPS, ("opacities",), ("opaque",), None),
     # the rows the stop rule drops at every pixel: the wall's rear rows and everything behind it
-    ("stop_entry_composited", R.GROUPS, R.TENSORS, ("wall", "occluded")),
+    ("stop_entry_composited", R.GROUPS, R.TENSORS, ("wall", "occluded"), None),
     # (the alpha group has no suffix sums: v_render = 0)
-    ("suffix_includes_self", ("render", "both"), GEOMETRY, LIVE),
-    ("conic_b_halved", R.GROUPS, ("conics",), LIVE),
-    ("absgrad_abs_of_sum", R.GROUPS, ("absgrad",), LIVE),
+    ("suffix_includes_self", ("render", "both"), GEOMETRY, LIVE, None),
+    ("conic_b_halved", R.GROUPS, ("conics",), LIVE, None),
+    ("absgrad_abs_of_sum", R.GROUPS, ("absgrad",), LIVE, None),
+    # the composite epilogue (the alpha group has v_out = 0: neither the mask nor the background term acts).  A blocked
+    # channel's cotangent reaches every tensor: the colours directly, the others through <c_j, v> and the alpha term.  (Over
+    # white and in the signed channels every regime's rows hold blocked pixels; over model-rgb's background the deep tile,
+    # which averages 300 faint rows, has none.)
+    ("blocked_channel_passes_gradient", ("render", "both"), R.TENSORS, LIVE, "model-rgbd"),
+    ("blocked_channel_passes_gradient", ("render", "both"), R.TENSORS, LIVE, "all-8"),
+    # the alpha cotangent reaches a row as T_final * v_alpha: nothing of it is left behind the wall (T_final <= 1e-4), and
+    # the colour gradient does not see it
+    ("background_missing_from_alpha_gradient", ("render", "both"), GEOMETRY, NOT_WALL, "bg-only"),
+    ("background_missing_from_alpha_gradient", ("render", "both"), GEOMETRY, NOT_WALL, "model-rgb"),
+    ("mask_bit_of_next_channel", ("render", "both"), R.TENSORS, LIVE, "model-rgbd"),
+    ("mask_bit_of_next_channel", ("render", "both"), R.TENSORS, LIVE, "all-8"),
+    # the unclamped signed channel leaves [0,1] on a third of the pixels: of the rows of a few pixels (barely, sub-pixel)
+    # fewer than three quarters hold one
+    ("clamp_reaches_channel_n_clamp", ("render", "both"), R.TENSORS, MANY_PIXELS, "model-rgbd"),
 ]
 
 
+def _reference_and_mutant(mutant, case):
+    """-> (g32, g64, gm): {group: (grads, accum)} of the fp32, the float64 and the mutant's float64 restatement."""
+    if case is None:
+        return _grads(torch.float32)[1], _grads(torch.float64)[1], _grads(torch.float64, mutant)[1]
+    return _epilogue(case, torch.float32)[3], _epilogue(case, torch.float64)[3], _epilogue(case, torch.float64, mutant)[3]
+
+
 def mutant_shares(factor):
-    """-> {(mutant, group, tensor, regime): (caught, rows, smallest caught-making F)}: a row of the mutant's float64 gradient
-    is CAUGHT when the GPU test would flag it -- not zero where the true row is exactly zero, or at least 4 * factor * E32
-    from the true row.  Rows that are zero in both do not count (the mutant does not reach them)."""
+    """-> {(mutant, group, tensor, regime, case): (caught, rows, smallest caught-making F)}: a row of the mutant's float64
+    gradient is CAUGHT when the GPU test would flag it -- not zero where the true row is exactly zero, or at least 4 * factor *
+    E32 from the true row.  Rows that are zero in both do not count (the mutant does not reach them)."""
     sc = _scene()
-    _, g32 = _grads(torch.float32)
-    _, g64 = _grads(torch.float64)
     out = {}
-    for mutant, groups, tensors, regimes in MUTANT_CASES:
-        _, gm = _grads(torch.float64, mutant)
+    for mutant, groups, tensors, regimes, case in MUTANT_CASES:
+        g32, g64, gm = _reference_and_mutant(mutant, case)
         for group in groups:
             for tensor in tensors:
                 ref, acc = g64[group][0][tensor], g64[group][1][tensor]
@@ -226,7 +263,7 @@ def mutant_shares(factor):
                         continue  # (no colour gradient without v_render)
                     caught = torch.where(zero[rows], ~zero_m[rows], d[rows] >= 4 * factor * e32[regime])
                     ratios = torch.where(zero[rows], torch.full_like(d[rows], float("inf")), d[rows] / e32[regime])
-                    out[(mutant, group, tensor, regime)] = (int(caught.sum()), len(rows), P.three_quarter_cap(ratios))
+                    out[(mutant, group, tensor, regime, case)] = (int(caught.sum()), len(rows), P.three_quarter_cap(ratios))
     return out
 
 
@@ -243,16 +280,21 @@ def test_mutants_are_caught_by_the_row_bound():
     for mutant in R.MUTANTS:
         fm, _ = _grads(torch.float64, mutant)
         assert torch.equal(fm["render"], f64["render"]) == (mutant != "stop_entry_composited"), mutant
+    # (of the epilogue's mutants only ``clamp_reaches_channel_n_clamp`` changes the finished image)
+    for mutant, _, _, _, case in MUTANT_CASES:
+        if case is not None:
+            same = torch.equal(_epilogue(case, torch.float64, mutant)[1]["out"], _epilogue(case, torch.float64)[1]["out"])
+            assert same == (mutant != "clamp_reaches_channel_n_clamp"), (mutant, case)
     factor = 1.0 if R.F is None else R.F
     shares = mutant_shares(factor)
     cap = min(v[2] for v in shares.values())
     worst = {}
-    for (mutant, group, tensor, regime), (caught, rows, c) in shares.items():
-        key = (mutant, regime)
+    for (mutant, group, tensor, regime, case), (caught, rows, c) in shares.items():
+        key = (mutant, regime) if case is None else (mutant, regime, case)
         if key not in worst or c < worst[key][4]:
             worst[key] = (caught, rows, group, tensor, c)
-    for (mutant, regime), (caught, rows, group, tensor, c) in worst.items():
-        print(f"{mutant} {regime}: {caught}/{rows} rows caught at F = {factor:g} in its weakest cell ({group}, {tensor}), which caps F at {c:.1f}")
+    for (mutant, regime, *case), (caught, rows, group, tensor, c) in worst.items():
+        print(f"{mutant} {regime}{' ' + case[0] if case else ''}: {caught}/{rows} rows caught at F = {factor:g} in its weakest cell ({group}, {tensor}), which caps F at {c:.1f}")
     print(f"the cap on F: {cap:.1f}")
     failures = [f"{k}: {v[0]}/{v[1]}" for k, v in shares.items() if v[1] == 0 or 4 * v[0] < 3 * v[1]]
     assert not failures, "\n".join(failures)
@@ -270,3 +312,112 @@ def test_mutants_are_caught_by_the_row_bound():
                 rows = sc.rows(regime)
                 rows = rows[zero[rows]]
                 assert len(rows) >= 4 and not bool(P.zero_rows(gm[group][0][tensor])[rows].any()), (group, tensor, regime)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the composite epilogue
+
+
+@pytest.mark.parametrize("case", R.EPILOGUE_CASES, ids=[c.name for c in R.EPILOGUE_CASES])
+def test_epilogue_pair_is_autograd_of_clamp(case):
+    """``epilogue`` / ``epilogue_backward`` against torch.autograd.grad of clamp(render + (1 - alpha) * bg, 0, 1) with the
+    unclamped channels concatenated behind the clamped ones, render and alpha float64 leaves: exactly."""
+    fwd = R.composite(_composite_scene(), case.channels, torch.float64)
+    render, alpha = fwd["render"].clone().requires_grad_(True), fwd["alpha"].clone().requires_grad_(True)
+    bg = torch.zeros(case.channels, dtype=torch.float64) if case.background is None else R.background_in(case.background, torch.float64)
+    pre = render + (1.0 - alpha)[..., None] * bg
+    n = case.n_clamp
+    out = torch.cat([torch.clamp(pre[..., :n], 0.0, 1.0), pre[..., n:]], -1)
+    ep = R.epilogue(fwd, case.background, n, torch.float64)
+    assert torch.equal(ep["out"], out.detach())
+    assert not bool(ep["blocked"][..., n:].any()) and bool(ep["blocked"].any()) == (n > 0)
+    assert bool(torch.isinf(ep["bound_distance"]).all()) == (n == 0)
+    everything = torch.ones(R.HEIGHT, R.WIDTH, dtype=torch.bool)
+    for group in R.GROUPS:
+        vo, va = R.cotangents(case.channels, group, everything)
+        g_render, g_alpha = torch.autograd.grad((out * vo).sum() + (alpha * va).sum(), (render, alpha), retain_graph=True)
+        vr_eff, va_eff = R.epilogue_backward(vo, va, ep["blocked"], None if case.background is None else bg)
+        assert torch.equal(vr_eff, g_render), (case.name, group)
+        assert torch.equal(va_eff, g_alpha), (case.name, group)
+
+
+def test_epilogue_fp32_and_float64_agree_on_the_mask():
+    for case in R.EPILOGUE_CASES:
+        _, e32, c32, _ = _epilogue(case.name, torch.float32)
+        _, e64, compared, _ = _epilogue(case.name, torch.float64)
+        assert torch.equal(c32, compared)
+        assert torch.equal(e32["blocked"][compared], e64["blocked"][compared]), case.name
+
+
+def test_epilogue_exclusions_are_few():
+    """Conditions on the inputs: in every case at most 2 % of the image's 2880 pixels are left out in total (the walk's margins
+    and CLAMP_MARGIN together)."""
+    kept = _margins()["kept"]
+    for case in R.EPILOGUE_CASES:
+        _, _, compared, _ = _epilogue(case.name, torch.float64)
+        assert compared.numel() == 2880 and not bool((compared & ~kept).any())
+        out = int((~compared).sum())
+        print(f"{case.name}: {out} of 2880 pixels left out ({100 * out / 2880:.2f} %), {int((kept & ~compared).sum())} of them "
+              f"for lying within {R.CLAMP_MARGIN:g} of a bound")  # fmt: skip
+        assert out <= 0.02 * 2880, case.name
+        if case.n_clamp == 0:
+            assert torch.equal(compared, kept)
+
+
+def test_epilogue_cases_clamp_on_both_sides_of_every_channel():
+    """Conditions on the inputs: in every case meant to clamp, each clamped channel is blocked on at least 5 % of the compared
+    pixels and not blocked on at least 30 %; the signed channels are blocked BELOW 0, the doubled ones above 1."""
+    for case in R.EPILOGUE_CASES:
+        fwd, ep, compared, _ = _epilogue(case.name, torch.float64)
+        for c in range(case.n_clamp):
+            share = float(ep["blocked"][..., c][compared].float().mean())
+            low = bool((ep["out"][..., c][compared & ep["blocked"][..., c]] == 0.0).all())
+            print(f"{case.name} channel {c}: blocked on {100 * share:.1f} % of the compared pixels, {'below 0' if low else 'above 1'}")
+            assert 0.05 <= share <= 0.70, (case.name, c, share)
+            assert low == (c >= 3), (case.name, c)
+    # bit 7 of the mask byte is set alone and together with others
+    _, ep, compared, _ = _epilogue("all-8", torch.float64)
+    b = ep["blocked"][compared]
+    assert bool((b[:, 7] & ~b[:, :7].any(dim=1)).any()) and bool((b[:, 7] & b[:, :7].any(dim=1)).any()) and bool((~b[:, 7]).any())
+
+
+def test_epilogue_yardsticks_are_floored_and_finite():
+    sc = _composite_scene()
+    for case in R.EPILOGUE_CASES:
+        f32, e32, _, g32 = _epilogue(case.name, torch.float32)
+        f64, e64, compared, g64 = _epilogue(case.name, torch.float64)
+        d = R.epilogue_forward_distance(e32["out"], e64)
+        for cls, e in P.yardstick(P.restrict(P.masks_of_index(R.pixel_class(), R.PIXEL_CLASSES), compared), d, R.FLOOR).items():
+            assert R.FLOOR <= e < 1e-4, (case.name, cls, e)
+        blocked = compared[..., None] & e64["blocked"]
+        assert torch.equal(e32["out"][blocked].double(), e64["out"][blocked])  # exactly 0 or 1, on the same side
+        for group in R.GROUPS:
+            grads, accum = g64[group]
+            for tensor in R.TENSORS:
+                assert bool(torch.isfinite(grads[tensor]).all()) and bool((accum[tensor] >= 0).all())
+                assert bool(P.zero_rows(grads[tensor])[P.zero_rows(accum[tensor])].all())
+                assert bool((g32[group][0][tensor][P.zero_rows(grads[tensor])] == 0).all()), (case.name, group, tensor)
+                d32 = P.distance(g32[group][0][tensor], grads[tensor], accum[tensor], rows=True)
+                for regime, e in P.yardstick(P.live_row_masks(sc.labels, grads[tensor]), d32, R.FLOOR).items():
+                    assert R.FLOOR <= e < 1e-3, (case.name, group, tensor, regime, e)
+
+
+def test_epilogue_bound_scene_sits_on_the_bound_and_passes_the_gradient():
+    """Conditions on the inputs of the GPU test's 'bound itself' sub-scene: channel 0 is exactly 0 on every pixel in both
+    arithmetics, never blocked, excludes no pixel -- and its colour gradient is not zero on at least 90 % of the rows that
+    contribute anywhere."""
+    sc, kept = R.bound_scene(_composite_scene()), _margins()["kept"]
+    total, _ = _footprints()
+    res = {}
+    for dtype in (torch.float32, torch.float64):
+        res[dtype] = R.epilogue_gradients(sc, R.BOUND_CASE, dtype, kept, exact_channels=(0,))
+        _, ep, compared, _ = res[dtype]
+        assert bool((ep["out"][..., 0] == 0).all()) and not bool(ep["blocked"][..., 0].any())
+        assert int((~compared).sum()) <= 0.02 * 2880
+    for group in ("render", "both"):
+        g0 = res[torch.float64][3][group][0]["features"][:, 0]
+        live = total > 0
+        share = float((g0[live] != 0).float().mean())
+        print(f"{group}: the channel-0 colour gradient is not zero on {100 * share:.1f} % of the {int(live.sum())} contributing rows")
+        assert share >= 0.9
+        assert bool((g0[~live] == 0).all())
