@@ -140,6 +140,16 @@ SIGNATURES = {
     "fg_se3_apply_fwd": (c_int, [c_int64, P, c_int64, P, c_int64, P, P, P]),  # (N, w, w_stride, v, v_stride, pts, out, stream)
     # (N, w, w_stride, v, v_stride, pts, g_out, g_w, gw_stride, g_v, gv_stride, g_pts, stream)
     "fg_se3_apply_bwd": (c_int, [c_int64, P, c_int64, P, c_int64, P, P, P, c_int64, P, c_int64, P, P]),
+    # the stage-2 control stage on a plan of the mask (csrc/control.hip); strides in floats
+    "fg_control_supported": (c_int, [c_int]),  # (M) -> 1 or 0
+    "fg_control_workspace_bytes": (c_size_t, [c_int64, c_int]),  # (n, M)
+    # (n, M, a, a_stride, b, b_stride, bits, counts (HOST int32[M]), workspace, bytes, d_avg, stream)
+    "fg_control_attr_mean": (c_int, [c_int64, c_int, P, c_int64, P, c_int64, P, P, P, c_size_t, P, P]),
+    "fg_control_value_rows": (c_int, [c_int64, c_int, P, P, P, P]),  # (n, M, bits, d_avg, value, stream)
+    # (N, n, rank, means, d_xyz, xyz_stride, d_rot, rot_stride, d_scale, scale_stride, out_means, d_rotation, d_scaling, stream)
+    "fg_control_scatter_fwd": (c_int, [c_int64, c_int64, P, P, P, c_int64, P, c_int64, P, c_int64, P, P, P, P]),
+    # (n, N, sel_index, g_means, g_rotation, g_scaling, g_d_xyz, xyz_stride, g_d_rot, rot_stride, g_d_scale, scale_stride, stream)
+    "fg_control_scatter_bwd": (c_int, [c_int64, c_int64, P, P, P, P, P, c_int64, P, c_int64, P, c_int64, P]),
 }  # fmt: skip
 
 # test hooks, not declared in the public header
@@ -156,6 +166,7 @@ MLP_FP32, MLP_BF16X3 = 0, 1  # FG_MLP_FP32, FG_MLP_BF16X3: fg_mlp_desc::precisio
 MLP_WGRAD_MAX_SLAB, MLP_WGRAD_MIN_SPLIT = 4096, 512  # FG_MLP_WGRAD_MAX_SLAB, FG_MLP_WGRAD_MIN_SPLIT
 MLP_TRAIN_BWD_CHUNK_SLABS = 16  # FG_MLP_TRAIN_BWD_CHUNK_SLABS
 COLOR_CORRECT_MAX_ITERS = 8  # FG_COLOR_CORRECT_MAX_ITERS
+CONTROL_MAX_ATTRS = 32  # FG_CONTROL_MAX_ATTRS
 
 
 def mlp_enc_width(aux_width: int) -> int:

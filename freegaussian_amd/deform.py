@@ -184,6 +184,19 @@ def fused_se3() -> bool:
     return knob == "1"
 
 
+def fused_control() -> bool:
+    """Whether stage 2's glue around the control MLP -- mask rows, attribute means, control values, the scatter into the full
+    set -- runs on a cached plan of the mask through the ``ops.control_*`` calls in place of boolean indexing, a Python loop and
+    ``index_put``: ``FG_FUSED_CONTROL`` (opt-in; read here and nowhere else, on the host, on every call) -- unset or "0": the
+    torch ops; "1": the fused stage, with no host synchronisation per step (profiles/control_fused.md).  Anything else is a
+    ``ValueError``: a typo must not train silently on the other path.  The caller (model.fused_control_applies) adds its own
+    conditions: CUDA float32 tensors, no crop, 1 to 32 attributes, each with at least one row."""
+    knob = os.environ.get("FG_FUSED_CONTROL", "0")
+    if knob not in ("0", "1"):
+        raise ValueError(f"FG_FUSED_CONTROL wants 0 or 1, got {knob!r}")
+    return knob == "1"
+
+
 def fused_train_applies(module: nn.Module, x: torch.Tensor, other: torch.Tensor) -> bool:
     """Whether a taped ``module(x, other)`` runs as one ``ops.mlp_train`` call (``fused_train_mode``)."""
     return fused_train_mode(module, x, other) != ""

@@ -19,7 +19,7 @@ from typing import Dict, List, Optional, Union
 import torch
 from torch import nn
 
-from .deform import FreeGaussianControllableModel, FreeGaussianDeformableModel, fused_applies, fused_se3
+from .deform import FreeGaussianControllableModel, FreeGaussianDeformableModel, fused_applies, fused_control, fused_se3
 from .rasterization import num_sh_bases, rasterization
 from .utils import get_viewmat, knn_mean_distance, random_quat_tensor, resize_image, transform_points
 
@@ -147,6 +147,30 @@ def _se3_apply(w: torch.Tensor, v: torch.Tensor, pts: torch.Tensor) -> torch.Ten
     from . import ops
 
     return ops.se3_apply(w, v, pts)
+
+
+def fused_control_applies(means: torch.Tensor, gaussian_mask: torch.Tensor, crop: Optional[torch.Tensor], plan=None) -> bool:
+    """Whether stage 2's control stage runs through the ``ops.control_*`` calls: ``FG_FUSED_CONTROL=1``
+    (``deform.fused_control``), CUDA float32 means and a CUDA bool mask [N,M] of 1 <= M <= 32 attributes on one device, and no
+    active crop (a crop changes the rows on every call: the torch ops keep it).  With the mask's ``plan`` (``ops.control_plan``,
+    or a callable that returns it, called only once everything above holds) also: at least one row, and every attribute with
+    at least one (the reference's empty attribute is a NaN that poisons every value; the torch ops keep that behaviour)."""
+    if not fused_control() or crop is not None:
+        return False
+    if not (means.is_cuda and gaussian_mask.is_cuda and means.device == gaussian_mask.device and means.dtype == torch.float32):
+        return False
+    if gaussian_mask.dtype != torch.bool or gaussian_mask.dim() != 2 or gaussian_mask.shape[0] != means.shape[0]:
+        return False
+    if not 1 <= gaussian_mask.shape[1] <= 32:
+        return False
+    if plan is None:
+        return True
+    return (plan() if callable(plan) else plan).refusal() is None
+
+
+def _mask_key(mask: torch.Tensor):
+    """Changes whenever the mask does: another tensor, an in-place edit, another shape, another device."""
+    return (mask.data_ptr(), mask._version, tuple(mask.shape), mask.device)
 
 
 class FreeGaussianModel(nn.Module):
@@ -624,6 +648,40 @@ class FreeGaussianControlModel(FreeGaussianModel):
 
     def _get_outputs_on_active_rows(self, camera: Camera):
         viewmat, K, W, H = self._camera_setup(camera)
+        means, d_rotation, d_scaling = self._control_stage(camera)
+        return self._bilateral(self._render(means, d_rotation, d_scaling, viewmat, K, W, H), camera)  # (control model :190-193)
+
+    def _control_plan(self):
+        """``ops.control_plan`` of the mask, kept until the mask changes (``_mask_key``; the mask itself is kept with it, so
+        that its address is not handed to another tensor meanwhile).  An edit that does not raise the mask's ``_version`` -- through
+        ``mask.data``, or under ``torch.inference_mode`` -- is not seen: the plan stays that of the mask before it.  Assign a new
+        tensor after such an edit."""
+        from . import ops
+
+        mask = self.gaussian_mask
+        cached = self.__dict__.get("_control_plan_cache")
+        if cached is None or cached[0] != _mask_key(mask):
+            cached = (_mask_key(mask), ops.control_plan(mask), mask)
+            _plain_set(self, "_control_plan_cache", cached)
+        return cached[1]
+
+    def _frozen_deformed(self, pts: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
+        """(:128-138) the selected rows moved by the frozen deformation net at time ``t``."""
+        t = t.to(self.device).expand(pts.shape[0], -1)
+        if fused_applies(self.deform, pts, t):
+            return self.deform.deformed_points(pts, t)[0]
+        if _se3_fused_for(pts, t):
+            w, v, _, _ = self.deform.heads(pts, t)
+            return _se3_apply(w, v, pts)
+        T, _, _ = self.deform(pts, t)
+        return transform_points(T, pts)
+
+    def _control_stage(self, camera: Camera):
+        """From the mask's rows to ``(means, d_rotation, d_scaling)``, the three full-N arrays of the raster call."""
+        # (the plan is asked for only once the knob, the tensors and the crop allow the fused stage; it is kept, so the second
+        #  look below costs a key comparison)
+        if fused_control_applies(self.gauss_params["means"], self.gaussian_mask, self._active_crop, self._control_plan):
+            return self._control_stage_fused(camera, self._control_plan())
         gmask = self.gaussian_mask if self._active_crop is None else self.gaussian_mask[self._active_crop]
         all_means, all_scales, all_quats = self.means, self.scales, self.quats
         sel = gmask.any(-1)
@@ -633,17 +691,7 @@ class FreeGaussianControlModel(FreeGaussianModel):
             d_avg = self.control_values.to(self.device)
         else:
             with torch.no_grad():  # (:128-138)
-                def deformed(t):
-                    t = t.to(self.device).expand(pts.shape[0], -1)
-                    if fused_applies(self.deform, pts, t):
-                        return self.deform.deformed_points(pts, t)[0]
-                    if _se3_fused_for(pts, t):
-                        w, v, _, _ = self.deform.heads(pts, t)
-                        return _se3_apply(w, v, pts)
-                    T, _, _ = self.deform(pts, t)
-                    return transform_points(T, pts)
-
-                delta = deformed(camera.times) - deformed(self.init_camera.times)
+                delta = self._frozen_deformed(pts, camera.times) - self._frozen_deformed(pts, self.init_camera.times)
                 d_avg = torch.stack([delta[pmask[:, i]].mean(0) for i in range(pmask.shape[1])])
         value = pmask.float() @ d_avg / pmask.sum(-1, keepdim=True)  # (:140)
         d_xyz, d_rot, d_scale = self.control(pts, value)
@@ -651,7 +699,25 @@ class FreeGaussianControlModel(FreeGaussianModel):
         means = all_means + torch.zeros_like(all_means).index_put(idx, d_xyz)
         d_scaling = torch.zeros_like(all_scales).index_put(idx, d_scale)
         d_rotation = torch.zeros_like(all_quats).index_put(idx, d_rot)
-        return self._bilateral(self._render(means, d_rotation, d_scaling, viewmat, K, W, H), camera)  # (control model :190-193)
+        return means, d_rotation, d_scaling
+
+    def _control_stage_fused(self, camera: Camera, plan):
+        """``FG_FUSED_CONTROL=1``: the same stage on the mask's plan -- one ``index_select``, the two frozen-deform
+        evaluations as above, then four small calls (csrc/control.hip) around the control MLP.  No boolean indexing, no
+        ``nonzero``, no Python loop over the attributes: nothing is read back, so the host runs ahead of the GPU."""
+        from . import ops
+
+        all_means = self.means
+        pts = all_means.index_select(0, plan.sel_index64)
+        if not self.training and "cameras0" not in camera.metadata and self.control_values is not None:
+            d_avg = self.control_values.to(device=self.device, dtype=torch.float32)
+        else:
+            with torch.no_grad():
+                d_avg = ops.control_attr_mean(plan, self._frozen_deformed(pts, camera.times),
+                                              self._frozen_deformed(pts, self.init_camera.times))  # fmt: skip
+        value = ops.control_value_rows(plan, d_avg)
+        d_xyz, d_rot, d_scale = self.control(pts, value)
+        return ops.control_scatter(plan, all_means, d_xyz, d_rot, d_scale)
 
     def get_param_groups(self):
         groups = super().get_param_groups()

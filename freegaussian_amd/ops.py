@@ -1320,6 +1320,144 @@ def se3_apply(w: torch.Tensor, v: torch.Tensor, pts: torch.Tensor) -> torch.Tens
     return _Se3Apply.apply(_rows3(w), _rows3(v), pts.contiguous())
 
 
+class ControlPlan:
+    """What the stage-2 control stage needs of an [N,M] bool mask, as device tensors (``control_plan`` builds it once per
+    mask; include/fgraster.h, section CT): ``sel_index`` int32 [n] the rows with any attribute, ascending
+    (``sel_index64``: the same as int64, for ``index_select``); ``bits`` uint32 [n], bit m set where row ``sel_index[i]`` has
+    attribute m; ``rank`` int32 [N], a row's position in ``sel_index`` or -1; ``counts`` int32 [M] the rows per attribute,
+    and ``counts_host`` the same as Python ints."""
+
+    __slots__ = ("N", "M", "n", "sel_index", "sel_index64", "bits", "rank", "counts", "counts_host", "_counts_c")
+
+    def refusal(self) -> Optional[str]:
+        """Why the fused stage does not take this mask, or None: no row at all, or an attribute without one (its mean is
+        the reference's NaN, which the torch statement keeps)."""
+        if self.n < 1:
+            return "no row has an attribute"
+        empty = [m for m, c in enumerate(self.counts_host) if c < 1]
+        return f"attribute {empty[0]} has no row" if empty else None
+
+
+def control_plan(gaussian_mask: torch.Tensor) -> ControlPlan:
+    """The ``ControlPlan`` of a bool mask [N,M], 1 <= M <= 32, on the mask's device.  Torch ops, with read-backs (the row
+    count, the counts): the one place of the fused control stage that synchronises, once per mask."""
+    if gaussian_mask.dim() != 2 or gaussian_mask.dtype != torch.bool:
+        raise ValueError(f"a bool mask [N,M] expected, got {gaussian_mask.dtype} {tuple(gaussian_mask.shape)}")
+    N, M = gaussian_mask.shape
+    if not 1 <= M <= _lib.CONTROL_MAX_ATTRS or N >= 2**31:
+        raise ValueError(f"1 <= M <= {_lib.CONTROL_MAX_ATTRS} attributes and N < 2^31 rows expected, got {tuple(gaussian_mask.shape)}")
+    dev = gaussian_mask.device
+    plan = ControlPlan()
+    plan.N, plan.M = int(N), int(M)
+    plan.sel_index64 = gaussian_mask.any(-1).nonzero().squeeze(-1)
+    plan.n = int(plan.sel_index64.numel())
+    plan.sel_index = plan.sel_index64.to(torch.int32)
+    weights = torch.ones(M, dtype=torch.int64, device=dev) << torch.arange(M, dtype=torch.int64, device=dev)
+    words = (gaussian_mask.index_select(0, plan.sel_index64).to(torch.int64) * weights).sum(-1)
+    # (torch has no arithmetic on uint32: the words pass through the int32 of the same bits)
+    plan.bits = torch.where(words >= 2**31, words - 2**32, words).to(torch.int32).view(torch.uint32)
+    plan.rank = torch.full((N,), -1, dtype=torch.int32, device=dev)
+    plan.rank[plan.sel_index64] = torch.arange(plan.n, dtype=torch.int32, device=dev)
+    plan.counts = gaussian_mask.sum(0).to(torch.int32)
+    plan.counts_host = tuple(int(c) for c in plan.counts.tolist())
+    plan._counts_c = (ctypes.c_int32 * M)(*plan.counts_host)
+    return plan
+
+
+def _rows_of(t: torch.Tensor, width: int) -> torch.Tensor:
+    """``_rows3`` for rows of ``width`` floats."""
+    if t.stride(1) == 1 and (t.shape[0] <= 1 or t.stride(0) >= width):
+        return t
+    return t.contiguous()
+
+
+def _control_rows(name: str, plan: ControlPlan, rows: int, **tensors) -> None:
+    """The call checks the control ops share: [rows,width] float32 CUDA tensors on the plan's device."""
+    for key, (t, width) in tensors.items():
+        if t.dim() != 2 or tuple(t.shape) != (rows, width):
+            raise ValueError(f"{name}: {key} [{rows},{width}] expected, got {tuple(t.shape)}")
+        if not t.is_cuda:
+            raise _lib.FgRasterError(f"{name} runs on the GPU only ({key} is a CPU tensor; model.FreeGaussianControlModel holds "
+                                     "the torch statement of it)")  # fmt: skip
+        if t.dtype != torch.float32 or t.device != plan.rank.device:
+            raise ValueError(f"{name}: float32 tensors on the plan's device {plan.rank.device} expected, got {key}: {t.dtype} on {t.device}")
+
+
+def control_attr_mean(plan: ControlPlan, a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """``d_avg`` [M,3]: per attribute the mean of ``a - b`` over its rows (``a``, ``b`` [n,3]: the selected rows at two
+    times), what ``torch.stack([(a - b)[pmask[:, i]].mean(0) for i in range(M)])`` states.  The difference in fp32, the sum
+    in float64 in a fixed order, rounded once: two launches, no atomics, bit for bit reproducible.  ``a`` and ``b`` are
+    read in place where they are contiguous or columns of a wider block.  Not differentiable (the reference forms it under
+    ``no_grad``).  An attribute without a row is a ``ValueError``."""
+    _control_rows("control_attr_mean", plan, plan.n, a=(a, 3), b=(b, 3))
+    why = plan.refusal()
+    if why:
+        raise ValueError(f"control_attr_mean: {why}")
+    a, b = _rows_of(a.detach(), 3), _rows_of(b.detach(), 3)
+    nbytes = _lib.load().fg_control_workspace_bytes(plan.n, plan.M)
+    if nbytes <= 0:
+        raise ValueError(f"control_attr_mean: {plan.n} rows of {plan.M} attributes are outside what the library takes")
+    workspace = torch.empty(nbytes // 8, dtype=torch.float64, device=a.device)
+    d_avg = torch.empty(plan.M, 3, dtype=torch.float32, device=a.device)
+    _call("fg_control_attr_mean", plan.n, plan.M, _ptr(a), _row_stride(a), _ptr(b), _row_stride(b), _ptr(plan.bits),
+          ctypes.addressof(plan._counts_c), _ptr(workspace), nbytes, _ptr(d_avg), _stream(), stage="fg_control_attr_mean")  # fmt: skip
+    return d_avg
+
+
+def control_value_rows(plan: ControlPlan, d_avg: torch.Tensor) -> torch.Tensor:
+    """``value`` [n,3]: per selected row the mean of ``d_avg`` [M,3] over the row's attributes, what
+    ``pmask.float() @ d_avg / pmask.sum(-1, keepdim=True)`` states: the sum over the set bits in ascending order in fp32,
+    divided by their number.  One launch.  Not differentiable."""
+    _control_rows("control_value_rows", plan, plan.M, d_avg=(d_avg, 3))
+    d_avg = d_avg.detach().contiguous()
+    value = torch.empty(plan.n, 3, dtype=torch.float32, device=d_avg.device)
+    _call("fg_control_value_rows", plan.n, plan.M, _ptr(plan.bits), _ptr(d_avg), _ptr(value), _stream(), stage="fg_control_value_rows")
+    return value
+
+
+class _ControlScatter(torch.autograd.Function):
+    """The control MLP's three heads scattered into the full set (csrc/control.hip): saves nothing but the plan; the backward
+    gathers the gradients that are wanted, and the gradient of ``means`` is the upstream tensor itself."""
+
+    @staticmethod
+    def forward(ctx, plan, means, d_xyz, d_rot, d_scale):
+        out_means = torch.empty_like(means)
+        d_rotation, d_scaling = means.new_empty(plan.N, 4), means.new_empty(plan.N, 3)
+        _call("fg_control_scatter_fwd", plan.N, plan.n, _ptr(plan.rank), _ptr(means), _ptr(d_xyz), _row_stride(d_xyz), _ptr(d_rot),
+              d_rot.stride(0) if plan.n > 1 else 4, _ptr(d_scale), _row_stride(d_scale), _ptr(out_means), _ptr(d_rotation),
+              _ptr(d_scaling), _stream(), stage="fg_control_scatter_fwd")  # fmt: skip
+        ctx.plan = plan
+        ctx.set_materialize_grads(False)
+        return out_means, d_rotation, d_scaling
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_means, g_rotation, g_scaling):
+        plan = ctx.plan
+        _, want_means, *want = ctx.needs_input_grad
+        g_heads = [None, None, None]
+        if any(want):
+            ups = [None if g is None else _f32(g, "the upstream gradient") for g in (g_means, g_rotation, g_scaling)]
+            dev = plan.rank.device
+            g_heads = [torch.empty(plan.n, w, dtype=torch.float32, device=dev) if k else None for k, w in zip(want, (3, 4, 3))]
+            _call("fg_control_scatter_bwd", plan.n, plan.N, _ptr(plan.sel_index), _ptr(ups[0]), _ptr(ups[1]), _ptr(ups[2]),
+                  _ptr(g_heads[0]), 3, _ptr(g_heads[1]), 4, _ptr(g_heads[2]), 3, _stream(), stage="fg_control_scatter_bwd")  # fmt: skip
+        return (None, g_means if want_means else None, *g_heads)
+
+
+def control_scatter(plan: ControlPlan, means: torch.Tensor, d_xyz: torch.Tensor, d_rot: torch.Tensor, d_scale: torch.Tensor):
+    """``(means + full(d_xyz), full(d_rot), full(d_scale))`` with ``full(x) = zeros.index_put((sel_index,), x)``: the three
+    heads of the control MLP ([n,3], [n,4], [n,3]: contiguous, or columns of ``mlp_train``'s [n,10] block read in place)
+    scattered into the N rows, as one launch that writes every element, and one gather in the backward.  Differentiable
+    with respect to ``means`` and the heads; only the gradients that are wanted are formed, an output nothing flowed into
+    counts as zeros.  No host synchronisation, nothing allocated outside torch's allocator: capturable."""
+    _control_rows("control_scatter", plan, plan.N, means=(means, 3))
+    _control_rows("control_scatter", plan, plan.n, d_xyz=(d_xyz, 3), d_rot=(d_rot, 4), d_scale=(d_scale, 3))
+    if plan.n < 1:
+        raise ValueError("control_scatter: the plan selects no row")
+    return _ControlScatter.apply(plan, means.contiguous(), _rows_of(d_xyz, 3), _rows_of(d_rot, 4), _rows_of(d_scale, 3))
+
+
 def color_correct_supported(numel: int, num_iters, eps) -> bool:
     """Does ``color_correct`` take ``numel // 3`` pixels with these arguments?  The library's own range (its query says) and
     the header's 0 < eps < 0.5."""

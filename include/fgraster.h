@@ -54,7 +54,10 @@ typedef void* fg_stream_t;
  * without them has no fused bilateral-grid slice, and the host keeps its torch statement of it.  Likewise BY NAME:
  * fg_color_correct_workspace_bytes and fg_color_correct -- a library without them has no fused colour correction of the
  * metrics, and the host keeps its torch statement of it.  Likewise BY NAME: fg_se3_apply_fwd and fg_se3_apply_bwd -- a library
- * without them has no fused SE(3) transform of the means, and the host keeps its torch statement of it.) */
+ * without them has no fused SE(3) transform of the means, and the host keeps its torch statement of it.  Likewise BY NAME:
+ * fg_control_supported, fg_control_workspace_bytes, fg_control_attr_mean, fg_control_value_rows, fg_control_scatter_fwd and
+ * fg_control_scatter_bwd -- a library without them has no fused stage-2 control stage, and the host keeps its torch statement
+ * of it.) */
 #define FG_COUNT_OUT_WORDS 16 /* int64 words of a count_out block (fg_stbin_count, fg_step_io): ABI 9 */
 
 int fg_abi_version(void);
@@ -1165,6 +1168,59 @@ int fg_se3_apply_fwd(int64_t N, const float* w, int64_t w_stride, const float* v
 int fg_se3_apply_bwd(int64_t N, const float* w, int64_t w_stride, const float* v, int64_t v_stride, const float* pts,
                      const float* g_out, float* g_w, int64_t gw_stride, float* g_v, int64_t gv_stride, float* g_pts,
                      fg_stream_t stream);
+
+/* ---- CT the stage-2 control stage around the control MLP (found BY NAME, see FG_ABI_MINOR; csrc/control.hip;
+ * freegaussian_amd/model.py FreeGaussianControlModel holds the torch statement: boolean indexing, a loop of masked means, a
+ * [n,M] x [M,3] product and three zeros + index_put).  The calls work on a PLAN the host builds once per [N,M] bool mask
+ * (1 <= M <= FG_CONTROL_MAX_ATTRS; ops.control_plan), n = the rows with any attribute:
+ *   sel_index  int32 [n]   those rows, ascending              rank    int32 [N]  a row's position in sel_index, or -1
+ *   bits       uint32 [n]  bit m set: row sel_index[i] has attribute m           counts  int32 [M], HOST: rows per attribute
+ * All floating data fp32.  Strides are in floats and at least the row's width; rows of d_xyz / d_rot / d_scale (and of the
+ * g_d_* outputs) may be three contiguous arrays or columns 0..2, 3..6, 7..9 of the fused MLP's [n,10] head block, in place.
+ *   fg_control_supported(M)           1 where 1 <= M <= FG_CONTROL_MAX_ATTRS, else 0.  Host only.
+ *   fg_control_workspace_bytes(n, M)  bytes of fg_control_attr_mean's workspace (float64 partial sums, one set per
+ *                                     FG_CONTROL_BLOCK_ROWS rows); 0 for an M or an n (1 .. FG_CONTROL_MAX_ROWS) outside the
+ *                                     range.  Host only.
+ *   fg_control_attr_mean   d_avg[m] = (sum over the rows i with bit m of (a_i - b_i)) / counts[m],  d_avg [M,3].  The
+ *       difference is formed in fp32 (what the torch statement subtracts), the sum in float64, and the quotient is rounded to
+ *       fp32 once:  |d_avg - exact mean of the fp32 differences| <= 2^-24 |mean| + n 2^-53 mean|a_i - b_i|.  Two launches:
+ *       partial sums per workgroup over a row partition that depends on n alone, then one pass that adds them in block
+ *       order.  No atomics: two runs are bit for bit equal.  a, b: rows of 3 floats.  workspace: 8-byte aligned.  The second
+ *       pass is one workgroup in which a lane adds one output's partials one after the other: n / FG_CONTROL_BLOCK_ROWS
+ *       dependent float64 additions (about 1000 at a million rows, 16 384 at FG_CONTROL_MAX_ROWS, which is set with that
+ *       in mind).
+ *   fg_control_value_rows  value[i] = (sum of d_avg[m] over the set bits of bits[i], ascending m, in fp32) / popcount(bits[i]),
+ *       value [n,3] contiguous.  One launch.  (A row without a bit is 0 / 0, as in the torch statement; a plan has none.)
+ *   fg_control_scatter_fwd out_means [N,3] = means + (rank >= 0 ? d_xyz[rank] : 0),  d_rotation [N,4] (16-byte aligned) and
+ *       d_scaling [N,3] = the row of d_rot / d_scale, or zeros.  One launch; every element of the three outputs is written.
+ *   fg_control_scatter_bwd g_d_xyz[i] = g_means[sel_index[i]], g_d_rot[i] = g_rotation[...], g_d_scale[i] = g_scaling[...]: a
+ *       gather, one launch.  A null upstream gradient (g_means [N,3], g_rotation [N,4], g_scaling [N,3]) counts as zeros; a
+ *       null output is not wanted and not written (all null: nothing is launched).  The gradient of means is g_means itself.
+ *   Bits at or above M are ignored; a rank or a sel_index entry outside its range reads nothing (zeros).
+ *   Aliasing: an output must not overlap an input or the workspace, by the span from its first to its last float; the g_d_*
+ *   outputs may be columns of one row block (equal strides, column ranges that do not meet).
+ *   FG_ERR_INVALID_ARG: a null pointer other than those named nullable, a negative count, n > N, attr_mean with n < 1 or a
+ *   counts[m] outside 1 .. n (an attribute without a row has no mean: an error, not a NaN), a stride below the row's width, a
+ *   misaligned workspace or d_rotation, an overlap as above;  FG_ERR_UNSUPPORTED: M above FG_CONTROL_MAX_ATTRS, n or N above
+ *   FG_CONTROL_MAX_ROWS, a stride above FG_CONTROL_MAX_STRIDE;  FG_ERR_WORKSPACE: workspace_bytes below the query.  All
+ *   before any launch.  n == 0 (value_rows, scatter_bwd) and N == 0 (scatter_fwd) are FG_OK with no launch.  Row and byte
+ *   offsets are 64-bit.  Asynchronous (no host read anywhere), capturable in a graph, no state, no environment.
+ *   Measured (profiles/control_fused.md). */
+#define FG_CONTROL_MAX_ATTRS 32
+#define FG_CONTROL_BLOCK_ROWS 1024
+#define FG_CONTROL_MAX_ROWS ((int64_t)1 << 24)
+#define FG_CONTROL_MAX_STRIDE ((int64_t)1 << 16)
+int fg_control_supported(int M);
+size_t fg_control_workspace_bytes(int64_t n, int M);
+int fg_control_attr_mean(int64_t n, int M, const float* a, int64_t a_stride, const float* b, int64_t b_stride, const uint32_t* bits,
+                         const int32_t* counts, void* workspace, size_t workspace_bytes, float* d_avg, fg_stream_t stream);
+int fg_control_value_rows(int64_t n, int M, const uint32_t* bits, const float* d_avg, float* value, fg_stream_t stream);
+int fg_control_scatter_fwd(int64_t N, int64_t n, const int32_t* rank, const float* means, const float* d_xyz, int64_t xyz_stride,
+                           const float* d_rot, int64_t rot_stride, const float* d_scale, int64_t scale_stride, float* out_means,
+                           float* d_rotation, float* d_scaling, fg_stream_t stream);
+int fg_control_scatter_bwd(int64_t n, int64_t N, const int32_t* sel_index, const float* g_means, const float* g_rotation,
+                           const float* g_scaling, float* g_d_xyz, int64_t xyz_stride, float* g_d_rot, int64_t rot_stride,
+                           float* g_d_scale, int64_t scale_stride, fg_stream_t stream);
 
 #ifdef __cplusplus
 }
