@@ -29,6 +29,7 @@
 // ceil(c (S-1) / (n-1)) is the same map inverted, so the gather and the slice agree on every pixel by construction.
 #include <algorithm>
 
+#include "arg_check.h"
 #include "fg_common.h"
 
 namespace {
@@ -246,10 +247,7 @@ size_t slice_lds_bytes(int W, int GX, int GL) {
   return (size_t)nodes * GL * 12 * sizeof(float);
 }
 
-bool overlap(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return a && b && x < y + nb && y < x + na;
-}
+using fg_args::clash;
 
 }  // namespace
 
@@ -265,7 +263,7 @@ extern "C" int fg_bilagrid_slice_fwd(int H, int W, int GX, int GY, int GL, const
   if (H < 2 || W < 2 || !grid || !rgb || !out) return FG_ERR_INVALID_ARG;
   if (!grid_ok(GX, GY, GL) || H > MAX_IMAGE || W > MAX_IMAGE) return FG_ERR_UNSUPPORTED;
   const size_t image = (size_t)H * W * 3 * sizeof(float), table = (size_t)12 * GL * GY * GX * sizeof(float);
-  if (overlap(out, image, rgb, image) || overlap(out, image, grid, table)) return FG_ERR_INVALID_ARG;
+  if (clash({{out, image}}, {{rgb, image}, {grid, table}})) return FG_ERR_INVALID_ARG;
   const dim3 blocks((W + SEG - 1) / SEG, H);
   hipLaunchKernelGGL(slice_kernel<false>, blocks, dim3(SEG), slice_lds_bytes(W, GX, GL), fg_hip_stream(stream), H, W, GX, GY, GL,
                      grid, rgb, (const float*)nullptr, out);
@@ -279,16 +277,11 @@ extern "C" int fg_bilagrid_slice_bwd(int H, int W, int GX, int GY, int GL, const
   if (!grid_ok(GX, GY, GL) || H > MAX_IMAGE || W > MAX_IMAGE) return FG_ERR_UNSUPPORTED;
   const size_t image = (size_t)H * W * 3 * sizeof(float), table = (size_t)12 * GL * GY * GX * sizeof(float);
   const size_t need = fg_bilagrid_bwd_workspace_bytes(H, W, GX, GY, GL);
-  if (overlap(v_rgb, image, rgb, image) || overlap(v_rgb, image, v_out, image) || overlap(v_rgb, image, grid, table) ||
-      overlap(v_grid, table, grid, table) || overlap(v_grid, table, rgb, image) || overlap(v_grid, table, v_out, image) ||
-      overlap(v_grid, table, v_rgb, image))
-    return FG_ERR_INVALID_ARG;
+  if (clash({{v_rgb, image}, {v_grid, table}}, {{rgb, image}, {v_out, image}, {grid, table}})) return FG_ERR_INVALID_ARG;
   if (v_grid) {
-    if (!workspace || ((uintptr_t)workspace & 15)) return FG_ERR_INVALID_ARG;
+    if (!workspace || !fg_args::aligned(workspace, 16)) return FG_ERR_INVALID_ARG;
     if (workspace_bytes < need) return FG_ERR_WORKSPACE;
-    if (overlap(workspace, need, v_grid, table) || overlap(workspace, need, rgb, image) || overlap(workspace, need, v_out, image) ||
-        overlap(workspace, need, v_rgb, image) || overlap(workspace, need, grid, table))
-      return FG_ERR_INVALID_ARG;
+    if (clash({{workspace, need}}, {{v_grid, table}, {rgb, image}, {v_out, image}, {v_rgb, image}, {grid, table}})) return FG_ERR_INVALID_ARG;
   }
   if (!v_rgb && !v_grid) return FG_OK;  // nothing asked for
   hipStream_t s = fg_hip_stream(stream);

@@ -25,6 +25,7 @@
 // img and ref only.  num_iters + 1 streaming passes and num_iters solve launches, all asynchronous on the stream.
 #include <algorithm>
 
+#include "arg_check.h"
 #include "color_correct_solve.h"
 #include "fg_common.h"
 
@@ -180,10 +181,7 @@ apply_kernel(int64_t P, const float* __restrict__ img, int num_iters, const floa
   out[at] = x0, out[at + 1] = x1, out[at + 2] = x2;
 }
 
-bool overlap(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return a && b && x < y + nb && y < x + na;
-}
+using fg_args::clash;
 
 }  // namespace
 
@@ -200,17 +198,11 @@ extern "C" int fg_color_correct(int64_t P, const float* img, const float* ref, i
   if (!in_range(P, num_iters, eps)) return FG_ERR_UNSUPPORTED;
   const size_t image = (size_t)P * 3 * sizeof(float), need = fg_color_correct_workspace_bytes(P, num_iters);
   const size_t n_warps = (size_t)num_iters * 30 * sizeof(float), n_rank = (size_t)num_iters * 3 * sizeof(int32_t);
-  if (overlap(out, image, img, image) || overlap(out, image, ref, image)) return FG_ERR_INVALID_ARG;
-  if (!workspace || ((uintptr_t)workspace & 15)) return FG_ERR_INVALID_ARG;
+  if (clash({{out, image}}, {{img, image}, {ref, image}})) return FG_ERR_INVALID_ARG;
+  if (!workspace || !fg_args::aligned(workspace, 16)) return FG_ERR_INVALID_ARG;
   if (workspace_bytes < need) return FG_ERR_WORKSPACE;
-  if (overlap(workspace, need, out, image) || overlap(workspace, need, img, image) || overlap(workspace, need, ref, image))
-    return FG_ERR_INVALID_ARG;
-  for (const void* o : {(const void*)warps, (const void*)rank}) {
-    const size_t n = o == (const void*)warps ? n_warps : n_rank;
-    if (overlap(o, n, img, image) || overlap(o, n, ref, image) || overlap(o, n, out, image) || overlap(o, n, workspace, need))
-      return FG_ERR_INVALID_ARG;
-  }
-  if (overlap(warps, n_warps, rank, n_rank)) return FG_ERR_INVALID_ARG;
+  if (clash({{workspace, need}}, {{out, image}, {img, image}, {ref, image}})) return FG_ERR_INVALID_ARG;
+  if (clash({{warps, n_warps}, {rank, n_rank}}, {{img, image}, {ref, image}, {out, image}, {workspace, need}})) return FG_ERR_INVALID_ARG;
   const float lo = (float)eps, hi = (float)(1.0 - eps);
   hipStream_t s = fg_hip_stream(stream);
   char* ws = static_cast<char*>(workspace);

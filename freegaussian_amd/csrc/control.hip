@@ -16,6 +16,7 @@
 // three of them).  LDS: the 4 x 24 float64 of attr_mean's cross-wave sum and value_rows' copy of d_avg, nothing else.
 // Registers (attr_mean): a lane keeps its 4 rows' differences and bits and walks the attributes in groups of 8 -- 24 float64
 // accumulators at a time, not M x 3 = 96.
+#include "arg_check.h"
 #include "fg_common.h"
 
 namespace {
@@ -183,33 +184,7 @@ bool attrs_ok(int M) { return M >= 1 && M <= CT_MAX_M; }
 bool rows_ok(int64_t n) { return n >= 1 && n <= FG_CONTROL_MAX_ROWS; }
 int64_t partial_blocks(int64_t n) { return (n + CT_ROWS - 1) / CT_ROWS; }
 unsigned row_blocks(int64_t rows) { return (unsigned)((rows + CT_BLOCK - 1) / CT_BLOCK); }
-
-// bytes of `rows` rows of `width` floats, `stride` floats apart, from the first to the last float (rows >= 1)
-size_t span_bytes(int64_t rows, int64_t stride, int width) { return ((size_t)(rows - 1) * (size_t)stride + (size_t)width) * sizeof(float); }
-
-bool overlap(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return a && b && x < y + nb && y < x + na;
-}
-
-struct ct_rows {  // rows of `width` floats, `stride` floats apart, at p (null: absent)
-  const float* p;
-  int64_t stride;
-  int width;
-};
-
-bool stride_invalid(const ct_rows& r) { return r.p && r.stride < r.width; }
-bool stride_far(const ct_rows& r) { return r.p && r.stride > FG_CONTROL_MAX_STRIDE; }
-
-// two row sets that may be columns of one block (mlp_train's [n,10]): equal strides and column ranges that do not meet
-bool columns_apart(const ct_rows& a, const ct_rows& b) {
-  if (a.stride != b.stride) return false;
-  const ct_rows& lo = (uintptr_t)a.p <= (uintptr_t)b.p ? a : b;
-  const ct_rows& hi = (uintptr_t)a.p <= (uintptr_t)b.p ? b : a;
-  const uintptr_t apart = (uintptr_t)hi.p - (uintptr_t)lo.p;
-  return apart % sizeof(float) == 0 && apart >= (size_t)lo.width * sizeof(float) &&
-         apart + (size_t)hi.width * sizeof(float) <= (size_t)lo.stride * sizeof(float);
-}
+using namespace fg_args;  // (arg_check.h: the heads and their gradients may be columns of one block, mlp_train's [n,10])
 
 }  // namespace
 
@@ -231,14 +206,11 @@ extern "C" int fg_control_attr_mean(int64_t n, int M, const float* a, int64_t a_
     if (counts[m] < 1 || counts[m] > n) return FG_ERR_INVALID_ARG;  // (an attribute without a row has no mean)
     by_value.c[m] = counts[m];
   }
-  if (!workspace || (uintptr_t)workspace % sizeof(double) != 0) return FG_ERR_INVALID_ARG;
+  if (!workspace || !aligned(workspace, sizeof(double))) return FG_ERR_INVALID_ARG;
   const size_t need = fg_control_workspace_bytes(n, M);
   if (workspace_bytes < need) return FG_ERR_WORKSPACE;
-  const size_t out_bytes = (size_t)M * 3 * sizeof(float), bits_bytes = (size_t)n * sizeof(uint32_t);
-  const size_t na = span_bytes(n, a_stride, 3), nb = span_bytes(n, b_stride, 3);
-  if (overlap(d_avg, out_bytes, a, na) || overlap(d_avg, out_bytes, b, nb) || overlap(d_avg, out_bytes, bits, bits_bytes) ||
-      overlap(d_avg, out_bytes, workspace, need) || overlap(workspace, need, a, na) || overlap(workspace, need, b, nb) ||
-      overlap(workspace, need, bits, bits_bytes))
+  if (clash({{d_avg, (size_t)M * 3 * sizeof(float)}, {workspace, need}},
+            {{a, span_bytes(n, a_stride, 3)}, {b, span_bytes(n, b_stride, 3)}, {bits, (size_t)n * sizeof(uint32_t)}}))
     return FG_ERR_INVALID_ARG;
   hipStream_t s = fg_hip_stream(stream);
   const int64_t blocks = partial_blocks(n);
@@ -254,8 +226,7 @@ extern "C" int fg_control_value_rows(int64_t n, int M, const uint32_t* bits, con
   if (n < 0 || M < 1 || !bits || !d_avg || !value) return FG_ERR_INVALID_ARG;
   if (n == 0) return attrs_ok(M) ? FG_OK : FG_ERR_UNSUPPORTED;
   if (!attrs_ok(M) || !rows_ok(n)) return FG_ERR_UNSUPPORTED;
-  const size_t out_bytes = span_bytes(n, 3, 3);
-  if (overlap(value, out_bytes, bits, (size_t)n * sizeof(uint32_t)) || overlap(value, out_bytes, d_avg, (size_t)M * 3 * sizeof(float)))
+  if (clash({{value, span_bytes(n, 3, 3)}}, {{bits, (size_t)n * sizeof(uint32_t)}, {d_avg, (size_t)M * 3 * sizeof(float)}}))
     return FG_ERR_INVALID_ARG;
   hipLaunchKernelGGL(control_value_kernel, dim3(row_blocks(n)), dim3(CT_BLOCK), 0, fg_hip_stream(stream), n, M, bits, d_avg, value);
   FG_RETURN_IF_LAUNCH_FAILED();
@@ -265,27 +236,17 @@ extern "C" int fg_control_value_rows(int64_t n, int M, const uint32_t* bits, con
 extern "C" int fg_control_scatter_fwd(int64_t N, int64_t n, const int32_t* rank, const float* means, const float* d_xyz,
                                       int64_t xyz_stride, const float* d_rot, int64_t rot_stride, const float* d_scale,
                                       int64_t scale_stride, float* out_means, float* d_rotation, float* d_scaling, fg_stream_t stream) {
-  const ct_rows in[3] = {{d_xyz, xyz_stride, 3}, {d_rot, rot_stride, 4}, {d_scale, scale_stride, 3}};
+  const rows in[3] = {{d_xyz, xyz_stride, 3}, {d_rot, rot_stride, 4}, {d_scale, scale_stride, 3}};
   if (N < 0 || n < 0 || n > N || !rank || !means || !d_xyz || !d_rot || !d_scale || !out_means || !d_rotation || !d_scaling)
     return FG_ERR_INVALID_ARG;
-  for (const ct_rows& r : in)
-    if (stride_invalid(r)) return FG_ERR_INVALID_ARG;
-  if ((uintptr_t)d_rotation % sizeof(float4) != 0) return FG_ERR_INVALID_ARG;
+  if (stride_invalid(in) || !aligned(d_rotation, sizeof(float4))) return FG_ERR_INVALID_ARG;
   if (N == 0) return FG_OK;
-  if (!rows_ok(N)) return FG_ERR_UNSUPPORTED;
-  for (const ct_rows& r : in)
-    if (stride_far(r)) return FG_ERR_UNSUPPORTED;
-  float* const outs[3] = {out_means, d_rotation, d_scaling};
-  const size_t out_bytes[3] = {span_bytes(N, 3, 3), span_bytes(N, 4, 4), span_bytes(N, 3, 3)};
-  for (int i = 0; i < 3; ++i) {
-    if (overlap(outs[i], out_bytes[i], rank, (size_t)N * sizeof(int32_t)) || overlap(outs[i], out_bytes[i], means, span_bytes(N, 3, 3)))
-      return FG_ERR_INVALID_ARG;
-    if (n > 0)
-      for (const ct_rows& r : in)
-        if (overlap(outs[i], out_bytes[i], r.p, span_bytes(n, r.stride, r.width))) return FG_ERR_INVALID_ARG;
-    for (int j = i + 1; j < 3; ++j)
-      if (overlap(outs[i], out_bytes[i], outs[j], out_bytes[j])) return FG_ERR_INVALID_ARG;
-  }
+  if (!rows_ok(N) || stride_far(in, FG_CONTROL_MAX_STRIDE)) return FG_ERR_UNSUPPORTED;
+  // the outputs have N rows, the heads n: without a selected row no head is read
+  span ins[5] = {{rank, (size_t)N * sizeof(int32_t)}, {means, span_bytes(N, 3, 3)}, {nullptr, 0}, {nullptr, 0}, {nullptr, 0}};
+  if (n > 0)
+    for (int k = 0; k < 3; ++k) ins[2 + k] = rows_span(in[k], n);
+  if (clash({{out_means, 3, 3}, {d_rotation, 4, 4}, {d_scaling, 3, 3}}, N, ins)) return FG_ERR_INVALID_ARG;
   hipLaunchKernelGGL(control_scatter_fwd_kernel, dim3(row_blocks(N)), dim3(CT_BLOCK), 0, fg_hip_stream(stream), N, n, rank, means, d_xyz,
                      xyz_stride, d_rot, rot_stride, d_scale, scale_stride, out_means, d_rotation, d_scaling);
   FG_RETURN_IF_LAUNCH_FAILED();
@@ -295,26 +256,14 @@ extern "C" int fg_control_scatter_fwd(int64_t N, int64_t n, const int32_t* rank,
 extern "C" int fg_control_scatter_bwd(int64_t n, int64_t N, const int32_t* sel_index, const float* g_means, const float* g_rotation,
                                       const float* g_scaling, float* g_d_xyz, int64_t xyz_stride, float* g_d_rot, int64_t rot_stride,
                                       float* g_d_scale, int64_t scale_stride, fg_stream_t stream) {
-  const ct_rows out[3] = {{g_d_xyz, xyz_stride, 3}, {g_d_rot, rot_stride, 4}, {g_d_scale, scale_stride, 3}};
-  if (n < 0 || N < 0 || n > N || !sel_index) return FG_ERR_INVALID_ARG;
-  for (const ct_rows& r : out)
-    if (stride_invalid(r)) return FG_ERR_INVALID_ARG;
+  const rows out[3] = {{g_d_xyz, xyz_stride, 3}, {g_d_rot, rot_stride, 4}, {g_d_scale, scale_stride, 3}};
+  if (n < 0 || N < 0 || n > N || !sel_index || stride_invalid(out)) return FG_ERR_INVALID_ARG;
   if (n == 0) return FG_OK;
-  if (!rows_ok(N)) return FG_ERR_UNSUPPORTED;
-  for (const ct_rows& r : out)
-    if (stride_far(r)) return FG_ERR_UNSUPPORTED;
-  const float* const ins[3] = {g_means, g_rotation, g_scaling};
-  const size_t in_bytes[3] = {span_bytes(N, 3, 3), span_bytes(N, 4, 4), span_bytes(N, 3, 3)};
-  for (int i = 0; i < 3; ++i) {
-    if (!out[i].p) continue;
-    const size_t bytes = span_bytes(n, out[i].stride, out[i].width);
-    if (overlap(out[i].p, bytes, sel_index, (size_t)n * sizeof(int32_t))) return FG_ERR_INVALID_ARG;
-    for (int k = 0; k < 3; ++k)
-      if (overlap(out[i].p, bytes, ins[k], in_bytes[k])) return FG_ERR_INVALID_ARG;
-    for (int j = i + 1; j < 3; ++j)
-      if (out[j].p && overlap(out[i].p, bytes, out[j].p, span_bytes(n, out[j].stride, out[j].width)) && !columns_apart(out[i], out[j]))
-        return FG_ERR_INVALID_ARG;
-  }
+  if (!rows_ok(N) || stride_far(out, FG_CONTROL_MAX_STRIDE)) return FG_ERR_UNSUPPORTED;
+  // the outputs have n rows, the upstream gradients N
+  if (clash(out, n, {{sel_index, (size_t)n * sizeof(int32_t)}, {g_means, span_bytes(N, 3, 3)}, {g_rotation, span_bytes(N, 4, 4)},
+                     {g_scaling, span_bytes(N, 3, 3)}}))
+    return FG_ERR_INVALID_ARG;
   if (!g_d_xyz && !g_d_rot && !g_d_scale) return FG_OK;  // nothing asked for
   hipLaunchKernelGGL(control_scatter_bwd_kernel, dim3(row_blocks(n)), dim3(CT_BLOCK), 0, fg_hip_stream(stream), n, N, sel_index, g_means,
                      g_rotation, g_scaling, g_d_xyz, xyz_stride, g_d_rot, rot_stride, g_d_scale, scale_stride);

@@ -13,6 +13,7 @@
 // non-finite, as in the torch ops) stays in its own row, and two runs give the same bits.  A lane reads its row's three
 // floats with three dword loads: the 64 lanes of a wave cover 768 contiguous bytes between them (contiguous [N,3] inputs), so
 // every cache line fetched is used whole; w and v read in place from the [N,13] head block use 24 of each row's 52 bytes.
+#include "arg_check.h"
 #include "fg_common.h"
 #include "se3_math.h"
 
@@ -61,20 +62,11 @@ se3_bwd_kernel(int64_t N, const float* __restrict__ wp, int64_t w_stride, const 
   }
 }
 
-// bytes of N rows of 3 floats, `stride` floats apart, from the first to the last float read or written (N >= 1)
-size_t span_bytes(int64_t N, int64_t stride) { return ((size_t)(N - 1) * (size_t)stride + 3) * sizeof(float); }
-
-bool overlap(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return a && b && x < y + nb && y < x + na;
-}
+using namespace fg_args;
 
 // FG_SE3_MAX_ROWS / FG_SE3_MAX_STRIDE: 2^30 workgroups at the most, and every span far below 2^63 bytes
 constexpr int64_t SE3_MAX_ROWS = FG_SE3_MAX_ROWS;
 constexpr int64_t SE3_MAX_STRIDE = FG_SE3_MAX_STRIDE;
-
-bool strides_ok(int64_t a, int64_t b) { return a >= 3 && b >= 3; }
-bool strides_far(int64_t a, int64_t b) { return a > SE3_MAX_STRIDE || b > SE3_MAX_STRIDE; }
 
 template <bool W, bool V, bool X>
 void launch_bwd(int64_t N, const float* w, int64_t w_stride, const float* v, int64_t v_stride, const float* pts, const float* g_out,
@@ -88,12 +80,11 @@ void launch_bwd(int64_t N, const float* w, int64_t w_stride, const float* v, int
 
 extern "C" int fg_se3_apply_fwd(int64_t N, const float* w, int64_t w_stride, const float* v, int64_t v_stride, const float* pts,
                                 float* out, fg_stream_t stream) {
-  if (N < 0 || !w || !v || !pts || !out || !strides_ok(w_stride, v_stride)) return FG_ERR_INVALID_ARG;
+  const rows in[2] = {{w, w_stride, 3}, {v, v_stride, 3}};
+  if (N < 0 || !w || !v || !pts || !out || stride_invalid(in)) return FG_ERR_INVALID_ARG;
   if (N == 0) return FG_OK;
-  if (N > SE3_MAX_ROWS || strides_far(w_stride, v_stride)) return FG_ERR_UNSUPPORTED;
-  const size_t rows = span_bytes(N, 3);
-  if (overlap(out, rows, w, span_bytes(N, w_stride)) || overlap(out, rows, v, span_bytes(N, v_stride)) || overlap(out, rows, pts, rows))
-    return FG_ERR_INVALID_ARG;
+  if (N > SE3_MAX_ROWS || stride_far(in, SE3_MAX_STRIDE)) return FG_ERR_UNSUPPORTED;
+  if (clash({{out, 3, 3}}, N, {rows_span(in[0], N), rows_span(in[1], N), {pts, span_bytes(N, 3, 3)}})) return FG_ERR_INVALID_ARG;
   const unsigned blocks = (unsigned)((N + SE3_BLOCK - 1) / SE3_BLOCK);
   hipLaunchKernelGGL(se3_fwd_kernel, dim3(blocks), dim3(SE3_BLOCK), 0, fg_hip_stream(stream), N, w, w_stride, v, v_stride, pts, out);
   FG_RETURN_IF_LAUNCH_FAILED();
@@ -103,28 +94,14 @@ extern "C" int fg_se3_apply_fwd(int64_t N, const float* w, int64_t w_stride, con
 extern "C" int fg_se3_apply_bwd(int64_t N, const float* w, int64_t w_stride, const float* v, int64_t v_stride, const float* pts,
                                 const float* g_out, float* g_w, int64_t gw_stride, float* g_v, int64_t gv_stride, float* g_pts,
                                 fg_stream_t stream) {
-  if (N < 0 || !w || !v || !pts || !g_out || !strides_ok(w_stride, v_stride)) return FG_ERR_INVALID_ARG;
-  if ((g_w && !strides_ok(gw_stride, 3)) || (g_v && !strides_ok(gv_stride, 3))) return FG_ERR_INVALID_ARG;
+  const rows in[2] = {{w, w_stride, 3}, {v, v_stride, 3}};
+  const rows outs[3] = {{g_w, gw_stride, 3}, {g_v, gv_stride, 3}, {g_pts, 3, 3}};  // (a null output's stride is not looked at)
+  if (N < 0 || !w || !v || !pts || !g_out || stride_invalid(in) || stride_invalid(outs)) return FG_ERR_INVALID_ARG;
   if (N == 0) return FG_OK;
-  if (N > SE3_MAX_ROWS || strides_far(w_stride, v_stride) || strides_far(g_w ? gw_stride : 3, g_v ? gv_stride : 3)) return FG_ERR_UNSUPPORTED;
-  const size_t rows = span_bytes(N, 3), nw = span_bytes(N, w_stride), nv = span_bytes(N, v_stride);
-  const size_t ngw = g_w ? span_bytes(N, gw_stride) : 0, ngv = g_v ? span_bytes(N, gv_stride) : 0;
-  float* const outs[3] = {g_w, g_v, g_pts};
-  const size_t out_bytes[3] = {ngw, ngv, rows};
-  for (int i = 0; i < 3; ++i) {
-    if (overlap(outs[i], out_bytes[i], w, nw) || overlap(outs[i], out_bytes[i], v, nv) || overlap(outs[i], out_bytes[i], pts, rows) ||
-        overlap(outs[i], out_bytes[i], g_out, rows))
-      return FG_ERR_INVALID_ARG;
-    for (int j = i + 1; j < 3; ++j)
-      if (overlap(outs[i], out_bytes[i], outs[j], out_bytes[j])) {
-        // g_w and g_v may be columns of one row block (interleaved rows, as w and v are): their spans overlap, their floats
-        // do not, where both have the same stride and lie at least 3 floats and less than a row apart
-        const uintptr_t a = (uintptr_t)g_w, b = (uintptr_t)g_v, apart = a > b ? a - b : b - a;
-        const bool interleaved = i == 0 && j == 1 && gw_stride == gv_stride && apart % sizeof(float) == 0 &&
-                                 apart >= 3 * sizeof(float) && apart + 3 * sizeof(float) <= (size_t)gw_stride * sizeof(float);
-        if (!interleaved) return FG_ERR_INVALID_ARG;
-      }
-  }
+  if (N > SE3_MAX_ROWS || stride_far(in, SE3_MAX_STRIDE) || stride_far(outs, SE3_MAX_STRIDE)) return FG_ERR_UNSUPPORTED;
+  // g_w and g_v may be columns of one row block (interleaved rows, as w and v are)
+  const size_t rows3 = span_bytes(N, 3, 3);
+  if (clash(outs, N, {rows_span(in[0], N), rows_span(in[1], N), {pts, rows3}, {g_out, rows3}})) return FG_ERR_INVALID_ARG;
   if (!g_w && !g_v && !g_pts) return FG_OK;  // nothing asked for
   hipStream_t s = fg_hip_stream(stream);
 #define SE3_BWD(W, V, X) launch_bwd<W, V, X>(N, w, w_stride, v, v_stride, pts, g_out, g_w, gw_stride, g_v, gv_stride, g_pts, s)

@@ -1202,6 +1202,33 @@ def l1_ssim(pred: torch.Tensor, gt: torch.Tensor):
     return _L1Ssim.apply(_f32(pred, "pred"), _f32(gt.detach(), "gt"))
 
 
+def _gpu_float32(op: str, statement: str, device: Optional[torch.device], **tensors: torch.Tensor) -> None:
+    """The call check the fused ops share.  A CPU tensor is an ``FgRasterError``: there is no CPU path, and ``statement``
+    says where the torch statement of ``op`` is.  Then a dtype other than float32 or a device other than ``device`` is a
+    ``ValueError`` (``device`` None: the op converts its inputs itself, neither is looked at)."""
+    for key, t in tensors.items():
+        if not t.is_cuda:
+            raise _lib.FgRasterError(f"{op} runs on the GPU only ({key} is a CPU tensor; {statement})")
+    for key, t in tensors.items():
+        if device is not None and (t.dtype != torch.float32 or t.device != device):
+            raise ValueError(f"{op}: float32 tensors on {device} expected, got {key}: {t.dtype} on {t.device}")
+
+
+def _rows(t: torch.Tensor, width: int) -> torch.Tensor:
+    """An [N,width] float32 tensor whose rows are ``width`` consecutive floats a fixed number (>= ``width``) of floats apart,
+    as it is -- a contiguous one, or columns of a wider row block such as ``mlp_train``'s [N,13] heads; anything else: a
+    copy."""
+    if t.stride(1) == 1 and (t.shape[0] <= 1 or t.stride(0) >= width):
+        return t
+    return t.contiguous()
+
+
+def _row_stride(t: torch.Tensor, width: int) -> int:
+    """The floats between two rows of a ``_rows(t, width)``; where there is at most one row, its width (torch's stride of
+    such a dimension is arbitrary)."""
+    return t.stride(0) if t.shape[0] > 1 else width
+
+
 class _BilagridApply(torch.autograd.Function):
     """One camera's bilateral grid sliced at (x, y, luma) and applied to an [H,W,3] image (csrc/bilagrid.hip): saves its
     inputs only; the backward recomputes the per-pixel matrices and forms the gradients that are asked for."""
@@ -1247,8 +1274,7 @@ def bilagrid_apply(grids: torch.Tensor, cam_idx: int, rgb: torch.Tensor) -> torc
     atomics, so the gradient is bit for bit reproducible) backward.  Differentiable with respect to ``grids`` and ``rgb``."""
     if grids.dim() != 5 or grids.shape[1] != 12 or rgb.dim() != 3 or rgb.shape[-1] != 3:
         raise ValueError(f"grids [num,12,GL,GY,GX] and rgb [H,W,3] expected, got {tuple(grids.shape)} and {tuple(rgb.shape)}")
-    if not (grids.is_cuda and rgb.is_cuda):
-        raise _lib.FgRasterError("bilagrid_apply runs on the GPU only (bilagrid.apply_to_render is the torch statement of it)")
+    _gpu_float32("bilagrid_apply", "bilagrid.apply_to_render is the torch statement of it", None, grids=grids, rgb=rgb)
     cam_idx = int(cam_idx)
     if not 0 <= cam_idx < grids.shape[0]:
         raise ValueError(f"cam_idx {cam_idx} outside the {grids.shape[0]} grids")
@@ -1261,18 +1287,6 @@ def bilagrid_apply(grids: torch.Tensor, cam_idx: int, rgb: torch.Tensor) -> torc
     return _BilagridApply.apply(_f32(grids, "grids"), cam_idx, _f32(rgb, "rgb"))
 
 
-def _rows3(t: torch.Tensor) -> torch.Tensor:
-    """An [N,3] float32 tensor whose rows are 3 consecutive floats a fixed number (>= 3) of floats apart, as it is -- a
-    contiguous one, or three columns of a wider row block such as ``mlp_train``'s [N,13] heads; anything else: a copy."""
-    if t.stride(1) == 1 and (t.shape[0] <= 1 or t.stride(0) >= 3):
-        return t
-    return t.contiguous()
-
-
-def _row_stride(t: torch.Tensor) -> int:
-    return t.stride(0) if t.shape[0] > 1 else 3
-
-
 class _Se3Apply(torch.autograd.Function):
     """exp_se3 of the (w, v) heads applied to points (csrc/se3_apply.hip): saves its three inputs only (36 B a row); the
     backward recomputes the transform and forms the gradients that are asked for."""
@@ -1281,7 +1295,7 @@ class _Se3Apply(torch.autograd.Function):
     def forward(ctx, w, v, pts):
         N = pts.shape[0]
         out = torch.empty_like(pts)
-        _call("fg_se3_apply_fwd", N, _ptr(w), _row_stride(w), _ptr(v), _row_stride(v), _ptr(pts), _ptr(out), _stream(),
+        _call("fg_se3_apply_fwd", N, _ptr(w), _row_stride(w, 3), _ptr(v), _row_stride(v, 3), _ptr(pts), _ptr(out), _stream(),
               stage="fg_se3_apply_fwd")  # fmt: skip
         ctx.save_for_backward(w, v, pts)
         return out
@@ -1295,7 +1309,7 @@ class _Se3Apply(torch.autograd.Function):
             return None, None, None
         g_out = _f32(g_out, "g_out")
         g_w, g_v, g_pts = (torch.empty_like(pts) if k else None for k in want)
-        _call("fg_se3_apply_bwd", pts.shape[0], _ptr(w), _row_stride(w), _ptr(v), _row_stride(v), _ptr(pts), _ptr(g_out),
+        _call("fg_se3_apply_bwd", pts.shape[0], _ptr(w), _row_stride(w, 3), _ptr(v), _row_stride(v, 3), _ptr(pts), _ptr(g_out),
               _ptr(g_w), 3, _ptr(g_v), 3, _ptr(g_pts), _stream(), stage="fg_se3_apply_bwd")  # fmt: skip
         return g_w, g_v, g_pts
 
@@ -1310,14 +1324,10 @@ def se3_apply(w: torch.Tensor, v: torch.Tensor, pts: torch.Tensor) -> torch.Tens
     for name, t in (("w", w), ("v", v), ("pts", pts)):
         if t.dim() != 2 or t.shape[1] != 3 or t.shape[0] != pts.shape[0]:
             raise ValueError(f"w, v, pts [N,3] expected, got {tuple(w.shape)}, {tuple(v.shape)}, {tuple(pts.shape)}")
-        if not t.is_cuda:
-            raise _lib.FgRasterError(f"se3_apply runs on the GPU only ({name} is a CPU tensor; deform._se3 + utils.transform_points "
-                                     "is the torch statement of it)")  # fmt: skip
-        if t.dtype != torch.float32 or t.device != pts.device:
-            raise ValueError(f"float32 tensors on one device expected, got {name}: {t.dtype} on {t.device}")
+        _gpu_float32("se3_apply", "deform._se3 + utils.transform_points is the torch statement of it", pts.device, **{name: t})
     if pts.shape[0] == 0:  # (nothing to launch; the result still hangs on its inputs)
         return pts + (w + v) * 0.0
-    return _Se3Apply.apply(_rows3(w), _rows3(v), pts.contiguous())
+    return _Se3Apply.apply(_rows(w, 3), _rows(v, 3), pts.contiguous())
 
 
 class ControlPlan:
@@ -1364,23 +1374,12 @@ def control_plan(gaussian_mask: torch.Tensor) -> ControlPlan:
     return plan
 
 
-def _rows_of(t: torch.Tensor, width: int) -> torch.Tensor:
-    """``_rows3`` for rows of ``width`` floats."""
-    if t.stride(1) == 1 and (t.shape[0] <= 1 or t.stride(0) >= width):
-        return t
-    return t.contiguous()
-
-
 def _control_rows(name: str, plan: ControlPlan, rows: int, **tensors) -> None:
     """The call checks the control ops share: [rows,width] float32 CUDA tensors on the plan's device."""
     for key, (t, width) in tensors.items():
         if t.dim() != 2 or tuple(t.shape) != (rows, width):
             raise ValueError(f"{name}: {key} [{rows},{width}] expected, got {tuple(t.shape)}")
-        if not t.is_cuda:
-            raise _lib.FgRasterError(f"{name} runs on the GPU only ({key} is a CPU tensor; model.FreeGaussianControlModel holds "
-                                     "the torch statement of it)")  # fmt: skip
-        if t.dtype != torch.float32 or t.device != plan.rank.device:
-            raise ValueError(f"{name}: float32 tensors on the plan's device {plan.rank.device} expected, got {key}: {t.dtype} on {t.device}")
+        _gpu_float32(name, "model.FreeGaussianControlModel holds the torch statement of it", plan.rank.device, **{key: t})
 
 
 def control_attr_mean(plan: ControlPlan, a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
@@ -1393,13 +1392,13 @@ def control_attr_mean(plan: ControlPlan, a: torch.Tensor, b: torch.Tensor) -> to
     why = plan.refusal()
     if why:
         raise ValueError(f"control_attr_mean: {why}")
-    a, b = _rows_of(a.detach(), 3), _rows_of(b.detach(), 3)
+    a, b = _rows(a.detach(), 3), _rows(b.detach(), 3)
     nbytes = _lib.load().fg_control_workspace_bytes(plan.n, plan.M)
     if nbytes <= 0:
         raise ValueError(f"control_attr_mean: {plan.n} rows of {plan.M} attributes are outside what the library takes")
     workspace = torch.empty(nbytes // 8, dtype=torch.float64, device=a.device)
     d_avg = torch.empty(plan.M, 3, dtype=torch.float32, device=a.device)
-    _call("fg_control_attr_mean", plan.n, plan.M, _ptr(a), _row_stride(a), _ptr(b), _row_stride(b), _ptr(plan.bits),
+    _call("fg_control_attr_mean", plan.n, plan.M, _ptr(a), _row_stride(a, 3), _ptr(b), _row_stride(b, 3), _ptr(plan.bits),
           ctypes.addressof(plan._counts_c), _ptr(workspace), nbytes, _ptr(d_avg), _stream(), stage="fg_control_attr_mean")  # fmt: skip
     return d_avg
 
@@ -1423,8 +1422,8 @@ class _ControlScatter(torch.autograd.Function):
     def forward(ctx, plan, means, d_xyz, d_rot, d_scale):
         out_means = torch.empty_like(means)
         d_rotation, d_scaling = means.new_empty(plan.N, 4), means.new_empty(plan.N, 3)
-        _call("fg_control_scatter_fwd", plan.N, plan.n, _ptr(plan.rank), _ptr(means), _ptr(d_xyz), _row_stride(d_xyz), _ptr(d_rot),
-              d_rot.stride(0) if plan.n > 1 else 4, _ptr(d_scale), _row_stride(d_scale), _ptr(out_means), _ptr(d_rotation),
+        _call("fg_control_scatter_fwd", plan.N, plan.n, _ptr(plan.rank), _ptr(means), _ptr(d_xyz), _row_stride(d_xyz, 3), _ptr(d_rot),
+              _row_stride(d_rot, 4), _ptr(d_scale), _row_stride(d_scale, 3), _ptr(out_means), _ptr(d_rotation),
               _ptr(d_scaling), _stream(), stage="fg_control_scatter_fwd")  # fmt: skip
         ctx.plan = plan
         ctx.set_materialize_grads(False)
@@ -1455,7 +1454,7 @@ def control_scatter(plan: ControlPlan, means: torch.Tensor, d_xyz: torch.Tensor,
     _control_rows("control_scatter", plan, plan.n, d_xyz=(d_xyz, 3), d_rot=(d_rot, 4), d_scale=(d_scale, 3))
     if plan.n < 1:
         raise ValueError("control_scatter: the plan selects no row")
-    return _ControlScatter.apply(plan, means.contiguous(), _rows_of(d_xyz, 3), _rows_of(d_rot, 4), _rows_of(d_scale, 3))
+    return _ControlScatter.apply(plan, means.contiguous(), _rows(d_xyz, 3), _rows(d_rot, 4), _rows(d_scale, 3))
 
 
 def color_correct_supported(numel: int, num_iters, eps) -> bool:
@@ -1477,10 +1476,7 @@ def color_correct(img: torch.Tensor, ref: torch.Tensor, num_iters: int = 5, eps:
     (rank = the eigenvalues each fit kept; -1 where a weight is not finite -- the output then carries the NaN)."""
     if img.dim() < 1 or img.shape[-1] != 3 or img.shape != ref.shape or img.numel() == 0:
         raise ValueError(f"two [...,3] images of one shape expected, got {tuple(img.shape)} and {tuple(ref.shape)}")
-    if not (img.is_cuda and ref.is_cuda):
-        raise _lib.FgRasterError("color_correct runs on the GPU only (bilagrid.color_correct is the torch statement of it)")
-    if img.dtype != torch.float32 or ref.dtype != torch.float32 or img.device != ref.device:
-        raise ValueError(f"float32 tensors on one device expected, got {img.dtype} on {img.device} and {ref.dtype} on {ref.device}")
+    _gpu_float32("color_correct", "bilagrid.color_correct is the torch statement of it", img.device, img=img, ref=ref)
     if not color_correct_supported(img.numel(), num_iters, eps):
         raise ValueError(f"num_iters {num_iters!r} / eps {eps!r} / {img.numel() // 3} pixels outside what the fused colour correction takes "
                          f"(1 .. {_lib.COLOR_CORRECT_MAX_ITERS} iterations, 0 < eps < 0.5)")  # fmt: skip

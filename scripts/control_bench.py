@@ -13,52 +13,16 @@ synchronise), three times per side, the sides taking turns.  Both cameras' times
 the host is uploaded by a blocking copy on either path."""
 import json
 import os
-import re
-import subprocess
 import sys
-import time
 
 import torch
 
+from fused_bench_common import TIMED, WARM, alternate, cell, csrc, host_ms_per_step, kernel_resources, verdict
+
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-WARM, TIMED = 10, 50
 STAGE_SIZES = ((240_000, 0.05), (240_000, 0.25), (1_000_000, 0.05))
 KNOB = "FG_FUSED_CONTROL"
 M = 3
-
-
-def _q(ms):
-    s = sorted(ms)
-    return {"median": s[len(s) // 2], "p10": s[len(s) // 10], "p90": s[(9 * len(s)) // 10]}
-
-
-def _alternate(sides, warm=WARM, timed=TIMED):
-    """``sides``: {name: callable}; the callables alternate call by call -> {name: quantiles of ms between device events}."""
-    ms = {k: [] for k in sides}
-    for i in range(warm + timed):
-        for k, fn in sides.items():
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn()
-            b.record()
-            b.synchronize()
-            if i >= warm:
-                ms[k].append(a.elapsed_time(b))
-    return {k: _q(v) for k, v in ms.items()}
-
-
-def _host_ms_per_step(sides, steps=TIMED, rounds=3):
-    """Host wall time per call of ``steps`` calls in a row with nothing that waits for the GPU in between."""
-    out = {k: [] for k in sides}
-    for _ in range(rounds):
-        for k, fn in sides.items():
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(steps):
-                fn()
-            out[k].append((time.perf_counter() - t0) * 1e3 / steps)
-            torch.cuda.synchronize()
-    return out
 
 
 def _mask(n, fraction, seed=0):
@@ -118,7 +82,7 @@ def _stage(n, fraction):
             outs[k] = cm._control_stage(cam)
     worst = max(float((a - b).abs().max()) for a, b in zip(outs["fused"], outs["torch"]))
     res = {"N": n, "fraction": fraction, "n": int(cm.gaussian_mask.any(-1).sum()), "max_abs_difference": worst,
-           "fwd_bwd_ms": _alternate(sides), "host_ms_per_call": _host_ms_per_step(sides)}  # fmt: skip
+           "fwd_bwd_ms": alternate(sides), "host_ms_per_call": host_ms_per_step(sides)}  # fmt: skip
     _set(False)
     return res
 
@@ -140,7 +104,7 @@ def _train_step():
 
     sides = {"unset": lambda: step(False), "1": lambda: step(True)}
     res = {"N": n, "n": int(cm.gaussian_mask.any(-1).sum()), "width": W, "height": H, "optimizers": sorted(opts),
-           "gpu_ms": _alternate(sides), "host_ms_per_step": _host_ms_per_step(sides)}  # fmt: skip
+           "gpu_ms": alternate(sides), "host_ms_per_step": host_ms_per_step(sides)}  # fmt: skip
     _set(False)
     return res
 
@@ -156,38 +120,6 @@ def measure(out):
     res["train_step"] = _train_step()
     json.dump(res, open(os.path.join(out, "control_fused.json"), "w"), indent=1)
     print(json.dumps(res["train_step"]), flush=True)
-
-
-def _cell(q):
-    return f"{q['median']:.3f} ({q['p10']:.3f} .. {q['p90']:.3f})"
-
-
-def _verdict(a, b):
-    """a against b by the project's rule."""
-    if a["p90"] < b["p10"]:
-        return f"gain, {a['median'] / b['median']:.2f} x"
-    if b["p90"] < a["p10"]:
-        return f"loss, {a['median'] / b['median']:.2f} x"
-    return "no difference"
-
-
-def _resources():
-    src = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "freegaussian_amd", "csrc", "control.hip")
-    cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only",
-           "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", os.devnull]  # fmt: skip
-    text = subprocess.run(cmd, capture_output=True, text=True).stderr
-    rows, cur = [], None
-    for line in text.splitlines():
-        m = re.search(r"remark:\s+(Function Name|TotalSGPRs|VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\S+)", line)
-        if not m:
-            continue
-        if m.group(1) == "Function Name":
-            name = subprocess.run(["c++filt", m.group(2)], capture_output=True, text=True).stdout.strip() or m.group(2)
-            cur = {"kernel": re.sub(r"\(anonymous namespace\)::|\(.*$|^void ", "", name)}
-            rows.append(cur)
-        else:
-            cur[m.group(1).split(" ")[0]] = m.group(2)
-    return rows
 
 
 def render(out):
@@ -207,16 +139,16 @@ def render(out):
         f, t = s["fwd_bwd_ms"]["fused"], s["fwd_bwd_ms"]["torch"]
         ratios.append(f["median"] / t["median"])
         hf, ht = (", ".join(f"{v:.3f}" for v in s["host_ms_per_call"][k]) for k in ("fused", "torch"))
-        print(f"| {s['N']:,} | {s['n']:,} ({100 * s['fraction']:.0f} %) | {_cell(f)} | {_cell(t)} | {_verdict(f, t)} | {hf} | {ht} | {s['max_abs_difference']:.2e} |")
+        print(f"| {s['N']:,} | {s['n']:,} ({100 * s['fraction']:.0f} %) | {cell(f)} | {cell(t)} | {verdict(f, t)} | {hf} | {ht} | {s['max_abs_difference']:.2e} |")
     t = r["train_step"]
     print(f"\n## (b) One stage-2 `harness.train_step` at {t['N']:,} Gaussians, {t['width']} x {t['height']}, {t['n']:,} masked rows\n")
     print("| | knob unset | `FG_FUSED_CONTROL=1` | outcome |\n|---|---|---|---|")
-    print(f"| GPU ms per step, between events | {_cell(t['gpu_ms']['unset'])} | {_cell(t['gpu_ms']['1'])} | {_verdict(t['gpu_ms']['1'], t['gpu_ms']['unset'])} |")
+    print(f"| GPU ms per step, between events | {cell(t['gpu_ms']['unset'])} | {cell(t['gpu_ms']['1'])} | {verdict(t['gpu_ms']['1'], t['gpu_ms']['unset'])} |")
     hu, h1 = (", ".join(f"{v:.3f}" for v in t["host_ms_per_step"][k]) for k in ("unset", "1"))
     print(f"| host wall ms per step, no synchronisation inside (three rounds) | {hu} | {h1} | |")
     print("\n## (c) Resource usage (`-Rpass-analysis=kernel-resource-usage`, gfx950)\n")
     print("| kernel | SGPRs | VGPRs | scratch bytes / lane | occupancy, waves / SIMD | LDS bytes / workgroup |\n|---|---|---|---|---|---|")
-    for k in _resources():
+    for k in kernel_resources(csrc("control.hip")):
         print(f"| `{k['kernel']}` | {k['TotalSGPRs']} | {k['VGPRs']} | {k['ScratchSize']} | {k['Occupancy']} | {k['LDS']} |")
     met = all(x <= 0.8 for x in ratios)
     print(f"\n## The default-on rule\n\nFused over torch ops, medians of (a): {', '.join(f'{x:.2f}' for x in ratios)}.  The rule (<= 0.8 x at every "

@@ -9,37 +9,16 @@ Protocol: the two sides alternate call by call in one process, 10 warm-up and 50
 (p10 .. p90).  A gain = medians apart with p10 .. p90 not overlapping; default-on would need <= 0.8 x at every size."""
 import json
 import os
-import re
-import subprocess
 import sys
 
 import torch
 
+from fused_bench_common import TIMED, WARM, alternate, cell, csrc, kernel_resources, verdict
+
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-WARM, TIMED = 10, 50
 SIZES = (33_000, 240_000, 1_000_000)
 KNOB = "FG_FUSED_SE3"
 FWD_BYTES, BWD_BYTES = 36 + 12, 36 + 12 + 36  # per row: w, v, pts -> out;  w, v, pts, g_out -> g_w, g_v, g_pts
-
-
-def _q(ms):
-    s = sorted(ms)
-    return {"median": s[len(s) // 2], "p10": s[len(s) // 10], "p90": s[(9 * len(s)) // 10]}
-
-
-def _alternate(sides, warm=WARM, timed=TIMED):
-    """``sides``: {name: callable}; the callables alternate call by call -> {name: quantiles of ms}."""
-    ms = {k: [] for k in sides}
-    for i in range(warm + timed):
-        for k, fn in sides.items():
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn()
-            b.record()
-            b.synchronize()
-            if i >= warm:
-                ms[k].append(a.elapsed_time(b))
-    return {k: _q(v) for k, v in ms.items()}
 
 
 def _inputs(n):
@@ -65,7 +44,7 @@ def _op(n):
         fn(*leaves).backward(go)
 
     sides = {"fused": lambda: run(ops.se3_apply), "torch": lambda: run(lambda w, v, x: transform_points(D._se3(w, v), x))}
-    res = {"n": n, "fwd_bwd_ms": _alternate(sides)}
+    res = {"n": n, "fwd_bwd_ms": alternate(sides)}
     peak = {}
     for k, fn in sides.items():
         for t in leaves:
@@ -82,7 +61,7 @@ def _op(n):
     out, gw, gv, gx = (torch.empty(n, 3, device="cuda") for _ in range(4))
     p = lambda t: t.data_ptr()  # noqa: E731
     wd, vd, xd = (t.detach() for t in leaves)
-    kern = _alternate({
+    kern = alternate({
         "fwd": lambda: lib.fg_se3_apply_fwd(n, p(wd), 3, p(vd), 3, p(xd), p(out), s),
         "bwd": lambda: lib.fg_se3_apply_bwd(n, p(wd), 3, p(vd), 3, p(xd), p(go), p(gw), 3, p(gv), 3, p(gx), s),
     })
@@ -125,7 +104,7 @@ def _model_step():
     for precision in ("fp32", "bf16x3"):
         os.environ["FG_FUSED_MLP_PRECISION"] = os.environ["FG_FUSED_MLP_WGRAD_PRECISION"] = precision
         del calls[:]
-        res["settings"][precision] = _alternate({"unset": lambda: step(False), "1": lambda: step(True)}, warm=5, timed=30)
+        res["settings"][precision] = alternate({"unset": lambda: step(False), "1": lambda: step(True)}, warm=5, timed=30)
         assert len(calls) == 35, len(calls)
     os.environ.pop(KNOB, None)
     ops.se3_apply = real
@@ -137,38 +116,6 @@ def measure(out):
     res = {"device": torch.cuda.get_device_name(0), "op": [_op(n) for n in SIZES], "model": _model_step()}
     json.dump(res, open(os.path.join(out, "se3_apply.json"), "w"), indent=1)
     print(json.dumps(res), flush=True)
-
-
-def _cell(q):
-    return f"{q['median']:.3f} ({q['p10']:.3f} .. {q['p90']:.3f})"
-
-
-def _verdict(a, b):
-    """a against b by the project's rule."""
-    if a["p90"] < b["p10"]:
-        return f"gain, {a['median'] / b['median']:.2f} x"
-    if b["p90"] < a["p10"]:
-        return f"loss, {a['median'] / b['median']:.2f} x"
-    return "no difference"
-
-
-def _resources():
-    src = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "freegaussian_amd", "csrc", "se3_apply.hip")
-    cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only",
-           "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", os.devnull]  # fmt: skip
-    text = subprocess.run(cmd, capture_output=True, text=True).stderr
-    rows, cur = [], None
-    for line in text.splitlines():
-        m = re.search(r"remark:\s+(Function Name|TotalSGPRs|VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\S+)", line)
-        if not m:
-            continue
-        if m.group(1) == "Function Name":
-            name = subprocess.run(["c++filt", m.group(2)], capture_output=True, text=True).stdout.strip() or m.group(2)
-            cur = {"kernel": re.sub(r"\(anonymous namespace\)::|\(.*$|^void ", "", name)}
-            rows.append(cur)
-        else:
-            cur[m.group(1).split(" ")[0]] = m.group(2)
-    return rows
 
 
 def render(out):
@@ -183,13 +130,13 @@ def render(out):
     print("| rows | fused ms | torch ops ms | outcome |\n|---|---|---|---|")
     for o in r["op"]:
         f, t = o["fwd_bwd_ms"]["fused"], o["fwd_bwd_ms"]["torch"]
-        print(f"| {o['n']:,} | {_cell(f)} | {_cell(t)} | {_verdict(f, t)} |")
+        print(f"| {o['n']:,} | {cell(f)} | {cell(t)} | {verdict(f, t)} |")
     print("\n## (b) One model training step at 240 000 Gaussians, 960 x 540, behind `warm_up`\n")
     print("`FG_FUSED_MLP_TRAIN=1` and `FG_FUSED_MLP_WGRAD=1` as in `profiles/mlp_wgrad_split.md` (c); the column is "
           "`FG_FUSED_MLP_PRECISION` = `FG_FUSED_MLP_WGRAD_PRECISION`.\n")
     print("| MLP precision | knob unset ms | `FG_FUSED_SE3=1` ms | outcome |\n|---|---|---|---|")
     for k, v in r["model"]["settings"].items():
-        print(f"| {k} | {_cell(v['unset'])} | {_cell(v['1'])} | {_verdict(v['1'], v['unset'])} |")
+        print(f"| {k} | {cell(v['unset'])} | {cell(v['1'])} | {verdict(v['1'], v['unset'])} |")
     print("\n## (c) Peak allocated memory of one forward + backward of (a), above the inputs\n")
     print("| rows | fused MB | torch ops MB | bytes per row, fused | bytes per row, torch ops |\n|---|---|---|---|---|")
     for o in r["op"]:
@@ -201,11 +148,11 @@ def render(out):
     print("| rows | forward ms | forward GB/s | backward ms | backward GB/s |\n|---|---|---|---|---|")
     for o in r["op"]:
         k, g = o["kernel_ms"], o["kernel_GBps"]
-        print(f"| {o['n']:,} | {_cell(k['fwd'])} | {g['fwd']:.0f} | {_cell(k['bwd'])} | {g['bwd']:.0f} |")
+        print(f"| {o['n']:,} | {cell(k['fwd'])} | {g['fwd']:.0f} | {cell(k['bwd'])} | {g['bwd']:.0f} |")
     print("\n## (e) Resource usage (`-Rpass-analysis=kernel-resource-usage`, gfx950)\n")
     print("`se3_bwd_kernel<w, v, pts>`: one kernel per set of gradients asked for.\n")
     print("| kernel | SGPRs | VGPRs | scratch bytes / lane | occupancy, waves / SIMD | LDS bytes / workgroup |\n|---|---|---|---|---|---|")
-    for k in _resources():
+    for k in kernel_resources(csrc("se3_apply.hip")):
         print(f"| `{k['kernel']}` | {k['TotalSGPRs']} | {k['VGPRs']} | {k['ScratchSize']} | {k['Occupancy']} | {k['LDS']} |")
 
 
