@@ -150,6 +150,11 @@ SIGNATURES = {
     "fg_control_scatter_fwd": (c_int, [c_int64, c_int64, P, P, P, c_int64, P, c_int64, P, c_int64, P, P, P, P]),
     # (n, N, sel_index, g_means, g_rotation, g_scaling, g_d_xyz, xyz_stride, g_d_rot, rot_stride, g_d_scale, scale_stride, stream)
     "fg_control_scatter_bwd": (c_int, [c_int64, c_int64, P, P, P, P, P, c_int64, P, c_int64, P, c_int64, P]),
+    # loss and squared error straight from the raw batch image (csrc/target_loss.hip); the first pointer is a `const fg_target_desc*`
+    "fg_target_loss_supported": (c_int, [P]),
+    "fg_target_loss_workspace_floats": (c_size_t, [P]),
+    "fg_target_loss_fwd": (c_int, [P, P, P, P, c_size_t, P, P]),  # (target, pred, maps or null, workspace, floats, out[3], stream)
+    "fg_target_loss_bwd": (c_int, [P, P, P, P, P, P]),  # (target, pred, maps, v_out[2], v_pred, stream)
 }  # fmt: skip
 
 # test hooks, not declared in the public header
@@ -167,6 +172,7 @@ MLP_WGRAD_MAX_SLAB, MLP_WGRAD_MIN_SPLIT = 4096, 512  # FG_MLP_WGRAD_MAX_SLAB, FG
 MLP_TRAIN_BWD_CHUNK_SLABS = 16  # FG_MLP_TRAIN_BWD_CHUNK_SLABS
 COLOR_CORRECT_MAX_ITERS = 8  # FG_COLOR_CORRECT_MAX_ITERS
 CONTROL_MAX_ATTRS = 32  # FG_CONTROL_MAX_ATTRS
+TARGET_U8, TARGET_F32 = 0, 1  # FG_TARGET_U8, FG_TARGET_F32: fg_target_desc::src_dtype / mask_dtype
 
 
 def mlp_enc_width(aux_width: int) -> int:
@@ -257,6 +263,14 @@ class MlpGrads(ctypes.Structure):
     _fields_ = [("size", ctypes.c_int32), ("reserved", ctypes.c_int32), ("weight", ctypes.c_void_p * 8),
                 ("bias", ctypes.c_void_p * 8), ("head_weight", ctypes.c_void_p * MLP_MAX_HEADS),
                 ("head_bias", ctypes.c_void_p * MLP_MAX_HEADS)]  # fmt: skip
+
+
+class TargetDesc(ctypes.Structure):
+    """``fg_target_desc``: field order = the header's; device pointers as integers."""
+
+    _fields_ = [(n, ctypes.c_int32) for n in ("size", "src_dtype", "height", "width", "channels", "downscale", "mask_dtype",
+                                              "reserved")] + [
+        ("src", ctypes.c_void_p), ("mask", ctypes.c_void_p), ("background", ctypes.c_void_p)]  # fmt: skip
 
 
 def load() -> ctypes.CDLL:

@@ -6,13 +6,14 @@ inner loop end to end on MI355X; dataset I/O and densification stay with the cal
 from __future__ import annotations
 
 import math
+import os
 from typing import Dict, Optional
 
 import torch
 import torch.nn.functional as F
 
 from .method_config import STAGE1_OPTIMIZERS, OptimSpec
-from .model import Camera, FreeGaussianModel
+from .model import FUSED_TARGET_KEY, Camera, FreeGaussianModel
 
 
 def _gauss_window(size: int = 11, sigma: float = 1.5, device=None) -> torch.Tensor:
@@ -55,6 +56,47 @@ def main_loss(pred: torch.Tensor, gt: torch.Tensor, ssim_lambda: float = 0.2) ->
     """pred, gt: [H,W,3] in [0,1]."""
     l1, sim = l1_and_ssim(pred, gt)
     return (1 - ssim_lambda) * l1 + ssim_lambda * (1 - sim)
+
+
+def fused_target() -> bool:
+    """``FG_FUSED_TARGET`` (opt-in; read here and nowhere else, on the host, on every call): unset or ``0`` = the target of the
+    loss is built with torch ops (``get_gt_img``, ``composite_with_background``, the mask multiplies) as ever, ``1`` = where
+    ``fused_target_applies``, ``get_loss_dict`` and ``get_metrics_dict`` take loss and PSNR from the raw batch image in one
+    ``ops.target_loss`` call (csrc/target_loss.hip, profiles/target_loss_fused.md); anything else is an error, not a silent
+    default."""
+    knob = os.environ.get("FG_FUSED_TARGET", "0")
+    if knob not in ("0", "1"):
+        raise ValueError(f"FG_FUSED_TARGET wants 0 or 1, got {knob!r}")
+    return knob == "1"
+
+
+def target_shapes_supported(pred: torch.Tensor, image: torch.Tensor, mask: Optional[torch.Tensor], d: int) -> bool:
+    """The sizes and dtypes ``ops.target_loss`` takes, wherever the tensors lie: ``pred`` [H,W,3] float32, the raw ``image``
+    [H0,W0,3 or 4] uint8 or float32 and contiguous, the optional ``mask`` [H0,W0,1] or [H0,W0] bool / uint8 / float32 and
+    contiguous; ``d`` in 1, 2, 4, 8; ``pred`` at (H0 // d, W0 // d), at least 11 x 11."""
+    from .ops import TARGET_DOWNSCALES, TARGET_MASK_DTYPES
+
+    if d not in TARGET_DOWNSCALES or pred.dim() != 3 or pred.shape[-1] != 3 or pred.dtype != torch.float32:
+        return False
+    if image.dim() != 3 or image.shape[-1] not in (3, 4) or image.dtype not in (torch.uint8, torch.float32) or not image.is_contiguous():
+        return False
+    H0, W0, _ = image.shape
+    if tuple(pred.shape[:2]) != (H0 // d, W0 // d) or min(pred.shape[:2]) < 11 or max(H0, W0) > 32768:
+        return False
+    if mask is not None:
+        if mask.dtype not in TARGET_MASK_DTYPES or not mask.is_contiguous() or tuple(mask.shape) not in ((H0, W0, 1), (H0, W0)):
+            return False
+    return True
+
+
+def fused_target_applies(pred: torch.Tensor, image: torch.Tensor, mask: Optional[torch.Tensor], d: int) -> bool:
+    """Whether ``ops.target_loss`` takes this batch (the knob is ``fused_target``'s, not looked at here): ``pred``, ``image``
+    and the mask on one GPU, and ``target_shapes_supported``.  A host-resident batch image keeps the torch path: the fused
+    call reads the image where it lies."""
+    tensors = [t for t in (pred, image, mask) if t is not None]
+    if not all(t.is_cuda and t.device == pred.device for t in tensors):
+        return False
+    return target_shapes_supported(pred, image, mask, d)
 
 
 def build_optimizers(model: FreeGaussianModel, table: Optional[Dict[str, OptimSpec]] = None):
@@ -145,6 +187,10 @@ def train_step(model: FreeGaussianModel, opts, camera: Camera, gt_image: torch.T
     if metrics_every > 1 and step % metrics_every != 0:
         return {"gaussian_count": model.num_points}
     with torch.no_grad():
+        kept = out.get(FUSED_TARGET_KEY) if gt is None else None
+        if kept is not None and kept[0] is gt_image and kept[1] is mask:
+            # (FG_FUSED_TARGET=1: the loss call left the squared error of this very batch; no target is composited)
+            return {"loss": float(loss), "psnr": float(-10.0 * torch.log10(kept[4])), "gaussian_count": model.num_points}
         if gt is None:
             gt = model.composite_with_background(model.get_gt_img(gt_image), out["background"])
         return {"loss": float(loss), "psnr": float(psnr(out["rgb"], gt)), "gaussian_count": model.num_points}

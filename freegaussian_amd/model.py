@@ -114,6 +114,8 @@ class FreeGaussianModelConfig:
     fused_front_end: bool = True
 
 
+# where get_loss_dict / get_metrics_dict leave the fused target call's (image, mask, l1, ssim, mse) in the outputs dict
+FUSED_TARGET_KEY = "_fused_target"
 _EVAL_BACKGROUND = {"random": torch.tensor([0.1490, 0.1647, 0.2157]), "white": torch.ones(3), "black": torch.zeros(3)}
 
 _POSE_RING = None
@@ -316,8 +318,41 @@ class FreeGaussianModel(nn.Module):
             return alpha * image[..., :3] + (1 - alpha) * background
         return image
 
+    def _fused_target(self, outputs, batch):
+        """``FG_FUSED_TARGET=1`` (``harness.fused_target``) and a batch the fused call takes (``harness.fused_target_applies``):
+        (L1, SSIM, squared error) of ``outputs["rgb"]`` against the target that the raw batch image stands for, through one
+        ``ops.target_loss`` -- no target tensor is built.  Else None: the torch ops.  ``get_loss_dict`` and
+        ``get_metrics_dict`` share the call: whichever runs first leaves (image, mask, l1, ssim, mse) in ``outputs`` under
+        ``FUSED_TARGET_KEY``, and the other takes it where image and mask are the same objects (a call made without a tape is
+        not reused by one that needs the gradient)."""
+        from . import harness
+
+        if not harness.fused_target():
+            return None
+        image, mask, pred = batch["image"], batch.get("mask"), outputs["rgb"]
+        taped = pred.requires_grad and torch.is_grad_enabled()
+        kept = outputs.get(FUSED_TARGET_KEY)
+        if kept is not None and kept[0] is image and kept[1] is mask and (kept[2].requires_grad or not taped):
+            return kept[2:]
+        d = self._get_downscale_factor()
+        bg = outputs["background"]
+        if not harness.fused_target_applies(pred, image, mask, d):
+            return None
+        if image.shape[-1] == 4 and not (bg.is_cuda and bg.device == pred.device and bg.dtype == torch.float32 and bg.numel() == 3):
+            return None
+        from . import ops
+
+        vals = ops.target_loss(pred, image, bg if image.shape[-1] == 4 else None, mask, d)
+        outputs[FUSED_TARGET_KEY] = (image, mask) + tuple(vals)
+        return vals
+
     def get_metrics_dict(self, outputs, batch):
-        """(:924-941) without the colour-corrected variant and the camera optimizer (mode "off", :120)."""
+        """(:924-941) without the colour-corrected variant and the camera optimizer (mode "off", :120).  With
+        ``FG_FUSED_TARGET=1`` and no colour-corrected metrics the squared error is ``_fused_target``'s (the colour-corrected
+        pair needs the target as a tensor and keeps the torch statement)."""
+        fused = None if self.config.color_corrected_metrics else self._fused_target(outputs, batch)
+        if fused is not None:
+            return {"psnr": -10.0 * torch.log10(fused[2]), "gaussian_count": self.num_points}
         gt_rgb = self.composite_with_background(self.get_gt_img(batch["image"]), outputs["background"])
         mse = torch.nn.functional.mse_loss(outputs["rgb"], gt_rgb)
         metrics = {"psnr": -10.0 * torch.log10(mse)}
@@ -358,25 +393,33 @@ class FreeGaussianModel(nn.Module):
         """(:944-990) main loss (1 - ssim_lambda) L1 + ssim_lambda (1 - SSIM) on the composited ground truth, the
         optional mask (both images blacked out), the optional scale-ratio regulariser on every 10th step, and while
         training with bilateral grids 10 x their total variation (:988-989).  The camera-optimizer term of the reference
-        is not mirrored (mode "off" in every shipped config)."""
+        is not mirrored (mode "off" in every shipped config).  With ``FG_FUSED_TARGET=1`` and a batch
+        the fused call takes, L1 and SSIM come from ``_fused_target`` and no target is built; the regulariser and the TV term
+        are the same either way."""
         from .harness import l1_and_ssim
 
-        gt_img = self.composite_with_background(self.get_gt_img(batch["image"]), outputs["background"])
-        pred_img = outputs["rgb"]
-        if "mask" in batch:
-            d = self._get_downscale_factor()
-            mask = batch["mask"]
-            mask = (resize_image(mask.float(), d) if d > 1 else mask.float()).to(self.device)
-            assert mask.shape[:2] == gt_img.shape[:2] == pred_img.shape[:2]
-            gt_img = gt_img * mask
-            pred_img = pred_img * mask
-        l1, sim = l1_and_ssim(pred_img, gt_img)  # (fused on the GPU: ops.l1_ssim)
+        fused = self._fused_target(outputs, batch)  # (FG_FUSED_TARGET=1: the target is never built)
+        if fused is not None:
+            l1, sim = fused[0], fused[1]
+        else:
+            gt_img = self.composite_with_background(self.get_gt_img(batch["image"]), outputs["background"])
+            pred_img = outputs["rgb"]
+            if "mask" in batch:
+                d = self._get_downscale_factor()
+                mask = batch["mask"]
+                mask = (resize_image(mask.float(), d) if d > 1 else mask.float()).to(self.device)
+                assert mask.shape[:2] == gt_img.shape[:2] == pred_img.shape[:2]
+                gt_img = gt_img * mask
+                pred_img = pred_img * mask
+            l1, sim = l1_and_ssim(pred_img, gt_img)  # (fused on the GPU: ops.l1_ssim)
         simloss = 1 - sim
         if self.config.use_scale_regularization and self.step % 10 == 0:
             scale_exp = torch.exp(self.scales)
             ratio = scale_exp.amax(dim=-1) / scale_exp.amin(dim=-1)
             limit = torch.tensor(self.config.max_gauss_ratio, device=ratio.device)
             scale_reg = 0.1 * (torch.maximum(ratio, limit) - self.config.max_gauss_ratio).mean()
+        elif fused is not None:
+            scale_reg = torch.zeros((), device=self.device)  # (a fill, not a host-to-device copy: the fused path never waits for the host)
         else:
             scale_reg = torch.tensor(0.0, device=self.device)
         lam = self.config.ssim_lambda

@@ -1214,6 +1214,108 @@ def _gpu_float32(op: str, statement: str, device: Optional[torch.device], **tens
             raise ValueError(f"{op}: float32 tensors on {device} expected, got {key}: {t.dtype} on {t.device}")
 
 
+TARGET_DOWNSCALES = (1, 2, 4, 8)  # what fg_target_loss_supported takes
+TARGET_MASK_DTYPES = (torch.bool, torch.uint8, torch.float32)
+
+
+def _target_desc(image: torch.Tensor, background: Optional[torch.Tensor], mask: Optional[torch.Tensor], d: int) -> "_lib.TargetDesc":
+    """``fg_target_desc`` of the batch tensors (which the caller keeps alive: the struct holds addresses only)."""
+    t = _lib.TargetDesc()
+    t.size = ctypes.sizeof(t)
+    t.src_dtype = _lib.TARGET_F32 if image.dtype == torch.float32 else _lib.TARGET_U8
+    t.height, t.width, t.channels = image.shape
+    t.downscale = d
+    t.src = _ptr(image)
+    if mask is not None:
+        t.mask_dtype = _lib.TARGET_F32 if mask.dtype == torch.float32 else _lib.TARGET_U8
+        t.mask = _ptr(mask)
+    if background is not None:
+        t.background = _ptr(background)
+    return t
+
+
+class _TargetLoss(torch.autograd.Function):
+    """mean |gt m - pred m|, mean SSIM and the unmasked mean squared error of ``pred`` against the target that the raw batch
+    image stands for (csrc/target_loss.hip): saves references to its inputs and the three derivative maps, no target."""
+
+    @staticmethod
+    def forward(ctx, pred, image, background, mask, d, want):
+        H, W, _ = pred.shape
+        dev = pred.device
+        desc = _target_desc(image, background, mask, d)
+        n_ws = int(_lib.load().fg_target_loss_workspace_floats(ctypes.addressof(desc)))
+        if n_ws == 0:
+            raise ValueError(f"target_loss: a {tuple(image.shape)} image at downscale {d} is outside what the fused target takes")
+        # (want: pred's gradient can be asked for -- the three maps are kept for it; else the values alone)
+        maps = torch.empty(3, 3, H - 10, W - 10, dtype=torch.float32, device=dev) if want else None
+        ws = torch.empty(n_ws, dtype=torch.float32, device=dev)
+        out = torch.empty(3, dtype=torch.float32, device=dev)
+        _call("fg_target_loss_fwd", ctypes.addressof(desc), _ptr(pred), _ptr(maps), _ptr(ws), n_ws, _ptr(out), _stream(),
+              stage="fg_target_loss_fwd")  # fmt: skip
+        if want:
+            ctx.save_for_backward(pred, image, background, mask, maps)
+            ctx.d = d
+        l1, ssim, mse = out[0], out[1], out[2]
+        ctx.mark_non_differentiable(mse)
+        return l1, ssim, mse
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, v_l1, v_ssim, _v_mse):
+        pred, image, background, mask, maps = ctx.saved_tensors
+        zero = pred.new_zeros(())
+        v = torch.stack([zero if v_l1 is None else v_l1.float().reshape(()), zero if v_ssim is None else v_ssim.float().reshape(())])
+        v_pred = torch.empty_like(pred)
+        desc = _target_desc(image, background, mask, ctx.d)
+        _call("fg_target_loss_bwd", ctypes.addressof(desc), _ptr(pred), _ptr(maps), _ptr(v), _ptr(v_pred), _stream(),
+              stage="fg_target_loss_bwd")  # fmt: skip
+        return v_pred, None, None, None, None, None
+
+
+def target_loss(pred: torch.Tensor, image: torch.Tensor, background: Optional[torch.Tensor] = None,
+                mask: Optional[torch.Tensor] = None, downscale: int = 1):
+    """(mean |gt m - pred m|, mean SSIM(pred m, gt m), mean (pred - gt)^2) of the render ``pred`` [H,W,3] against the target
+    that the raw batch ``image`` [H0,W0,3 or 4] (uint8: v / 255; float32) stands for: box-downscaled by ``downscale`` (1, 2, 4
+    or 8; H = H0 // downscale, W = W0 // downscale), composited -- 4 channels, after the downscale -- over ``background`` [3],
+    and with ``mask`` ([H0,W0,1] or [H0,W0]; bool, uint8 or float32; box-downscaled too) multiplied into both images of the
+    first two values.  What ``model.get_gt_img`` + ``composite_with_background`` + the mask lines of ``get_loss_dict`` +
+    ``l1_ssim`` + ``mse_loss`` state in torch ops, with no target tensor: one kernel and a fixed-order reduction forward
+    (bit for bit reproducible), one kernel backward.  Differentiable with respect to ``pred`` only; the third value carries no
+    gradient.  include/fgraster.h (TL) has the contract."""
+    if pred.dim() != 3 or pred.shape[-1] != 3 or pred.dtype != torch.float32:
+        raise ValueError(f"target_loss: pred [H,W,3] float32 expected, got {tuple(pred.shape)} {pred.dtype}")
+    if image.dim() != 3 or image.shape[-1] not in (3, 4) or image.dtype not in (torch.uint8, torch.float32):
+        raise ValueError(f"target_loss: image [H0,W0,3 or 4] uint8 or float32 expected, got {tuple(image.shape)} {image.dtype}")
+    if not image.is_contiguous():
+        raise ValueError("target_loss: the image is read in place: a contiguous tensor expected")
+    d = int(downscale)
+    if d not in TARGET_DOWNSCALES:
+        raise ValueError(f"target_loss: downscale 1, 2, 4 or 8 expected, got {downscale}")
+    H0, W0, ch = image.shape
+    if tuple(pred.shape[:2]) != (H0 // d, W0 // d):
+        raise ValueError(f"target_loss: pred is {tuple(pred.shape[:2])}, the image at downscale {d} is {(H0 // d, W0 // d)}")
+    if pred.shape[0] < 11 or pred.shape[1] < 11:
+        raise ValueError(f"SSIM needs images larger than its 11 x 11 window, got {pred.shape[0]} x {pred.shape[1]}")
+    if ch == 4:
+        if background is None or background.dtype != torch.float32 or background.numel() != 3:
+            raise ValueError("target_loss: a 4-channel image is composited over a background of 3 float32 values")
+        background = background.detach().reshape(3).contiguous()
+    else:
+        background = None
+    if mask is not None:
+        if mask.dtype not in TARGET_MASK_DTYPES or tuple(mask.shape) not in ((H0, W0, 1), (H0, W0)) or not mask.is_contiguous():
+            raise ValueError(f"target_loss: mask [H0,W0,1] or [H0,W0], contiguous, bool / uint8 / float32 expected, got "
+                             f"{tuple(mask.shape)} {mask.dtype}")  # fmt: skip
+        mask = mask.detach()
+    statement = "model.get_gt_img + composite_with_background + harness.l1_and_ssim is the torch statement of it"
+    _gpu_float32("target_loss", statement, None, **{k: t for k, t in dict(pred=pred, image=image, background=background, mask=mask).items()
+                                                    if t is not None})  # fmt: skip
+    devices = {t.device for t in (pred, image, background, mask) if t is not None}
+    if len(devices) != 1:
+        raise ValueError(f"target_loss: tensors on one device expected, got {sorted(map(str, devices))}")
+    return _TargetLoss.apply(pred.contiguous(), image.detach(), background, mask, d, pred.requires_grad and torch.is_grad_enabled())
+
+
 def _rows(t: torch.Tensor, width: int) -> torch.Tensor:
     """An [N,width] float32 tensor whose rows are ``width`` consecutive floats a fixed number (>= ``width``) of floats apart,
     as it is -- a contiguous one, or columns of a wider row block such as ``mlp_train``'s [N,13] heads; anything else: a

@@ -57,7 +57,8 @@ typedef void* fg_stream_t;
  * without them has no fused SE(3) transform of the means, and the host keeps its torch statement of it.  Likewise BY NAME:
  * fg_control_supported, fg_control_workspace_bytes, fg_control_attr_mean, fg_control_value_rows, fg_control_scatter_fwd and
  * fg_control_scatter_bwd -- a library without them has no fused stage-2 control stage, and the host keeps its torch statement
- * of it.) */
+ * of it.  Likewise BY NAME: fg_target_loss_supported, fg_target_loss_workspace_floats, fg_target_loss_fwd and
+ * fg_target_loss_bwd -- a library without them has no fused training target, and the host keeps its torch statement of it.) */
 #define FG_COUNT_OUT_WORDS 16 /* int64 words of a count_out block (fg_stbin_count, fg_step_io): ABI 9 */
 
 int fg_abi_version(void);
@@ -1221,6 +1222,58 @@ int fg_control_scatter_fwd(int64_t N, int64_t n, const int32_t* rank, const floa
 int fg_control_scatter_bwd(int64_t n, int64_t N, const int32_t* sel_index, const float* g_means, const float* g_rotation,
                            const float* g_scaling, float* g_d_xyz, int64_t xyz_stride, float* g_d_rot, int64_t rot_stride,
                            float* g_d_scale, int64_t scale_stride, fg_stream_t stream);
+
+/* ---- TL the training loss and the PSNR's squared error straight from the RAW batch image (found BY NAME, see FG_ABI_MINOR;
+ * csrc/target_loss.hip): the target of fg_l1_ssim_fwd -- the batch image as floats, box-downscaled, composited over the
+ * step's background, masked (freegaussian_amd/model.py get_gt_img, composite_with_background and the mask lines of
+ * get_loss_dict are the torch statement) -- is formed per pixel inside the loss kernels.  No target tensor is written.
+ *
+ *   The source is [height, width, channels] contiguous, uint8 or float32, channels 3 or 4; the output (= pred) is
+ *   [H, W, 3] float32 contiguous with H = height / downscale, W = width / downscale (integer division).
+ *   Per output pixel (y, x), channel c, d = downscale:
+ *     s_k   source channel k as a real number: a uint8 v is v / 255, a float32 is taken as it is
+ *     t_k   = mean of s_k over the d x d source block at (y d, x d), for every source channel, alpha included; source rows
+ *             and columns at or beyond H d, W d are never read (as a strided pooling ignores them); the sum is exact (uint8: an
+ *             integer; float32: in double) and the mean rounded once, so a flat block gives its own value back
+ *     gt_c  = t_c with 3 channels;  t_3 t_c + (1 - t_3) background[c] with 4: the composite comes AFTER the downscale, on
+ *             values that are not premultiplied.  background: 3 device floats
+ *     m     = the same box mean of the mask ([height, width] bytes -- a bool's 0 / 1, a uint8 by its value -- or float32);
+ *             1 without a mask
+ *   fg_target_loss_fwd:  out[0] = mean |gt m - pred m|, out[1] = mean SSIM(pred m, gt m) with the window, borders and
+ *     constants of fg_l1_ssim_fwd, out[2] = mean (pred - gt)^2 of the UNMASKED images (the PSNR's).  maps[3, 3, H-10, W-10]
+ *     are fg_l1_ssim_fwd's; a null maps keeps none (a forward whose pred needs no gradient).  The per-workgroup partial sums
+ *     (workspace[fg_target_loss_workspace_floats(target)] floats, 16-byte aligned) are reduced in a fixed order by a second
+ *     launch: no atomics, two runs are bit for bit equal.
+ *   fg_target_loss_bwd:  v_out[2] (device) = dL/d out[0], dL/d out[1]  ->  v_pred[H, W, 3] = m (v_out[0] L1 term + v_out[1]
+ *     SSIM term), overwritten; target pixel and mask are recomputed from the source.  Exactly 0 where m = 0.  out[2] carries no
+ *     gradient; the source, the mask and the background get none.
+ *   Supported (fg_target_loss_supported = 1, else 0; the query gives 0 floats): downscale 1, 2, 4 or 8; channels 3 or 4;
+ *     src_dtype and -- with a mask -- mask_dtype FG_TARGET_U8 or FG_TARGET_F32; height, width <= 32768; H, W >= 11.
+ *   FG_ERR_INVALID_ARG: a null descriptor or one whose size is not sizeof(fg_target_desc), height or width <= 0, a null src /
+ *   pred / workspace / out (fwd) or pred / maps / v_out / v_pred (bwd), a null background with 4 channels, a source that is not
+ *   aligned to its pixel (4-channel: 4 bytes uint8, 16 bytes float32; 3-channel float32: 4 bytes), a misaligned float mask,
+ *   background or workspace, an output (maps, workspace, out; v_pred) that overlaps an input or another output;
+ *   FG_ERR_UNSUPPORTED: anything outside the supported range;  FG_ERR_WORKSPACE: workspace_floats below the query.  All before
+ *   any launch.  Asynchronous, capturable in a graph, no state, no environment.  Measured (profiles/target_loss_fused.md). */
+#define FG_TARGET_U8 0
+#define FG_TARGET_F32 1
+typedef struct fg_target_desc {
+  int32_t size;       /* sizeof(fg_target_desc) */
+  int32_t src_dtype;  /* FG_TARGET_U8 or FG_TARGET_F32 */
+  int32_t height, width, channels; /* of the source */
+  int32_t downscale;
+  int32_t mask_dtype; /* FG_TARGET_U8 (bool too) or FG_TARGET_F32; not looked at with a null mask */
+  int32_t reserved;   /* 0 */
+  const void* src;
+  const void* mask;        /* or null */
+  const float* background; /* or null (3 channels only) */
+} fg_target_desc;
+int fg_target_loss_supported(const fg_target_desc* target);
+size_t fg_target_loss_workspace_floats(const fg_target_desc* target);
+int fg_target_loss_fwd(const fg_target_desc* target, const float* pred, float* maps, float* workspace, size_t workspace_floats,
+                       float* out, fg_stream_t stream);
+int fg_target_loss_bwd(const fg_target_desc* target, const float* pred, const float* maps, const float* v_out, float* v_pred,
+                       fg_stream_t stream);
 
 #ifdef __cplusplus
 }
