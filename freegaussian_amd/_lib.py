@@ -155,6 +155,17 @@ SIGNATURES = {
     "fg_target_loss_workspace_floats": (c_size_t, [P]),
     "fg_target_loss_fwd": (c_int, [P, P, P, P, c_size_t, P, P]),  # (target, pred, maps or null, workspace, floats, out[3], stream)
     "fg_target_loss_bwd": (c_int, [P, P, P, P, P, P]),  # (target, pred, maps, v_out[2], v_pred, stream)
+    # the displacement of the projected centres between two frames (csrc/flow_disp.hip); strides in floats
+    # (N, means_t, mt_stride, means_0, m0_stride, viewmat_t, viewmat_0 or null, K, width, height, near, margin, disp, stream)
+    "fg_flow_disp_fwd": (c_int, [c_int64, P, c_int64, P, c_int64, P, P, P, c_int, c_int, c_float, c_float, P, P]),
+    # (..., margin, g_disp, g_means_t or null, g_means_0 or null, stream)
+    "fg_flow_disp_bwd": (c_int, [c_int64, P, c_int64, P, c_int64, P, P, P, c_int, c_int, c_float, c_float, P, P, P, P]),
+    # the masked flow L1 against the full-resolution batch array (csrc/flow_loss.hip)
+    "fg_flow_l1_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),  # (H0, W0, downscale)
+    # (H, W, pred, pixel_stride, row_stride, H0, W0, downscale, flows, mask or null, mask_dtype, workspace, bytes, out[1], stream)
+    "fg_flow_l1_fwd": (c_int, [c_int, c_int, P, c_int64, c_int64, c_int, c_int, c_int, P, P, c_int, P, c_size_t, P, P]),
+    # (..., mask_dtype, workspace, v_out[1], g_pred, stream)
+    "fg_flow_l1_bwd": (c_int, [c_int, c_int, P, c_int64, c_int64, c_int, c_int, c_int, P, P, c_int, P, P, P, P]),
 }  # fmt: skip
 
 # test hooks, not declared in the public header

@@ -15,7 +15,19 @@
   of Corollary 1 (docs/index.html:293-299), sum_i T_i alpha_i (mu_{i,t} - mu_{i,0}), rendered as
   two extra channels of the same raster pass, plus F2 (Lemma 1) per-Gaussian Jacobian terms
   through ``ops.gaussian_flow``.  The reference ships no loss that consumes these (SURVEY.md §0
-  finding 3); the loss form here (L1 on finite-depth pixels) is a build choice."""
+  finding 3); the loss form here (L1 on finite-depth pixels) is a build choice.
+
+THE FLOW CONVENTION of everything that trains against a flow array (``FreeGaussianModelConfig.flow_loss_weight``,
+``harness.train_step(flows=...)``, ``ops.flow_l1``):  ``flows[y, x]`` is the displacement, in FULL-RESOLUTION pixels,
+by which the surface seen at ``(x, y)`` of the CURRENT frame has moved since frame 0 (the frame of
+``camera.metadata["cameras0"]``, ``interval`` frames earlier): where it is now minus where it was.  A render at
+downscale d compares with the box mean of the d x d block divided by d; a block with a NaN or inf carries no weight.
+With ``flow_camera_motion=False`` the array is interflow -- the camera's own flow already taken out, as the
+reference's ``interflow_n{k}/*.npy`` are -- and both frames are projected under the current camera; with True it is
+raw optical flow and frame 0 is projected under ``cameras0``'s pose.  The training path is
+``ops.flow_displacement`` (the per-Gaussian mu_t - mu_0, one launch) -> two extra raster channels -> ``ops.flow_l1``;
+``render_with_flow`` and ``flow_loss`` below stay as the stage-by-stage statement the tests compare it with.
+Stage 2 (the control model), ``graphed.GraphedModelStep`` and view-DP take no flow term."""
 from __future__ import annotations
 
 from typing import Dict, Optional, Tuple

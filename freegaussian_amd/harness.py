@@ -133,7 +133,8 @@ def apply_schedules(opts, step: int, table: Optional[Dict[str, OptimSpec]] = Non
 
 def train_step(model: FreeGaussianModel, opts, camera: Camera, gt_image: torch.Tensor, step: int, table=None,
                grad_sync=None, num_train_data: Optional[int] = None, stats_sync=None, graphed=None,
-               mask: Optional[torch.Tensor] = None, metrics_every: int = 1, dp=None) -> Dict[str, float]:  # fmt: skip
+               mask: Optional[torch.Tensor] = None, metrics_every: int = 1, dp=None,
+               flows: Optional[torch.Tensor] = None) -> Dict[str, float]:  # fmt: skip
     """One iteration in the reference's callback order: step_cb -> get_outputs ->
     loss -> backward -> [view-DP gradient exchange] -> optimizers -> after_train_iter ->
     refinement_after every ``refine_every`` steps (freegaussian_model.py:575-590; needs
@@ -147,11 +148,16 @@ def train_step(model: FreeGaussianModel, opts, camera: Camera, gt_image: torch.T
     (freegaussian_model.py:956-963).  The loss is the sum of ``model.get_loss_dict`` (main loss + the optional
     scale regulariser), as nerfstudio's trainer sums it.  ``metrics_every`` = k: loss / psnr are read back (one host
     synchronisation) only on steps divisible by k, as a trainer that logs every k steps does; the other steps return
-    the Gaussian count alone and the host runs ahead of the GPU."""
+    the Gaussian count alone and the host runs ahead of the GPU.  ``flows`` [H0,W0,2]: the batch's flow array in
+    full-resolution pixels (flow.py has the convention); where the model's flow branch is active for ``camera``
+    (``config.flow_loss_weight`` > 0, ``model.flow_camera0``) the loss dict's ``flow_loss`` joins the sum and is returned beside
+    ``loss``; such a step never takes the graphed path (``graphed.GraphedModelStep`` captures no flow branch)."""
     model.step_cb(step)
+    flow_step = flows is not None and model.flow_camera0(camera) is not None
     plain_loss = (mask is None and gt_image.shape[-1] == 3 and not model.config.use_scale_regularization
                   and not model.config.use_bilateral_grid)
-    if graphed is not None and dp is None and plain_loss and graphed.applicable(camera):
+    flow_loss = None
+    if graphed is not None and dp is None and plain_loss and not flow_step and graphed.applicable(camera):
         # (no zero_grad: the replay refills the .grad tensors, which are static buffers of the graph)
         out, loss = graphed.step(camera, gt_image)
         gt = graphed.static["gt"]
@@ -165,10 +171,15 @@ def train_step(model: FreeGaussianModel, opts, camera: Camera, gt_image: torch.T
         with (dp.step() if dp is not None else contextlib.nullcontext()):  # (view-DP: the exchange runs on exit)
             out = model.get_outputs(camera)
             batch = {"image": gt_image} if mask is None else {"image": gt_image, "mask": mask}
+            if flows is not None:
+                batch["flows"] = flows
             loss_dict = model.get_loss_dict(out, batch)
             loss = loss_dict["main_loss"] + loss_dict["scale_reg"]
             if "tv_loss" in loss_dict:  # (bilateral grids: freegaussian_model.py:988-989)
                 loss = loss + loss_dict["tv_loss"]
+            if "flow_loss" in loss_dict:
+                flow_loss = loss_dict["flow_loss"]
+                loss = loss + flow_loss
             gt = None  # (composited below, only on the steps whose metrics are read)
             loss.backward()
     if grad_sync is not None:
@@ -187,13 +198,14 @@ def train_step(model: FreeGaussianModel, opts, camera: Camera, gt_image: torch.T
     if metrics_every > 1 and step % metrics_every != 0:
         return {"gaussian_count": model.num_points}
     with torch.no_grad():
+        flow_read = {} if flow_loss is None else {"flow_loss": float(flow_loss)}
         kept = out.get(FUSED_TARGET_KEY) if gt is None else None
         if kept is not None and kept[0] is gt_image and kept[1] is mask:
             # (FG_FUSED_TARGET=1: the loss call left the squared error of this very batch; no target is composited)
-            return {"loss": float(loss), "psnr": float(-10.0 * torch.log10(kept[4])), "gaussian_count": model.num_points}
+            return {"loss": float(loss), "psnr": float(-10.0 * torch.log10(kept[4])), "gaussian_count": model.num_points, **flow_read}
         if gt is None:
             gt = model.composite_with_background(model.get_gt_img(gt_image), out["background"])
-        return {"loss": float(loss), "psnr": float(psnr(out["rgb"], gt)), "gaussian_count": model.num_points}
+        return {"loss": float(loss), "psnr": float(psnr(out["rgb"], gt)), "gaussian_count": model.num_points, **flow_read}
 
 
 def eval_image(model: FreeGaussianModel, camera: Camera, batch: Dict[str, torch.Tensor]):

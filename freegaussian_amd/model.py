@@ -12,6 +12,7 @@ Everything here is plain torch (small elementwise ops and the MLP GEMMs); the ra
 the HIP library behind ``freegaussian_amd.rasterization``."""
 from __future__ import annotations
 
+import contextlib
 import copy
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Union
@@ -112,6 +113,16 @@ class FreeGaussianModelConfig:
     # build extension: fold the SH cat, exp / sigmoid / quaternion
     # normalisation (+ MLP deltas) and the background composite + clamp into the HIP passes
     fused_front_end: bool = True
+    # build extension: flow-supervised stage-1 training (INTEGRATION.md "Flow supervision").  0 = off: nothing below is looked at.
+    # Above 0, a training camera whose metadata["cameras0"] is a camera of its own with times adds the composited Gaussian flow
+    # (ops.flow_displacement as two extra raster channels) to the outputs, and get_loss_dict adds
+    # flow_loss_weight * ops.flow_l1 against batch["flows"].
+    flow_loss_weight: float = 0.0
+    # False: batch["flows"] is interflow (camera flow already removed: what the reference's loader delivers), both frames are
+    # projected under the current camera; True: raw optical flow, frame 0 is projected under cameras0's pose
+    flow_camera_motion: bool = False
+    # False: the frame-0 means are evaluated under no_grad (the gradient-free fused MLP forward where that applies)
+    flow_frame0_grad: bool = True
 
 
 # where get_loss_dict / get_metrics_dict leave the fused target call's (image, mask, l1, ssim, mse) in the outputs dict
@@ -412,6 +423,7 @@ class FreeGaussianModel(nn.Module):
                 gt_img = gt_img * mask
                 pred_img = pred_img * mask
             l1, sim = l1_and_ssim(pred_img, gt_img)  # (fused on the GPU: ops.l1_ssim)
+        flow_term = self._flow_loss(outputs, batch)
         simloss = 1 - sim
         if self.config.use_scale_regularization and self.step % 10 == 0:
             scale_exp = torch.exp(self.scales)
@@ -428,7 +440,24 @@ class FreeGaussianModel(nn.Module):
             from .bilagrid import total_variation_loss
 
             loss_dict["tv_loss"] = 10 * total_variation_loss(self.bil_grids.grids)
+        if flow_term is not None:
+            loss_dict["flow_loss"] = flow_term
         return loss_dict
+
+    def _flow_loss(self, outputs, batch):
+        """``flow_loss_weight`` x the masked L1 of ``outputs["flow"]`` against ``batch["flows"]`` ([H0,W0,2], full-resolution
+        pixels; flow.py has the convention) through one ``ops.flow_l1`` -- the downscale, the mask's box mean and the weights of
+        non-finite source pixels are formed inside the call, nothing is read back.  None where the outputs carry no flow or the
+        batch no flows: the key is then absent."""
+        if "flow" not in outputs or "flows" not in batch:
+            return None
+        from . import ops
+
+        flows = torch.as_tensor(batch["flows"]).to(self.device, torch.float32).contiguous()
+        mask = batch.get("mask")
+        if mask is not None:
+            mask = mask.to(self.device).contiguous()
+        return self.config.flow_loss_weight * ops.flow_l1(outputs["flow"], flows, mask, self._get_downscale_factor())
 
     # -- the pieces of get_outputs shared by stage 1 and stage 2 ------------------------------------
     def _camera_setup(self, camera: Camera):
@@ -482,8 +511,9 @@ class FreeGaussianModel(nn.Module):
             raise ValueError("Unknown rasterize_mode: %s", self.config.rasterize_mode)
         return "RGB+ED" if (self.config.output_depth_during_training or not self.training) else "RGB"
 
-    def _rasterize_and_finish(self, means, quats, scales, colors, sh_degree, viewmat, K, W, H):
-        """The raster call with the reference's exact kwargs (:847-868) and O1 (:869-898)."""
+    def _rasterize_and_finish(self, means, quats, scales, colors, sh_degree, viewmat, K, W, H, extra_channels=None):
+        """The raster call with the reference's exact kwargs (:847-868) and O1 (:869-898).  ``extra_channels`` [N,2] (the flow
+        branch): composited behind the render-mode channels and returned as ``"flow"``, a view of the render."""
         render_mode = self._render_mode()
         render, alpha, info = rasterization(
             means=means,
@@ -504,6 +534,7 @@ class FreeGaussianModel(nn.Module):
             sparse_grad=False,
             absgrad=True,
             rasterize_mode=self.config.rasterize_mode,
+            **({} if extra_channels is None else {"extra_channels": extra_channels}),
         )
         if self.training and info["means2d"].requires_grad:
             info["means2d"].retain_grad()
@@ -519,20 +550,23 @@ class FreeGaussianModel(nn.Module):
             depth = None
         if not self.training:
             background = background.expand(H, W, 3)
-        return {"rgb": rgb.squeeze(0), "depth": depth, "accumulation": alpha.squeeze(0), "background": background}
+        out = {"rgb": rgb.squeeze(0), "depth": depth, "accumulation": alpha.squeeze(0), "background": background}
+        if extra_channels is not None:
+            out["flow"] = render[0, :, :, render.shape[-1] - 2 :]
+        return out
 
-    def _render(self, means, d_rotation, d_scaling, viewmat, K, W, H):
+    def _render(self, means, d_rotation, d_scaling, viewmat, K, W, H, extra_channels=None):
         """Activations (:801, :826-830, :844-851) + raster call + O1, either folded into the HIP
         passes (``fused_front_end``; SH path only) or spelled out in torch exactly like the
         reference."""
         if self.config.fused_front_end and self.config.sh_degree > 0:
-            return self._rasterize_raw_and_finish(means, d_rotation, d_scaling, viewmat, K, W, H)
+            return self._rasterize_raw_and_finish(means, d_rotation, d_scaling, viewmat, K, W, H, extra_channels)
         colors, sh_degree = self._colors_and_degree()
         scales = torch.exp(self.scales) + d_scaling
         quats = self.quats / self.quats.norm(dim=-1, keepdim=True) + d_rotation
-        return self._rasterize_and_finish(means, quats, scales, colors, sh_degree, viewmat, K, W, H)
+        return self._rasterize_and_finish(means, quats, scales, colors, sh_degree, viewmat, K, W, H, extra_channels)
 
-    def _rasterize_raw_and_finish(self, means, d_rotation, d_scaling, viewmat, K, W, H):
+    def _rasterize_raw_and_finish(self, means, d_rotation, d_scaling, viewmat, K, W, H, extra_channels=None):
         from .rasterization import rasterize_gauss_params
 
         render_mode = self._render_mode()
@@ -545,6 +579,7 @@ class FreeGaussianModel(nn.Module):
             d_scales=d_scaling if torch.is_tensor(d_scaling) else None,
             background=background, clamp=True, near_plane=0.01, far_plane=1e10, tile_size=16,
             render_mode=render_mode, absgrad=True, rasterize_mode=self.config.rasterize_mode,
+            **({} if extra_channels is None else {"extra_channels": extra_channels}),
         )  # fmt: skip
         if self.training and info["means2d"].requires_grad:
             info["means2d"].retain_grad()
@@ -559,8 +594,11 @@ class FreeGaussianModel(nn.Module):
         if not self.training:
             background = background.expand(H, W, 3)
         # (a full-width slice is still a SliceBackward node: a zeros + a copy launch in every backward)
-        return {"rgb": (rgb if rgb.shape[-1] == 3 else rgb[..., :3]).squeeze(0), "depth": depth, "accumulation": alpha.squeeze(0),
-                "background": background}  # fmt: skip
+        out = {"rgb": (rgb if rgb.shape[-1] == 3 else rgb[..., :3]).squeeze(0), "depth": depth, "accumulation": alpha.squeeze(0),
+               "background": background}  # fmt: skip
+        if extra_channels is not None:
+            out["flow"] = rgb[0, :, :, rgb.shape[-1] - 2 :]
+        return out
 
     # -- H1 + H4 -----------------------------------------------------------------------------------
     def get_outputs(self, camera: Camera) -> Dict[str, Union[torch.Tensor, List, None]]:
@@ -582,7 +620,50 @@ class FreeGaussianModel(nn.Module):
 
     def _get_outputs_on_active_rows(self, camera: Camera):
         viewmat, K, W, H = self._camera_setup(camera)
-        return self._bilateral(self._outputs_from(viewmat, K, W, H, camera.times), camera)
+        cam0 = self.flow_camera0(camera)
+        if cam0 is None:
+            return self._bilateral(self._outputs_from(viewmat, K, W, H, camera.times), camera)
+        # the flow branch: frame 0's time, and its pose where the batch flows still hold the camera's motion
+        viewmat0 = self._staged_viewmat(cam0) if self.config.flow_camera_motion else None
+        return self._bilateral(self._outputs_from(viewmat, K, W, H, camera.times, flow=(cam0.times, viewmat0)), camera)
+
+    def flow_camera0(self, camera: Camera) -> Optional[Camera]:
+        """The frame-0 camera of the flow branch, or None where ``get_outputs`` does not take it.  It does while training with
+        ``flow_loss_weight`` > 0 for a camera whose ``metadata["cameras0"]`` is a ``Camera`` of its own with ``times``, from
+        ``warm_up`` on -- or from the first step with ``flow_camera_motion``: before the warm-up both frames have the same means,
+        so under one camera the displacement is identically zero and carries no gradient."""
+        cfg = self.config
+        if not (self.training and cfg.flow_loss_weight > 0):
+            return None
+        cam0 = camera.metadata.get("cameras0") if camera.metadata is not None else None
+        if not isinstance(cam0, Camera) or cam0 is camera or cam0.times is None or camera.times is None:
+            return None
+        if self.step < cfg.warm_up and not cfg.flow_camera_motion:
+            return None
+        return cam0
+
+    def _staged_viewmat(self, camera: Camera) -> torch.Tensor:
+        """``camera``'s world-to-camera matrix [1,4,4] on the device; a host-side pose goes through the pinned staging ring of
+        ``_camera_setup``, asynchronously."""
+        c2w = camera.camera_to_worlds
+        if c2w.is_cuda or self.device.type != "cuda":
+            return get_viewmat(c2w.to(self.device))
+        stage, _ = _pose_slot()
+        stage[:16] = get_viewmat(c2w.float()).reshape(-1)
+        return stage[:16].to(self.device, non_blocking=True).view(1, 4, 4)
+
+    def _flow_channels(self, means, flow, viewmat, K, W, H):
+        """[N,2]: the displacement of every projected centre since frame 0 (``ops.flow_displacement``; margin = the longer image
+        side).  The frame-0 means take the deformation path of the current ones, at ``cameras0``'s time; before the warm-up they
+        are the means themselves."""
+        from . import ops
+
+        times0, viewmat0 = flow
+        with contextlib.nullcontext() if self.config.flow_frame0_grad else torch.no_grad():
+            means0 = self.means if self.step < self.config.warm_up else self._deformed(self.means, times0)[0]
+        if not self.config.flow_frame0_grad:
+            means0 = means0.detach()
+        return ops.flow_displacement(means, means0, viewmat, viewmat0, K, W, H, near=0.01, margin=float(max(W, H)))
 
     def _bilateral(self, out, camera: Camera):
         """(:879-882) while training, the rendered image through the bilateral grid of its training camera."""
@@ -593,27 +674,32 @@ class FreeGaussianModel(nn.Module):
             out["rgb"] = apply_to_render(self.bil_grids, rgb.unsqueeze(0), camera.metadata["cam_idx"], rgb.shape[0], rgb.shape[1]).squeeze(0)
         return out
 
-    def _outputs_from(self, viewmat, K, W, H, times):
+    def _outputs_from(self, viewmat, K, W, H, times, flow=None):
         """H4 + the raster call on device-resident camera data: everything of ``get_outputs`` behind the host
-        side of the camera (what ``graphed.GraphedModelStep`` captures)."""
+        side of the camera (what ``graphed.GraphedModelStep`` captures).  ``flow``: None, or the flow branch's (frame-0 times,
+        frame-0 viewmat or None for the current camera)."""
         if self.step < self.config.warm_up:
             means = self.means
             d_rotation, d_scaling = 0.0, 0.0
         else:
-            pts = self.means
-            times = times.to(self.device).expand(pts.shape[0], -1)
-            if not torch.is_grad_enabled() and fused_applies(self.deform, pts, times):
-                # (no gradient wanted: the fused forward applies the transform itself and never writes [N,4,4])
-                means, d_rotation, d_scaling = self.deform.deformed_points(pts.detach(), times)
-            elif _se3_fused_for(pts, times):
-                # (FG_FUSED_SE3=1: the heads to the moved means in one launch, and one in the backward; pts is the
-                #  undetached parameter, so its gradient arrives as it does below)
-                w, v, d_rotation, d_scaling = self.deform.heads(pts.detach(), times)
-                means = _se3_apply(w, v, pts)
-            else:
-                d_xyz, d_rotation, d_scaling = self.deform(pts.detach(), times)
-                means = transform_points(d_xyz, pts)  # (:840-843; not torch.bmm: utils.small_bmm)
-        return self._render(means, d_rotation, d_scaling, viewmat, K, W, H)
+            means, d_rotation, d_scaling = self._deformed(self.means, times)
+        if flow is None:
+            return self._render(means, d_rotation, d_scaling, viewmat, K, W, H)
+        return self._render(means, d_rotation, d_scaling, viewmat, K, W, H, self._flow_channels(means, flow, viewmat, K, W, H))
+
+    def _deformed(self, pts, times):
+        """(means, d_rotation, d_scaling) of ``pts`` (the undetached parameter) moved by the deformation net at ``times``."""
+        times = times.to(self.device).expand(pts.shape[0], -1)
+        if not torch.is_grad_enabled() and fused_applies(self.deform, pts, times):
+            # (no gradient wanted: the fused forward applies the transform itself and never writes [N,4,4])
+            return self.deform.deformed_points(pts.detach(), times)
+        if _se3_fused_for(pts, times):
+            # (FG_FUSED_SE3=1: the heads to the moved means in one launch, and one in the backward; pts is the
+            #  undetached parameter, so its gradient arrives as it does below)
+            w, v, d_rotation, d_scaling = self.deform.heads(pts.detach(), times)
+            return _se3_apply(w, v, pts), d_rotation, d_scaling
+        d_xyz, d_rotation, d_scaling = self.deform(pts.detach(), times)
+        return transform_points(d_xyz, pts), d_rotation, d_scaling  # (:840-843; not torch.bmm: utils.small_bmm)
 
     @torch.no_grad()
     def get_outputs_for_camera(self, camera: Camera):

@@ -9,6 +9,7 @@ from __future__ import annotations
 from typing import Optional, Tuple
 
 import ctypes
+import math
 import os
 import threading
 import time
@@ -1430,6 +1431,164 @@ def se3_apply(w: torch.Tensor, v: torch.Tensor, pts: torch.Tensor) -> torch.Tens
     if pts.shape[0] == 0:  # (nothing to launch; the result still hangs on its inputs)
         return pts + (w + v) * 0.0
     return _Se3Apply.apply(_rows(w, 3), _rows(v, 3), pts.contiguous())
+
+
+class _FlowDisplacement(torch.autograd.Function):
+    """The displacement of the projected centres between frame 0 and the current frame (csrc/flow_disp.hip): saves its inputs
+    only (24 B a row and the camera constants); the backward recomputes and forms the gradients that are asked for."""
+
+    @staticmethod
+    def forward(ctx, means_t, means_0, viewmat_t, viewmat_0, K, width, height, near, margin):
+        N = means_t.shape[0]
+        disp = torch.empty(N, 2, dtype=torch.float32, device=means_t.device)
+        _call("fg_flow_disp_fwd", N, _ptr(means_t), _row_stride(means_t, 3), _ptr(means_0), _row_stride(means_0, 3), _ptr(viewmat_t),
+              _ptr(viewmat_0), _ptr(K), width, height, near, margin, _ptr(disp), _stream(), stage="fg_flow_disp_fwd")  # fmt: skip
+        ctx.save_for_backward(means_t, means_0, viewmat_t, viewmat_0, K)
+        ctx.args = (width, height, near, margin)
+        return disp
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_disp):
+        means_t, means_0, viewmat_t, viewmat_0, K = ctx.saved_tensors
+        want = ctx.needs_input_grad[:2]
+        if not any(want):
+            return (None,) * 9
+        g_disp = _f32(g_disp, "g_disp")
+        N = means_t.shape[0]
+        g_t, g_0 = (torch.empty(N, 3, dtype=torch.float32, device=g_disp.device) if k else None for k in want)
+        _call("fg_flow_disp_bwd", N, _ptr(means_t), _row_stride(means_t, 3), _ptr(means_0), _row_stride(means_0, 3), _ptr(viewmat_t),
+              _ptr(viewmat_0), _ptr(K), *ctx.args, _ptr(g_disp), _ptr(g_t), _ptr(g_0), _stream(), stage="fg_flow_disp_bwd")  # fmt: skip
+        return (g_t, g_0) + (None,) * 7
+
+
+def flow_displacement(means_t: torch.Tensor, means_0: torch.Tensor, viewmat_t: torch.Tensor, viewmat_0: Optional[torch.Tensor],
+                      K: torch.Tensor, width: int, height: int, near: float = 0.01, margin: float = math.inf) -> torch.Tensor:
+    """The 2-D displacement [N,2] of the projected Gaussian centres: ``means_t`` [N,3] under ``viewmat_t`` minus ``means_0``
+    [N,3] under ``viewmat_0`` (None: the same camera for both frames), in pixels of the ``width`` x ``height`` image of ``K``
+    -- the per-Gaussian term of the composited Gaussian flow, to be passed as ``extra_channels`` of the raster call.  Formed
+    without cancelling at small motion; a row behind either camera (z <= ``near``) or with a projected centre more than
+    ``margin`` pixels outside the image is exactly zero and gets exactly zero gradients (include/fgraster.h, FD).  What two
+    ``ops.project`` passes, a select and two ``_Project`` backwards state, as one launch forward and one backward.
+    Differentiable with respect to both sets of means; the cameras are constants: a ``viewmat`` or ``K`` that requires a
+    gradient is refused.  The means are read in place where they are contiguous or columns of a wider row block."""
+    for name, t in (("means_t", means_t), ("means_0", means_0)):
+        if t.dim() != 2 or t.shape[1] != 3 or t.shape[0] != means_t.shape[0]:
+            raise ValueError(f"flow_displacement: {name} [N,3] expected, got means_t {tuple(means_t.shape)}, means_0 {tuple(means_0.shape)}")
+    cams = {"viewmat_t": (viewmat_t, 16), "K": (K, 9)}
+    if viewmat_0 is not None:
+        cams["viewmat_0"] = (viewmat_0, 16)
+    for name, (t, n) in cams.items():
+        if t.numel() != n:
+            raise ValueError(f"flow_displacement: {name} of {n} elements expected, got {tuple(t.shape)}")
+        if t.requires_grad and torch.is_grad_enabled():
+            raise NotImplementedError(f"flow_displacement: {name} requires a gradient: the cameras are constants here; detach() it")
+    statement = "flow.render_with_flow's two ops.project passes are the torch-level statement of it"
+    _gpu_float32("flow_displacement", statement, means_t.device, means_t=means_t, means_0=means_0,
+                 **{name: t for name, (t, _) in cams.items()})  # fmt: skip
+    width, height, near, margin = int(width), int(height), float(near), float(margin)
+    if width <= 0 or height <= 0:
+        raise ValueError(f"flow_displacement: width and height above 0 expected, got {width} x {height}")
+    if not (0.0 <= near < math.inf):
+        raise ValueError(f"flow_displacement: near finite and not negative expected, got {near}")
+    if not margin >= 0.0:
+        raise ValueError(f"flow_displacement: margin of at least 0 (inf: no rectangle test) expected, got {margin}")
+    if means_t.shape[0] == 0:  # (nothing to launch; the result still hangs on its inputs)
+        return (means_t + means_0)[:, :2] * 0.0
+    flat = lambda t: None if t is None else t.detach().reshape(-1).contiguous()  # noqa: E731
+    return _FlowDisplacement.apply(_rows(means_t, 3), _rows(means_0, 3), flat(viewmat_t), flat(viewmat_0), flat(K), width, height,
+                                   near, margin)  # fmt: skip
+
+
+def _flow_view(pred: torch.Tensor) -> torch.Tensor:
+    """``pred`` [H,W,2] as ``fg_flow_l1_fwd`` reads it, in place: channel stride 1, pixels at least 2 floats apart, rows that
+    do not interleave -- the last two channels of a render are; anything else: a copy."""
+    H, W, _ = pred.shape
+    px = pred.stride(1) if W > 1 else 2
+    rw = pred.stride(0) if H > 1 else (W - 1) * px + 2
+    if pred.stride(2) == 1 and px >= 2 and rw >= (W - 1) * px + 2 and px <= 65536 and pred.data_ptr() % 4 == 0:
+        return pred
+    return pred.contiguous()
+
+
+def _flow_strides(pred: torch.Tensor):
+    """(pixel stride, row stride) of a ``_flow_view`` in floats; of an axis of one element, its tight value (torch's stride of
+    such an axis is arbitrary)."""
+    H, W, _ = pred.shape
+    px = pred.stride(1) if W > 1 else 2
+    return px, (pred.stride(0) if H > 1 else (W - 1) * px + 2)
+
+
+class _FlowL1(torch.autograd.Function):
+    """The masked L1 of the rendered flow channels against the full-resolution batch array (csrc/flow_loss.hip): saves
+    references to its inputs and the 16-byte totals of its workspace; no target tensor."""
+
+    @staticmethod
+    def forward(ctx, pred, flows, mask, d):
+        H, W, _ = pred.shape
+        H0, W0, _ = flows.shape
+        dev = pred.device
+        n_ws = int(_lib.load().fg_flow_l1_workspace_bytes(H0, W0, d))
+        if n_ws == 0:
+            raise ValueError(f"flow_l1: flows {tuple(flows.shape)} at downscale {d} is outside what the fused flow loss takes")
+        ws = torch.empty(n_ws // 8, dtype=torch.float64, device=dev)
+        out = torch.empty(1, dtype=torch.float32, device=dev)
+        mdt = _lib.TARGET_F32 if (mask is not None and mask.dtype == torch.float32) else _lib.TARGET_U8
+        px, rw = _flow_strides(pred)
+        _call("fg_flow_l1_fwd", H, W, _ptr(pred), px, rw, H0, W0, d, _ptr(flows), _ptr(mask), mdt, _ptr(ws), n_ws, _ptr(out), _stream(),
+              stage="fg_flow_l1_fwd")  # fmt: skip
+        ctx.save_for_backward(pred, flows, mask, ws)
+        ctx.args = (d, mdt)
+        return out[0]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, v):
+        pred, flows, mask, ws = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        d, mdt = ctx.args
+        H, W, _ = pred.shape
+        H0, W0, _ = flows.shape
+        v = _f32(v, "v_out").reshape(1)
+        g = torch.empty(H, W, 2, dtype=torch.float32, device=pred.device)
+        px, rw = _flow_strides(pred)
+        _call("fg_flow_l1_bwd", H, W, _ptr(pred), px, rw, H0, W0, d, _ptr(flows), _ptr(mask), mdt, _ptr(ws), _ptr(v), _ptr(g), _stream(),
+              stage="fg_flow_l1_bwd")  # fmt: skip
+        return g, None, None, None
+
+
+def flow_l1(pred: torch.Tensor, flows: torch.Tensor, mask: Optional[torch.Tensor] = None, downscale: int = 1) -> torch.Tensor:
+    """The masked L1 (a scalar) between the rendered flow ``pred`` [H,W,2] -- a view such as the last two channels of the
+    render, read in place -- and the batch's ``flows`` [H0,W0,2] in FULL-resolution pixels, H = H0 // downscale, W = W0 //
+    downscale, downscale in 1, 2, 4, 8.  Per render pixel the target is the box mean of its source block divided by
+    ``downscale``; the weight is 0 where any source value of the block is not finite, else the box mean of ``mask`` ([H0,W0,1]
+    or [H0,W0]; bool, uint8 or float32; 1 without one); loss = sum w (|dx| + |dy|) / (2 sum w), and 0 with a zero gradient where
+    sum w = 0 (include/fgraster.h, FL).  Sums in double in a fixed order: bit for bit reproducible; nothing is read back.
+    Differentiable with respect to ``pred`` only."""
+    if pred.dim() != 3 or pred.shape[-1] != 2 or pred.dtype != torch.float32:
+        raise ValueError(f"flow_l1: pred [H,W,2] float32 expected, got {tuple(pred.shape)} {pred.dtype}")
+    if flows.dim() != 3 or flows.shape[-1] != 2 or flows.dtype != torch.float32:
+        raise ValueError(f"flow_l1: flows [H0,W0,2] float32 expected, got {tuple(flows.shape)} {flows.dtype}")
+    if not flows.is_contiguous():
+        raise ValueError("flow_l1: flows is read in place: a contiguous tensor expected")
+    d = int(downscale)
+    if d not in TARGET_DOWNSCALES:
+        raise ValueError(f"flow_l1: downscale 1, 2, 4 or 8 expected, got {downscale}")
+    H0, W0, _ = flows.shape
+    if tuple(pred.shape[:2]) != (H0 // d, W0 // d) or min(pred.shape[:2]) < 1:
+        raise ValueError(f"flow_l1: pred is {tuple(pred.shape[:2])}, flows at downscale {d} is {(H0 // d, W0 // d)}")
+    if mask is not None:
+        if mask.dtype not in TARGET_MASK_DTYPES or tuple(mask.shape) not in ((H0, W0, 1), (H0, W0)) or not mask.is_contiguous():
+            raise ValueError(f"flow_l1: mask [H0,W0,1] or [H0,W0], contiguous, bool / uint8 / float32 expected, got "
+                             f"{tuple(mask.shape)} {mask.dtype}")  # fmt: skip
+        mask = mask.detach()
+    statement = "flow.flow_loss on resized arrays is the torch statement of it"
+    _gpu_float32("flow_l1", statement, None, **{k: t for k, t in dict(pred=pred, flows=flows, mask=mask).items() if t is not None})
+    devices = {t.device for t in (pred, flows, mask) if t is not None}
+    if len(devices) != 1:
+        raise ValueError(f"flow_l1: tensors on one device expected, got {sorted(map(str, devices))}")
+    return _FlowL1.apply(_flow_view(pred), flows.detach(), mask, d)
 
 
 class ControlPlan:

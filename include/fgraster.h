@@ -58,7 +58,9 @@ typedef void* fg_stream_t;
  * fg_control_supported, fg_control_workspace_bytes, fg_control_attr_mean, fg_control_value_rows, fg_control_scatter_fwd and
  * fg_control_scatter_bwd -- a library without them has no fused stage-2 control stage, and the host keeps its torch statement
  * of it.  Likewise BY NAME: fg_target_loss_supported, fg_target_loss_workspace_floats, fg_target_loss_fwd and
- * fg_target_loss_bwd -- a library without them has no fused training target, and the host keeps its torch statement of it.) */
+ * fg_target_loss_bwd -- a library without them has no fused training target, and the host keeps its torch statement of it.
+ * Likewise BY NAME: fg_flow_disp_fwd, fg_flow_disp_bwd, fg_flow_l1_workspace_bytes, fg_flow_l1_fwd and fg_flow_l1_bwd -- a
+ * library without them has no flow-supervised training: the model's flow term is an error there, not a torch fall-back.) */
 #define FG_COUNT_OUT_WORDS 16 /* int64 words of a count_out block (fg_stbin_count, fg_step_io): ABI 9 */
 
 int fg_abi_version(void);
@@ -1274,6 +1276,75 @@ int fg_target_loss_fwd(const fg_target_desc* target, const float* pred, float* m
                        float* out, fg_stream_t stream);
 int fg_target_loss_bwd(const fg_target_desc* target, const float* pred, const float* maps, const float* v_out, float* v_pred,
                        fg_stream_t stream);
+
+/* ---- FD the 2-D displacement of the projected Gaussian centres between frame 0 and the current frame (found BY NAME, see
+ * FG_ABI_MINOR; csrc/flow_disp.hip), forward and backward, one streaming launch each: the per-Gaussian term mu_t - mu_0 of the
+ * composited Gaussian flow that the raster pass carries as two extra channels.  All fp32.  Per row r < N:
+ *   p_t = R_t m_t + tau_t,  p_0 = R_0 m_0 + tau_0   (R, tau: the upper 3 x 4 of a row-major [4,4] world-to-camera matrix)
+ *   VALIDITY RULE: the row is valid iff z_t > near and z_0 > near and both projected centres (f_x x / z + c_x, f_y y / z + c_y)
+ *     lie in [-margin, width + margin] x [-margin, height + margin]; margin = inf switches the rectangle test off (a centre
+ *     that is not a number is outside).  An invalid row writes exact zeros and gets exact zero gradients.
+ *   CANCELLATION-FREE FORM: with Delta = p_t - p_0,
+ *     disp_x = f_x (Delta_x z_0 - x_0 Delta_z) / (z_t z_0),   disp_y = f_y (Delta_y z_0 - y_0 Delta_z) / (z_t z_0)
+ *     -- f (x_t / z_t - x_0 / z_0) without the two quotients, whose difference at small motion keeps only their last bits.
+ *     c_x, c_y never enter the value.  viewmat_0 null = one camera for both frames: Delta = R_t (m_t - m_0) and
+ *     p_t = p_0 + Delta, so the translation never enters Delta.
+ *   means_t, means_0   rows of 3 floats, mt_stride / m0_stride floats apart (>= 3): contiguous [N,3] or columns of a wider
+ *     row block, read in place; they may overlap each other.  viewmat_t, viewmat_0 (or null), K [3,3]: device arrays, constants.
+ *   disp, g_disp [N,2] contiguous, 8-byte aligned; g_means_t, g_means_0 [N,3] contiguous.
+ * fg_flow_disp_bwd recomputes everything from the inputs (the forward saves nothing) and writes the closed form
+ *   g_means_t = R_t^T (a, b, -(a x_t + b y_t) / z_t),  a = g_x f_x / z_t, b = g_y f_y / z_t;   g_means_0 likewise with R_0, p_0
+ *   and the opposite sign.  Either may be null: that gradient is neither computed nor written (both null: no launch).
+ *   DETERMINISM: rows are independent, no atomics, no workspace: two runs are bit for bit equal, a gradient asked for alone
+ *   has the bits of the joint call, permuted rows give permuted bits.
+ *   Aliasing: an output must not overlap an input or another output (csrc/arg_check.h).
+ *   FG_ERR_INVALID_ARG: N < 0, a null means_t / means_0 / viewmat_t / K / disp / g_disp, a stride below 3, width or height
+ *   <= 0, near negative, infinite or not a number, margin negative or not a number, a misaligned disp / g_disp, an output that
+ *   overlaps;  FG_ERR_UNSUPPORTED: N > FG_FLOW_DISP_MAX_ROWS or a stride above FG_FLOW_DISP_MAX_STRIDE.  N == 0 is FG_OK with no
+ *   launch (after the null, sign and stride checks).  All before any launch.  Asynchronous, capturable, no state, no environment.
+ *   Measured (profiles/flow_supervision.md). */
+#define FG_FLOW_DISP_MAX_ROWS ((int64_t)1 << 38)
+#define FG_FLOW_DISP_MAX_STRIDE ((int64_t)1 << 16)
+int fg_flow_disp_fwd(int64_t N, const float* means_t, int64_t mt_stride, const float* means_0, int64_t m0_stride,
+                     const float* viewmat_t, const float* viewmat_0, const float* K, int width, int height, float near,
+                     float margin, float* disp, fg_stream_t stream);
+int fg_flow_disp_bwd(int64_t N, const float* means_t, int64_t mt_stride, const float* means_0, int64_t m0_stride,
+                     const float* viewmat_t, const float* viewmat_0, const float* K, int width, int height, float near,
+                     float margin, const float* g_disp, float* g_means_t, float* g_means_0, fg_stream_t stream);
+
+/* ---- FL the masked L1 between the rendered flow channels and the batch's flow array at FULL resolution (found BY NAME, see
+ * FG_ABI_MINOR; csrc/flow_loss.hip).  No target tensor is written.
+ *   pred   [H, W, 2] float32 read in place: channel stride 1, pixel_stride floats between two pixels (>= 2), row_stride floats
+ *          between two rows (>= (W - 1) pixel_stride + 2) -- the last two channels of a [1,H,W,C] render.
+ *   flows  [H0, W0, 2] float32 contiguous, 8-byte aligned, in full-resolution pixels.  H = H0 / d, W = W0 / d (integer division),
+ *          d = downscale in 1, 2, 4, 8; the source rows and columns at or beyond H d, W d are never read.
+ *   mask   null, or [H0, W0] bytes (FG_TARGET_U8: a bool's 0 / 1, a uint8 by its value) or float32 (FG_TARGET_F32).
+ *   TARGET AND WEIGHT, per render pixel:
+ *     t = the mean of the d x d source block at (y d, x d) DIVIDED BY d (a flow in full-resolution pixels shrinks with the image);
+ *     w = 0 if any of the block's 2 d^2 source values is not finite, else the same box mean of the mask (1 without a mask).
+ *     Block sums are exact (double) and rounded once.
+ *   fg_flow_l1_fwd:  out[0] = sum w (|pred_x - t_x| + |pred_y - t_y|) / (2 max(sum w, FG_FLOW_L1_TINY)); sum w = 0 gives 0.  A
+ *     pixel with w = 0 is not read from pred.
+ *   fg_flow_l1_bwd:  g_pred[H, W, 2] (contiguous, 8-byte aligned, overwritten) = v_out[0] w sign(pred - t) / (2 max(sum w, tiny)),
+ *     sign(0) = 0; exactly 0 where w = 0, so sum w = 0 gives a zero gradient, never NaN.  flows and mask get none.
+ *   DETERMINISM: per-pixel terms, per-workgroup partial sums and their fixed-order total are doubles, rounded once; no atomics;
+ *     two runs are bit for bit equal.  The totals stay in the first 16 bytes of the workspace
+ *     (fg_flow_l1_workspace_bytes(H0, W0, d) bytes, 16-byte aligned; 0 = unsupported), which the backward reads: hand it the
+ *     forward's workspace unchanged.  Nothing is read back by the host.
+ *   FG_ERR_INVALID_ARG: H0 or W0 <= 0, H != H0 / d or W != W0 / d, a null or misaligned pred / flows / workspace / out / v_out /
+ *   g_pred, a float mask that is misaligned, a pixel or row stride below the above, an output (workspace, out; g_pred) that
+ *   overlaps an input or another output;  FG_ERR_UNSUPPORTED: another d, a side above 32768 or below d, a mask dtype that is
+ *   neither, a pixel stride above FG_FLOW_L1_MAX_STRIDE;  FG_ERR_WORKSPACE: workspace_bytes below the query.  All before any
+ *   launch.  Asynchronous, capturable, no state, no environment.  Measured (profiles/flow_supervision.md). */
+#define FG_FLOW_L1_TINY 1e-30
+#define FG_FLOW_L1_MAX_STRIDE ((int64_t)1 << 16)
+size_t fg_flow_l1_workspace_bytes(int H0, int W0, int downscale);
+int fg_flow_l1_fwd(int H, int W, const float* pred, int64_t pixel_stride, int64_t row_stride, int H0, int W0, int downscale,
+                   const float* flows, const void* mask, int mask_dtype, void* workspace, size_t workspace_bytes, float* out,
+                   fg_stream_t stream);
+int fg_flow_l1_bwd(int H, int W, const float* pred, int64_t pixel_stride, int64_t row_stride, int H0, int W0, int downscale,
+                   const float* flows, const void* mask, int mask_dtype, const void* workspace, const float* v_out, float* g_pred,
+                   fg_stream_t stream);
 
 #ifdef __cplusplus
 }
