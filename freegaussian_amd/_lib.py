@@ -166,15 +166,23 @@ SIGNATURES = {
     "fg_flow_l1_fwd": (c_int, [c_int, c_int, P, c_int64, c_int64, c_int, c_int, c_int, P, P, c_int, P, c_size_t, P, P]),
     # (..., mask_dtype, workspace, v_out[1], g_pred, stream)
     "fg_flow_l1_bwd": (c_int, [c_int, c_int, P, c_int64, c_int64, c_int, c_int, c_int, P, P, c_int, P, P, P, P]),
+    # exact DBSCAN over [n,3] points (csrc/dbscan.hip)
+    "fg_dbscan_workspace_bytes": (c_size_t, [c_int64]),
+    # (n, xyz, eps, min_samples, labels_out int32[n], core_out uint8[n], counts_out int32[2] = {K, status}, workspace, bytes, stream)
+    "fg_dbscan": (c_int, [c_int64, P, c_float, c_int, P, P, P, P, c_size_t, P]),
 }  # fmt: skip
 
 # test hooks, not declared in the public header
 _EXTRA = {"fg_debug_wave_reduce16": (c_int, [P, P, P]), "fg_debug_knn_grid": (c_int, [c_int64, P, c_int, P, P]),
-          "fg_debug_color_correct_solve": (c_int, [P, P, P, P])}  # (G[10,10], r[10], w[10], rank[1]): host float64
+          "fg_debug_color_correct_solve": (c_int, [P, P, P, P]),  # (G[10,10], r[10], w[10], rank[1]): host float64
+          # fg_dbscan's arguments, then ms_host float[6] (per stage, between device events) and staged_out int32[1]
+          "fg_debug_dbscan_stages": (c_int, [c_int64, P, c_float, c_int, P, P, P, P, c_size_t, P, P, P])}
 
 ABI_VERSION = 14
 ABI_MINOR = 1  # FG_ABI_MINOR: the least the binding needs (symbols added without raising FG_ABI_VERSION)
 KNN_MAX_K = 8  # FG_KNN_MAX_K
+DBSCAN_MAX_ROWS, DBSCAN_MAX_MIN_SAMPLES = 1 << 24, 65535  # FG_DBSCAN_MAX_ROWS, FG_DBSCAN_MAX_MIN_SAMPLES
+DBSCAN_MIN_EPS, DBSCAN_MAX_EPS = 1e-18, 1e18  # FG_DBSCAN_MIN_EPS, FG_DBSCAN_MAX_EPS
 MLP_ROW_TILE = 64  # FG_MLP_ROW_TILE
 MLP_MAX_HEADS = 4  # FG_MLP_MAX_HEADS
 MLP_SE3, MLP_PLAIN = 0, 1  # FG_MLP_SE3, FG_MLP_PLAIN

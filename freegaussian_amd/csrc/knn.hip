@@ -18,11 +18,9 @@
 // Arithmetic (compiled with -ffp-contract=off; tests/knn_restatement.py states it on the CPU, bit for bit):
 //   dx = xq - xp (y, z alike), d2 = (dx dx + dy dy) + dz dz, candidates ordered by (d2, row number), the query's own
 //   row excluded by number.
-#include <algorithm>
-#include <cmath>
 #include <cstdlib>
 
-#include "radix_sort.h"
+#include "knn_grid.h"
 
 #ifndef FG_KNN_OCC
 #define FG_KNN_OCC 4  // mean points per cell: a starting value, not yet picked by measurement (make knn-occ builds others)
@@ -30,58 +28,9 @@
 
 namespace {
 
-constexpr int KNN_BLOCK = 256;
+using namespace fg_grid;  // the grid, its keys / cells launches and the sample's extent: knn_grid.h, shared with dbscan.hip
+
 constexpr int KNN_CHUNK = 1024;  // float4 slots of the LDS stage (16 KiB)
-constexpr int KNN_SAMPLE = 4096;
-constexpr int KNN_MAX_DIM = 1024;  // cells per axis: keys stay below 2^30
-
-struct KnnGrid {
-  float lo[3], inv[3], h[3];  // cell c of axis a spans [lo + c h, lo + (c + 1) h); inv = 1 / h (0 on a one-cell axis)
-  int g[3];
-  float slack;  // what the rounding of the cell assignment and of the face positions may amount to
-};
-
-__global__ void __launch_bounds__(KNN_BLOCK)
-knn_sample_kernel(int64_t n, int count, const float* __restrict__ xyz, float* __restrict__ sample) {
-  const int s = blockIdx.x * KNN_BLOCK + threadIdx.x;
-  if (s >= count) return;
-  const int64_t i = (int64_t)s * n / count;
-  sample[3 * s + 0] = xyz[3 * i + 0];
-  sample[3 * s + 1] = xyz[3 * i + 1];
-  sample[3 * s + 2] = xyz[3 * i + 2];
-}
-
-// (fmaxf drops a NaN: whatever the coordinate, the cell is inside the grid)
-__device__ __forceinline__ int knn_cell(float x, float lo, float inv, int g) {
-  return (int)fminf(fmaxf(floorf((x - lo) * inv), 0.f), (float)(g - 1));
-}
-
-__global__ void __launch_bounds__(KNN_BLOCK)
-knn_keys_kernel(int64_t n, KnnGrid gr, const float* __restrict__ xyz, uint32_t* __restrict__ keys) {
-  const int64_t i = (int64_t)blockIdx.x * KNN_BLOCK + threadIdx.x;
-  if (i >= n) return;
-  const int cx = knn_cell(xyz[3 * i + 0], gr.lo[0], gr.inv[0], gr.g[0]);
-  const int cy = knn_cell(xyz[3 * i + 1], gr.lo[1], gr.inv[1], gr.g[1]);
-  const int cz = knn_cell(xyz[3 * i + 2], gr.lo[2], gr.inv[2], gr.g[2]);
-  keys[i] = (uint32_t)((cz * gr.g[1] + cy) * gr.g[0] + cx);
-}
-
-// slot i: writes the start of every cell in (key[i-1], key[i]] (the last slot: of every cell after its own, too) and
-// gathers its point
-__global__ void __launch_bounds__(KNN_BLOCK)
-knn_cells_kernel(int64_t n, int cells, const uint32_t* __restrict__ keys, const uint32_t* __restrict__ order,
-                 const float* __restrict__ xyz, int32_t* __restrict__ cell_start, float4* __restrict__ pts) {
-  const int64_t i = (int64_t)blockIdx.x * KNN_BLOCK + threadIdx.x;
-  if (i >= n) return;
-  const int key = (int)keys[i];
-  const int prev = i ? (int)keys[i - 1] : -1;
-  for (int c = prev + 1; c <= key; ++c) cell_start[c] = (int32_t)i;
-  if (i == n - 1)
-    for (int c = key + 1; c <= cells; ++c) cell_start[c] = (int32_t)n;
-  const uint32_t row = order[i];
-  pts[i] = make_float4(xyz[3 * (int64_t)row + 0], xyz[3 * (int64_t)row + 1], xyz[3 * (int64_t)row + 2],
-                       __int_as_float((int)row));
-}
 
 // the K best (d2, row) pairs of a lane, ascending, in registers: every index below is a compile-time constant
 template <int K>
@@ -216,18 +165,7 @@ knn_search_kernel(int n, KnnGrid gr, const uint32_t* __restrict__ keys, const fl
 // the grid from the sample (host): robust extent per axis, cells of ~FG_KNN_OCC points, an axis thinner than a cell = one cell
 KnnGrid knn_plan_grid(int64_t n, const float* sample, int count, float* v /*[count] scratch*/) {
   double lo[3], ext[3];
-  for (int a = 0; a < 3; ++a) {
-    for (int s = 0; s < count; ++s) {
-      const float x = sample[3 * s + a];
-      v[s] = std::isfinite(x) ? x : 0.f;
-    }
-    std::sort(v, v + count);
-    const double q0 = v[(int)(0.02 * (count - 1))], q1 = v[(int)std::ceil(0.98 * (count - 1))];
-    const double pad = 0.05 * (q1 - q0);
-    lo[a] = std::max(q0 - pad, (double)v[0]);
-    ext[a] = std::min(q1 + pad, (double)v[count - 1]) - lo[a];
-    if (!(ext[a] > 0.0) || !std::isfinite(ext[a])) ext[a] = 0.0;
-  }
+  knn_extent(sample, count, v, lo, ext);
   const double target = std::max<double>(1.0, (double)n / FG_KNN_OCC);
   bool on[3] = {ext[0] > 0.0, ext[1] > 0.0, ext[2] > 0.0};
   double h = 0.0;
@@ -250,7 +188,6 @@ KnnGrid knn_plan_grid(int64_t n, const float* sample, int count, float* v /*[cou
     if (!dropped) break;
   }
   KnnGrid gr;
-  double amax = 0.0;
   for (int a = 0; a < 3; ++a) {
     int g = 1;
     if (on[a] && h > 0.0) g = (int)std::min<double>(KNN_MAX_DIM, std::max(1.0, std::floor(ext[a] / h)));
@@ -261,18 +198,7 @@ KnnGrid knn_plan_grid(int64_t n, const float* sample, int count, float* v /*[cou
     if (gr.g[a] <= 1) break;
     --gr.g[a];
   }
-  for (int a = 0; a < 3; ++a) {
-    gr.lo[a] = (float)lo[a];
-    gr.h[a] = gr.g[a] > 1 ? (float)(ext[a] / gr.g[a]) : 0.f;
-    gr.inv[a] = gr.g[a] > 1 ? (float)(gr.g[a] / ext[a]) : 0.f;
-    if (!std::isfinite(gr.inv[a]) || !(gr.h[a] > 0.f)) {
-      gr.g[a] = 1;
-      gr.h[a] = gr.inv[a] = 0.f;
-    }
-    amax = std::max(amax, std::fabs(lo[a]) + std::fabs(lo[a] + ext[a]) + ext[a]);
-  }
-  // x - lo, the product with inv, lo + c h and the face distance each round once: a few ulps of the coordinates' size
-  gr.slack = (float)(1e-6 * amax);
+  knn_finish_grid(gr, lo, ext);
   return gr;
 }
 
@@ -339,27 +265,14 @@ extern "C" int fg_knn(int64_t n, const float* xyz, int k, float* dist2_out, int3
   // (heap, not 64 KB of the caller's stack: a C host may call from a thread with a small one)
   float* host = static_cast<float*>(std::malloc((size_t)count * 4 * sizeof(float)));
   if (!host) return FG_ERR_LAUNCH;
-  hipLaunchKernelGGL(knn_sample_kernel, dim3((count + KNN_BLOCK - 1) / KNN_BLOCK), dim3(KNN_BLOCK), 0, s, n, count, xyz,
-                     sample);
-  const bool read_back = hipGetLastError() == hipSuccess &&
-                         hipMemcpyAsync(host, sample, (size_t)count * 3 * sizeof(float), hipMemcpyDeviceToHost, s) == hipSuccess &&
-                         hipStreamSynchronize(s) == hipSuccess;
+  const bool read_back = knn_read_sample(n, count, xyz, sample, host, s);
   KnnGrid gr = {};
   if (read_back) gr = knn_plan_grid(n, host, count, host + (size_t)count * 3);
   std::free(host);
   if (!read_back) return FG_ERR_LAUNCH;
-  const int cells = gr.g[0] * gr.g[1] * gr.g[2];
-
   const int nb = (int)((n + KNN_BLOCK - 1) / KNN_BLOCK);
-  hipLaunchKernelGGL(knn_keys_kernel, dim3(nb), dim3(KNN_BLOCK), 0, s, n, gr, xyz, keys);
-  FG_RETURN_IF_LAUNCH_FAILED();
-  int end_bit = 1;  // (one cell: still one pass, it numbers the rows)
-  while (end_bit < 32 && ((int64_t)1 << end_bit) < cells) ++end_bit;
-  const int rc = fg_sort::sort_pairs<uint32_t>(n, keys, order, end_bit, ws + w.sort, workspace_bytes - w.sort, s, nullptr,
-                                               /*iota_vals=*/true);
+  const int rc = knn_build_cells(n, gr, xyz, keys, order, pts, cell_start, ws + w.sort, workspace_bytes - w.sort, s);
   if (rc != FG_OK) return rc;
-  hipLaunchKernelGGL(knn_cells_kernel, dim3(nb), dim3(KNN_BLOCK), 0, s, n, cells, keys, order, xyz, cell_start, pts);
-  FG_RETURN_IF_LAUNCH_FAILED();
 #define FG_KNN_SEARCH(KK)                                                                                          \
   case KK:                                                                                                         \
     hipLaunchKernelGGL((knn_search_kernel<KK>), dim3(nb), dim3(KNN_BLOCK), 0, s, (int)n, gr, keys, pts, cell_start, \

@@ -9,7 +9,7 @@ from typing import Iterable, Optional, Tuple
 
 import torch
 
-from . import _lib
+from . import _lib, ops
 from .rasterization import rasterization
 
 
@@ -59,4 +59,55 @@ def build_gaussian_masks(means, quats, scales, opacities, colors, sh_degree: Opt
                           mask_valids)  # fmt: skip
     if out is None:
         raise ValueError("no key frames")
+    return out
+
+
+def flow_motion_labels(flow: torch.Tensor, threshold: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """A Gaussian-flow map ``[H,W,2]`` binarised into the label maps of one key frame: channel 0 is "moving"
+    (``|flow| > threshold``, both components finite), channel 1 its complement, which ``backproject_frame`` drops as the
+    background.  -> ``(atrb_masks bool [H,W,2], mask_valids bool [2])``.  ``build_gaussian_masks`` over such frames yields
+    the dynamic set ``[N,1]`` that ``cluster_gaussian_masks`` splits into columns."""
+    if flow.dim() != 3 or flow.shape[2] != 2:
+        raise ValueError(f"flow [H,W,2] expected, got {tuple(flow.shape)}")
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float)) or not threshold >= 0:
+        raise ValueError(f"a threshold >= 0 expected, got {threshold!r}")
+    f = flow.detach().float()
+    moving = torch.isfinite(f).all(dim=-1) & (torch.linalg.vector_norm(f, dim=-1) > threshold)
+    return torch.stack([moving, ~moving], dim=-1), torch.ones(2, dtype=torch.bool, device=flow.device)
+
+
+@torch.no_grad()
+def cluster_gaussian_masks(means: torch.Tensor, dynamic: torch.Tensor, eps: float, min_samples: int = 4,
+                           min_cluster_size: int = 1, max_clusters: Optional[int] = None) -> torch.Tensor:
+    """The dynamic Gaussians grouped into mask columns (project page, "Dynamic Gaussian clustering and tracking"):
+    ``ops.dbscan`` on ``means[dynamic]``, one column per cluster.  Clusters below ``min_cluster_size`` rows are dropped; of
+    the rest the ``max_clusters`` largest are kept (ties: the lower cluster number); columns stay in cluster order.  Noise
+    rows and non-dynamic rows are all-False.  -> bool ``[N,K]`` on ``means``'s device, every column non-empty: what
+    ``io.save_gaussian_mask`` writes and ``ops.control_plan`` takes (K <= 32)."""
+    N = means.shape[0]
+    if means.dim() != 2 or means.shape[1] != 3:
+        raise ValueError(f"means [N,3] expected, got {tuple(means.shape)}")
+    if dynamic.dtype != torch.bool or dynamic.shape not in ((N,), (N, 1)):
+        raise ValueError(f"dynamic: bool [N] or [N,1] expected, got {dynamic.dtype} {tuple(dynamic.shape)}")
+    if not isinstance(min_cluster_size, int) or min_cluster_size < 1:
+        raise ValueError(f"min_cluster_size >= 1 expected, got {min_cluster_size!r}")
+    if max_clusters is not None and (not isinstance(max_clusters, int) or max_clusters < 1):
+        raise ValueError(f"max_clusters: None or an int >= 1 expected, got {max_clusters!r}")
+    rows = dynamic.reshape(N).to(means.device).nonzero().squeeze(1)
+    if rows.numel() == 0:
+        raise ValueError("no dynamic Gaussian to cluster")
+    labels, _, k = ops.dbscan(means.detach()[rows].float().contiguous(), eps, min_samples)
+    labels = labels.to(device=means.device, dtype=torch.int64)
+    sizes = torch.bincount(labels[labels >= 0], minlength=k)
+    keep = sizes >= min_cluster_size
+    if max_clusters is not None and int(keep.sum()) > max_clusters:
+        # a stable descending sort: among equal sizes the lower cluster number comes first
+        order = torch.sort(torch.where(keep, sizes, torch.zeros_like(sizes)), descending=True, stable=True).indices
+        keep = torch.zeros_like(keep)
+        keep[order[:max_clusters]] = True
+    kept = keep.nonzero().squeeze(1)
+    if kept.numel() == 0:
+        raise ValueError(f"no cluster survives: {k} clusters, sizes {sizes.tolist()}, min_cluster_size {min_cluster_size}")
+    out = torch.zeros(N, kept.numel(), dtype=torch.bool, device=means.device)
+    out[rows] = labels[:, None] == kept[None, :]
     return out

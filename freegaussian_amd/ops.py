@@ -1813,6 +1813,45 @@ def knn(x: torch.Tensor, k: int = 3, squared: bool = False) -> Tuple[torch.Tenso
     return (d2 if squared else d2.sqrt()), idx
 
 
+@torch.no_grad()
+def dbscan(x: torch.Tensor, eps: float, min_samples: int = 4) -> Tuple[torch.Tensor, torch.Tensor, int]:
+    """Exact DBSCAN of the rows of ``x`` [n,3] (``fg_dbscan``; the definition is in include/fgraster.h, "DB", and on the
+    CPU in tests/dbscan_restatement.py): ``j`` neighbours ``i`` iff the fp32 ``d2 <= eps * eps`` of ``ops.knn``, a core row
+    has at least ``min_samples`` neighbours with itself counted, clusters are the connected components of the core rows
+    numbered by their lowest core row, a border row takes the lowest-numbered cluster among its core neighbours, the rest
+    (a row with a non-finite coordinate too) is -1.  Returns ``(labels int32 [n], core bool [n], n_clusters)`` on ``x``'s
+    device.  A preprocessing call: it reads the cluster count back (K sizes the mask), so it synchronises the stream and
+    cannot be captured in a graph.  There is no CPU path."""
+    if x.dim() != 2 or x.shape[1] != 3:
+        raise ValueError(f"dbscan wants [n,3] points, got {tuple(x.shape)}")
+    n = x.shape[0]
+    if not 1 <= n <= _lib.DBSCAN_MAX_ROWS:
+        raise ValueError(f"dbscan wants 1 <= n <= {_lib.DBSCAN_MAX_ROWS} rows, got {n}")
+    if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not math.isfinite(eps) or not eps > 0:
+        raise ValueError(f"dbscan wants a finite eps > 0, got {eps!r}")
+    if not _lib.DBSCAN_MIN_EPS <= eps <= _lib.DBSCAN_MAX_EPS:
+        raise ValueError(f"dbscan wants {_lib.DBSCAN_MIN_EPS:g} <= eps <= {_lib.DBSCAN_MAX_EPS:g}, got {eps!r}")
+    if isinstance(min_samples, bool) or not isinstance(min_samples, int) or not 1 <= min_samples <= _lib.DBSCAN_MAX_MIN_SAMPLES:
+        raise ValueError(f"dbscan wants an int 1 <= min_samples <= {_lib.DBSCAN_MAX_MIN_SAMPLES}, got {min_samples!r}")
+    if x.dtype != torch.float32:
+        raise ValueError(f"dbscan wants float32 points, got {x.dtype}")
+    if not x.is_cuda:
+        raise _lib.FgRasterError("dbscan runs on the GPU only (x is a CPU tensor; tests/dbscan_restatement.py is the CPU statement)")
+    xf = x.detach().contiguous()
+    dev = xf.device
+    labels = torch.empty(n, dtype=torch.int32, device=dev)
+    core = torch.empty(n, dtype=torch.uint8, device=dev)
+    counts = torch.empty(2, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        ws = torch.empty(int(_lib.load().fg_dbscan_workspace_bytes(n)), dtype=torch.uint8, device=dev)
+        _call("fg_dbscan", n, _ptr(xf), float(eps), min_samples, _ptr(labels), _ptr(core), _ptr(counts), _ptr(ws), ws.numel(),
+              _stream())  # fmt: skip
+        k, status = counts.tolist()  # the read-back that sizes the mask
+    if status != 0:
+        raise _lib.FgRasterError(f"fg_dbscan: status {status} (a root walk of the union pass exceeded its bound)")
+    return labels, core.bool(), int(k)
+
+
 MLP_ROW_TILE = _lib.MLP_ROW_TILE  # rows of one workgroup of fg_mlp_fwd (tests place their sizes around it)
 _MLP_OUT_COLS = {"se3": ((4, 4), (4,), (3,), (3,)), "plain": None}
 _MLP_PRECISIONS = {"fp32": _lib.MLP_FP32, "bf16x3": _lib.MLP_BF16X3}

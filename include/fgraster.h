@@ -60,7 +60,9 @@ typedef void* fg_stream_t;
  * of it.  Likewise BY NAME: fg_target_loss_supported, fg_target_loss_workspace_floats, fg_target_loss_fwd and
  * fg_target_loss_bwd -- a library without them has no fused training target, and the host keeps its torch statement of it.
  * Likewise BY NAME: fg_flow_disp_fwd, fg_flow_disp_bwd, fg_flow_l1_workspace_bytes, fg_flow_l1_fwd and fg_flow_l1_bwd -- a
- * library without them has no flow-supervised training: the model's flow term is an error there, not a torch fall-back.) */
+ * library without them has no flow-supervised training: the model's flow term is an error there, not a torch fall-back.
+ * Likewise BY NAME: fg_dbscan_workspace_bytes and fg_dbscan -- a library without them cannot cluster the dynamic Gaussians:
+ * a stage-2 mask then has to come from annotated label maps.) */
 #define FG_COUNT_OUT_WORDS 16 /* int64 words of a count_out block (fg_stbin_count, fg_step_io): ABI 9 */
 
 int fg_abi_version(void);
@@ -1345,6 +1347,39 @@ int fg_flow_l1_fwd(int H, int W, const float* pred, int64_t pixel_stride, int64_
 int fg_flow_l1_bwd(int H, int W, const float* pred, int64_t pixel_stride, int64_t row_stride, int H0, int W0, int downscale,
                    const float* flows, const void* mask, int mask_dtype, const void* workspace, const float* v_out, float* g_pred,
                    fg_stream_t stream);
+
+/* ---- DB exact DBSCAN over xyz[n,3] fp32 points (found BY NAME, see FG_ABI_MINOR; csrc/dbscan.hip): the clustering of the
+ * dynamic Gaussians into the columns of a stage-2 mask (project page, "Dynamic Gaussian clustering and tracking"; the reference
+ * has the step only as commented-out scikit-learn lines, preprocess/knn_gaussian.py:139-147).
+ *   THE DEFINITION (tests/dbscan_restatement.py states it on the CPU; everything else follows it):
+ *     pair distance in fp32 without contraction, as fg_knn: dx = x_i - x_j (y, z alike), d2 = (dx dx + dy dy) + dz dz;
+ *     eps2 = eps * eps in fp32;  j is a NEIGHBOUR of i iff d2 <= eps2.  The relation is symmetric bit for bit, a finite row
+ *     neighbours itself, a row with a non-finite coordinate neighbours nobody (not itself either) and is noise.
+ *     core(i): at least min_samples neighbours, the row itself counted.
+ *     CLUSTERS: the connected components of the core rows under the neighbour relation, numbered 0..K-1 by ascending lowest
+ *     core row.  A non-core row with at least one core neighbour is a BORDER row and takes the lowest-numbered cluster among
+ *     its core neighbours.  Every other row is -1.
+ *     This is sklearn.cluster.DBSCAN(eps, min_samples).fit(x).labels_ wherever no pair distance sits at the rounding edge of
+ *     eps.  The labels depend on the predicate alone: nothing about the cell grid enters them.
+ *   labels_out int32[n], core_out uint8[n] (1 = core), counts_out int32[2] = {K, status}, all device memory, written in the
+ *     caller's row order.  status 0 = in order; 1 = a root walk of the union pass exceeded its bound of n + 1 steps (a defect:
+ *     the labels are then not to be used).  The pass is lock-free and every loop in it is bounded: such a defect ends as this
+ *     word, never as a hang.
+ *   DETERMINISM: the partition is unique and the numbering is by row, so two runs are equal bit for bit, whatever order the
+ *     atomics of the union pass land in.
+ *   Limits: 1 <= n <= FG_DBSCAN_MAX_ROWS, eps > 0 and finite, 1 <= min_samples <= FG_DBSCAN_MAX_MIN_SAMPLES, no null pointer:
+ *     else FG_ERR_INVALID_ARG, nothing is clamped.  FG_ERR_UNSUPPORTED: eps outside [FG_DBSCAN_MIN_EPS, FG_DBSCAN_MAX_EPS]
+ *     (outside it eps2 is no normal fp32 number).  FG_ERR_WORKSPACE: workspace_bytes below fg_dbscan_workspace_bytes(n), which
+ *     is 0 for an n outside the limits.  All before any launch.
+ *   NOT capturable in a graph: like fg_knn the call reads a few KB of sampled coordinates back (one stream synchronisation)
+ *     to size its cell grid.  The caller reads counts_out back to learn K.  Cost: profiles/dbscan.md. */
+#define FG_DBSCAN_MAX_ROWS ((int64_t)1 << 24)
+#define FG_DBSCAN_MAX_MIN_SAMPLES 65535
+#define FG_DBSCAN_MIN_EPS 1e-18f
+#define FG_DBSCAN_MAX_EPS 1e18f
+size_t fg_dbscan_workspace_bytes(int64_t n);
+int fg_dbscan(int64_t n, const float* xyz, float eps, int min_samples, int32_t* labels_out, uint8_t* core_out,
+              int32_t* counts_out, void* workspace, size_t workspace_bytes, fg_stream_t stream);
 
 #ifdef __cplusplus
 }

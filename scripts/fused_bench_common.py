@@ -60,10 +60,11 @@ def verdict(a, b):
     return "no difference"
 
 
-def kernel_resources(src_path):
-    """The kernels of one .hip unit with what ``-Rpass-analysis=kernel-resource-usage`` says of each, for gfx950."""
+def kernel_resources(src_path, extra=()):
+    """The kernels of one .hip unit with what ``-Rpass-analysis=kernel-resource-usage`` says of each, for gfx950
+    (``extra``: further compiler flags, such as the -D of a measurement build)."""
     cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only",
-           "-Rpass-analysis=kernel-resource-usage", "-c", src_path, "-o", os.devnull]  # fmt: skip
+           *extra, "-Rpass-analysis=kernel-resource-usage", "-c", src_path, "-o", os.devnull]  # fmt: skip
     text = subprocess.run(cmd, capture_output=True, text=True).stderr
     rows, cur = [], None
     for line in text.splitlines():
