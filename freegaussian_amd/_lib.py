@@ -170,6 +170,14 @@ SIGNATURES = {
     "fg_dbscan_workspace_bytes": (c_size_t, [c_int64]),
     # (n, xyz, eps, min_samples, labels_out int32[n], core_out uint8[n], counts_out int32[2] = {K, status}, workspace, bytes, stream)
     "fg_dbscan": (c_int, [c_int64, P, c_float, c_int, P, P, P, P, c_size_t, P]),
+    # dense optical flow from two frames (csrc/optflow.hip)
+    "fg_optflow_supported": (c_int, [c_int, c_int, c_int, c_int, c_int]),  # (H, W, levels, radius, iters) -> 1 or 0
+    "fg_optflow_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),  # (H, W, levels, both_directions)
+    # (H, W, channels, dtype, img, levels, workspace, bytes, stream)
+    "fg_optflow_pyramid": (c_int, [c_int, c_int, c_int, c_int, P, c_int, P, c_size_t, P]),
+    # (H, W, channels, dtype, a, b, levels, iters, radius, min_eig, both_directions, consistency, init or null, flow [H,W,2],
+    #  valid uint8 [H,W], workspace, bytes, stream)
+    "fg_optflow": (c_int, [c_int, c_int, c_int, c_int, P, P, c_int, c_int, c_int, c_float, c_int, c_float, P, P, P, P, c_size_t, P]),
 }  # fmt: skip
 
 # test hooks, not declared in the public header
@@ -183,6 +191,9 @@ ABI_MINOR = 1  # FG_ABI_MINOR: the least the binding needs (symbols added withou
 KNN_MAX_K = 8  # FG_KNN_MAX_K
 DBSCAN_MAX_ROWS, DBSCAN_MAX_MIN_SAMPLES = 1 << 24, 65535  # FG_DBSCAN_MAX_ROWS, FG_DBSCAN_MAX_MIN_SAMPLES
 DBSCAN_MIN_EPS, DBSCAN_MAX_EPS = 1e-18, 1e18  # FG_DBSCAN_MIN_EPS, FG_DBSCAN_MAX_EPS
+OPTFLOW_MIN_SIDE, OPTFLOW_MAX_SIDE = 16, 16384  # FG_OPTFLOW_MIN_SIDE, FG_OPTFLOW_MAX_SIDE
+OPTFLOW_MAX_LEVELS, OPTFLOW_MIN_COARSEST = 8, 8  # FG_OPTFLOW_MAX_LEVELS, FG_OPTFLOW_MIN_COARSEST
+OPTFLOW_MAX_RADIUS, OPTFLOW_MAX_ITERS = 7, 16  # FG_OPTFLOW_MAX_RADIUS, FG_OPTFLOW_MAX_ITERS
 MLP_ROW_TILE = 64  # FG_MLP_ROW_TILE
 MLP_MAX_HEADS = 4  # FG_MLP_MAX_HEADS
 MLP_SE3, MLP_PLAIN = 0, 1  # FG_MLP_SE3, FG_MLP_PLAIN

@@ -1,5 +1,5 @@
 // The fused ops' aliasing rule (include/fgraster.h: no output may overlap an input or another output), stated once for the
-// entry points of se3_apply.hip, control.hip, bilagrid.hip, color_correct.hip, target_loss.hip, flow_disp.hip and flow_loss.hip.  Host only: addresses are compared, nothing
+// entry points of se3_apply.hip, control.hip, bilagrid.hip, color_correct.hip, target_loss.hip, flow_disp.hip, flow_loss.hip and optflow.hip.  Host only: addresses are compared, nothing
 // is read through them.
 #pragma once
 #include <algorithm>

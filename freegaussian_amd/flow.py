@@ -27,7 +27,11 @@ reference's ``interflow_n{k}/*.npy`` are -- and both frames are projected under 
 raw optical flow and frame 0 is projected under ``cameras0``'s pose.  The training path is
 ``ops.flow_displacement`` (the per-Gaussian mu_t - mu_0, one launch) -> two extra raster channels -> ``ops.flow_l1``;
 ``render_with_flow`` and ``flow_loss`` below stay as the stage-by-stage statement the tests compare it with.
-Stage 2 (the control model), ``graphed.GraphedModelStep`` and view-DP take no flow term."""
+Stage 2 (the control model), ``graphed.GraphedModelStep`` and view-DP take no flow term.
+
+WHERE A FLOW ARRAY COMES FROM.  ``optical_flow_since`` and ``optical_flow_forward`` estimate one from two frames with
+``ops.optical_flow`` (classical pyramidal Lucas-Kanade as HIP, include/fgraster.h "OF"; not a learned estimator, and not
+measured against one).  They answer two different questions on two different grids -- see their docstrings."""
 from __future__ import annotations
 
 from typing import Dict, Optional, Tuple
@@ -67,6 +71,36 @@ def relative_camera_motion(c2w0: torch.Tensor, c2w1: torch.Tensor) -> Tuple[torc
 def camera_flow_map(depth: torch.Tensor, K: torch.Tensor, veloc: torch.Tensor, omega: torch.Tensor) -> torch.Tensor:
     """depth [H,W] or [H,W,1] (inf allowed) -> camera flow [H,W,2] (fp32, GPU)."""
     return ops.camera_flow(depth.reshape(depth.shape[0], depth.shape[1]), K, veloc, omega)
+
+
+def _nan_where_invalid(u: torch.Tensor, valid: torch.Tensor) -> torch.Tensor:
+    return torch.where(valid[..., None], u, torch.full_like(u, float("nan")))
+
+
+def optical_flow_since(image0: torch.Tensor, image: torch.Tensor, **kw) -> torch.Tensor:
+    """-> ``flows`` [H,W,2] in THE FLOW CONVENTION above (``batch["flows"]``, ``ops.flow_l1``, ``masks.flow_motion_labels``):
+    on the CURRENT frame's grid, where the surface seen at a pixel of ``image`` is now minus where it was in ``image0``;
+    NaN where the estimate is invalid (the "no measurement" mark both consumers honour).  It is
+    ``-ops.optical_flow(image, image0)`` with the validity applied: the estimator runs FROM the current frame, so its
+    vectors sit on the current frame's pixels, and point back to frame 0 -- hence the sign.  ``kw``: ``levels``, ``iters``,
+    ``radius``, ``min_eig``, ``consistency`` of ``ops.optical_flow``.
+
+    WHICH OF THE TWO.  Training and the stage-2 masks compare with a render of the CURRENT frame: they want this one.
+    ``optical_flow_forward`` is for writing the reference's files.  The two are not negatives of each other pixel by pixel:
+    they describe the same motion sampled at the two ends of every vector (``since`` at x + u, ``forward`` at x), so they
+    agree only after one is regridded by the flow itself, and each is NaN where ITS frame shows something the other hides."""
+    u, valid = ops.optical_flow(image, image0, **kw)
+    return _nan_where_invalid(-u, valid)
+
+
+def optical_flow_forward(image0: torch.Tensor, image1: torch.Tensor, **kw) -> torch.Tensor:
+    """-> [H,W,2] on FRAME 0's grid: where the surface seen at a pixel of ``image0`` is in ``image1`` minus where it is in
+    ``image0`` -- the layout mmflow's ``inference_model(model, image0, image1)`` returns (preprocess/epipolar_flow.py:367-372),
+    NaN where invalid.  Its sum with ``camera_flow_map(depth0, ...)`` is what the reference stores as
+    ``interflow_n{k}/<frame1>.npy`` (``io.save_interflow``).  It is ``ops.optical_flow(image0, image1)`` with the validity
+    applied.  A training batch wants ``optical_flow_since`` instead (see there)."""
+    u, valid = ops.optical_flow(image0, image1, **kw)
+    return _nan_where_invalid(u, valid)
 
 
 def reprojection_motion(c2w0: torch.Tensor, c2w1: torch.Tensor) -> torch.Tensor:

@@ -1852,6 +1852,115 @@ def dbscan(x: torch.Tensor, eps: float, min_samples: int = 4) -> Tuple[torch.Ten
     return labels, core.bool(), int(k)
 
 
+def optical_flow_default_levels(H: int, W: int) -> int:
+    """``levels=None`` of ``optical_flow``: the largest L <= 6 whose coarsest level has a shorter side >= 16."""
+    L, s = 1, min(H, W)
+    while L < 6 and (s + 1) // 2 >= 16:
+        s, L = (s + 1) // 2, L + 1
+    return L
+
+
+def optical_flow_level_shapes(H: int, W: int, levels: int):
+    """[(h, w)] of the pyramid: every level is ((h + 1) // 2, (w + 1) // 2) of the one above."""
+    out = [(H, W)]
+    for _ in range(levels - 1):
+        out.append(((out[-1][0] + 1) // 2, (out[-1][1] + 1) // 2))
+    return out
+
+
+def _optflow_image(who: str, img: torch.Tensor, name: str):
+    """-> (the dense image, channels, FG_TARGET_* dtype) of an [H,W] float32 or [H,W,3] float32 / uint8 image."""
+    if img.dim() not in (2, 3) or (img.dim() == 3 and img.shape[2] != 3):
+        raise ValueError(f"{who} wants [H,W] or [H,W,3] images, got {name}: {tuple(img.shape)} (composite an alpha channel first)")
+    if img.dtype != torch.float32 and not (img.dtype == torch.uint8 and img.dim() == 3):
+        raise ValueError(f"{who} wants float32 images, or uint8 [H,W,3] ones, got {name}: {img.dtype} {tuple(img.shape)}")
+    return img.detach(), (1 if img.dim() == 2 else 3), (_lib.TARGET_F32 if img.dtype == torch.float32 else _lib.TARGET_U8)
+
+
+def _optflow_on_gpu(who: str, **tensors) -> None:
+    """After every other refusal: there is no CPU path."""
+    for name, t in tensors.items():
+        if t is not None and not t.is_cuda:
+            raise _lib.FgRasterError(f"{who} runs on the GPU only ({name} is a CPU tensor; tests/optical_flow_restatement.py is the CPU statement)")
+
+
+def _optflow_shape(who: str, H: int, W: int, levels, radius: int = 1, iters: int = 1) -> int:
+    """The ranges of include/fgraster.h ("OF") -> the level count."""
+    lo, hi = _lib.OPTFLOW_MIN_SIDE, _lib.OPTFLOW_MAX_SIDE
+    if not (lo <= H <= hi and lo <= W <= hi):
+        raise ValueError(f"{who} wants {lo} <= H, W <= {hi}, got {H} x {W}")
+    if levels is None:
+        levels = optical_flow_default_levels(H, W)
+    for name, v, top in (("levels", levels, _lib.OPTFLOW_MAX_LEVELS), ("radius", radius, _lib.OPTFLOW_MAX_RADIUS),
+                         ("iters", iters, _lib.OPTFLOW_MAX_ITERS)):  # fmt: skip
+        if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= top:
+            raise ValueError(f"{who} wants an int 1 <= {name} <= {top}, got {v!r}")
+    if min(optical_flow_level_shapes(H, W, levels)[-1]) < _lib.OPTFLOW_MIN_COARSEST:
+        raise ValueError(f"{who}: {levels} levels leave a coarsest level of {optical_flow_level_shapes(H, W, levels)[-1]}, "
+                         f"below {_lib.OPTFLOW_MIN_COARSEST} on its shorter side")  # fmt: skip
+    return levels
+
+
+def optical_flow_pyramid(img: torch.Tensor, levels: int):
+    """The grey pyramid ``fg_optflow`` works on (``fg_optflow_pyramid``): a list of ``levels`` float32 [h,w] tensors, level 0
+    the grey image (0.299 R + 0.587 G + 0.114 B, uint8 divided by 255), each further one the 5-tap binomial of the one above
+    at even coordinates.  Views of one workspace."""
+    x, channels, dtype = _optflow_image("optical_flow_pyramid", img, "img")
+    H, W = x.shape[:2]
+    levels = _optflow_shape("optical_flow_pyramid", H, W, levels)
+    _optflow_on_gpu("optical_flow_pyramid", img=x)
+    x = x.contiguous()
+    with torch.cuda.device(x.device):
+        ws = torch.empty(int(_lib.load().fg_optflow_workspace_bytes(H, W, levels, 0)), dtype=torch.uint8, device=x.device)
+        _call("fg_optflow_pyramid", H, W, channels, dtype, _ptr(x), levels, _ptr(ws), ws.numel(), _stream())
+    out, at = [], 0
+    for h, w in optical_flow_level_shapes(H, W, levels):
+        out.append(ws[at : at + 4 * h * w].view(torch.float32).view(h, w))
+        at += (4 * h * w + 255) // 256 * 256
+    return out
+
+
+def optical_flow(a: torch.Tensor, b: torch.Tensor, levels: Optional[int] = None, iters: int = 4, radius: int = 3,
+                 min_eig: float = 1e-5, consistency: Optional[float] = 1.0,
+                 init: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:  # fmt: skip
+    """Dense optical flow from ``a`` to ``b`` (``fg_optflow``; the definition is in include/fgraster.h, "OF", and on the CPU
+    in tests/optical_flow_restatement.py): pyramidal, patch-based, inverse-compositional Lucas-Kanade with a forward-backward
+    check -- classical, weight-free, deterministic; its quality against a learned estimator has not been measured.
+    ``a``, ``b``: [H,W] float32, or [H,W,3] float32 or uint8.  Returns ``(flow [H,W,2] float32, valid bool [H,W])`` with
+    ``a(x) ~ b(x + flow[y,x])`` in full-resolution pixels.  An invalid pixel KEEPS its estimate here (the raw statement);
+    ``flow.optical_flow_since`` / ``flow.optical_flow_forward`` write NaN there.  ``levels=None``: the largest L <= 6 whose
+    coarsest level has a shorter side >= 16.  ``consistency=None`` skips the b -> a run and its test; the flow is the same bit
+    for bit.  ``init`` [H,W,2]: where the coarsest level starts (level-0 pixels).  Asynchronous: nothing is read back.
+    There is no CPU path."""
+    xa, channels, dtype = _optflow_image("optical_flow", a, "a")
+    xb, cb, db = _optflow_image("optical_flow", b, "b")
+    if xa.shape != xb.shape or db != dtype or xb.device != xa.device:
+        raise ValueError(f"optical_flow wants two images of one shape, dtype and device, got {tuple(a.shape)} {a.dtype} on {a.device} "
+                         f"and {tuple(b.shape)} {b.dtype} on {b.device}")  # fmt: skip
+    H, W = xa.shape[:2]
+    levels = _optflow_shape("optical_flow", H, W, levels, radius, iters)
+    for name, v in (("min_eig", min_eig),) + ((("consistency", consistency),) if consistency is not None else ()):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
+            raise ValueError(f"optical_flow wants a finite {name} >= 0, got {v!r}")
+    dev = xa.device
+    if init is not None:
+        if tuple(init.shape) != (H, W, 2) or init.dtype != torch.float32:
+            raise ValueError(f"optical_flow wants init as float32 [{H},{W},2], got {init.dtype} {tuple(init.shape)}")
+        if init.device != dev:
+            raise ValueError(f"optical_flow wants init on {dev}, got {init.device}")
+        init = init.detach().contiguous()
+    _optflow_on_gpu("optical_flow", a=xa, b=xb, init=init)
+    xa, xb = xa.contiguous(), xb.contiguous()
+    both = consistency is not None
+    flow = torch.empty(H, W, 2, dtype=torch.float32, device=dev)
+    valid = torch.empty(H, W, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        ws = torch.empty(int(_lib.load().fg_optflow_workspace_bytes(H, W, levels, int(both))), dtype=torch.uint8, device=dev)
+        _call("fg_optflow", H, W, channels, dtype, _ptr(xa), _ptr(xb), levels, iters, radius, float(min_eig), int(both),
+              float(consistency) if both else 0.0, _ptr(init), _ptr(flow), _ptr(valid), _ptr(ws), ws.numel(), _stream())  # fmt: skip
+    return flow, valid.view(torch.bool)
+
+
 MLP_ROW_TILE = _lib.MLP_ROW_TILE  # rows of one workgroup of fg_mlp_fwd (tests place their sizes around it)
 _MLP_OUT_COLS = {"se3": ((4, 4), (4,), (3,), (3,)), "plain": None}
 _MLP_PRECISIONS = {"fp32": _lib.MLP_FP32, "bf16x3": _lib.MLP_BF16X3}

@@ -62,7 +62,9 @@ typedef void* fg_stream_t;
  * Likewise BY NAME: fg_flow_disp_fwd, fg_flow_disp_bwd, fg_flow_l1_workspace_bytes, fg_flow_l1_fwd and fg_flow_l1_bwd -- a
  * library without them has no flow-supervised training: the model's flow term is an error there, not a torch fall-back.
  * Likewise BY NAME: fg_dbscan_workspace_bytes and fg_dbscan -- a library without them cannot cluster the dynamic Gaussians:
- * a stage-2 mask then has to come from annotated label maps.) */
+ * a stage-2 mask then has to come from annotated label maps.  Likewise BY NAME: fg_optflow_supported,
+ * fg_optflow_workspace_bytes, fg_optflow_pyramid and fg_optflow -- a library without them estimates no optical flow: the
+ * flow maps then have to come from elsewhere.) */
 #define FG_COUNT_OUT_WORDS 16 /* int64 words of a count_out block (fg_stbin_count, fg_step_io): ABI 9 */
 
 int fg_abi_version(void);
@@ -1380,6 +1382,59 @@ int fg_flow_l1_bwd(int H, int W, const float* pred, int64_t pixel_stride, int64_
 size_t fg_dbscan_workspace_bytes(int64_t n);
 int fg_dbscan(int64_t n, const float* xyz, float eps, int min_samples, int32_t* labels_out, uint8_t* core_out,
               int32_t* counts_out, void* workspace, size_t workspace_bytes, fg_stream_t stream);
+
+/* ---- OF dense optical flow from two frames (found BY NAME, see FG_ABI_MINOR; csrc/optflow.hip): the flow maps that the flow
+ * loss (FL) and the annotation-free stage-2 masks consume.  The reference makes them with a learned network (mmflow's GMA,
+ * preprocess/epipolar_flow.py:367-372); this is a CLASSICAL, weight-free, deterministic estimator: pyramidal, patch-based,
+ * inverse-compositional Lucas-Kanade with a forward-backward check.  Its quality against a learned estimator on real footage
+ * has not been measured.
+ *   THE DEFINITION (tests/optical_flow_restatement.py states it on the CPU, in float64 and in fp32, operation by operation):
+ *     images    a, b: [H,W] float32, or [H,W,3] float32 or uint8 (dtype FG_TARGET_F32 / FG_TARGET_U8), device memory, dense.
+ *               grey = 0.299 R + 0.587 G + 0.114 B, a uint8 value divided by 255 first.
+ *     convention flow[y,x] = u with a(x) ~ b(x + u), in pixels of the full-resolution grid of a.
+ *     pyramid   level 0 = grey; level l+1 = level l under the separable 5-tap binomial [1 4 6 4 1]/16, coordinates clamped to
+ *               the image, sampled at even coordinates: size ((h+1)/2, (w+1)/2).
+ *     per level, coarse to fine: u starts at 0 on the coarsest level -- or, with `init` [H,W,2] (level-0 pixels), at
+ *               init[y s, x s] / s, s = 2^(levels-1) -- and on every other level at twice the bilinear sample of the coarser
+ *               level's u at (x/2, y/2), clamped.  grad A by central differences on the clamp-padded level.  Per pixel p, over
+ *               the (2r+1)^2 box window q, window coordinates clamped to the image:
+ *                 G = sum grad A grad A^T + lambda I, lambda = 1e-6
+ *                 `iters` times: It(q) = B(clamp(p+q) + u(p)) - A(clamp(p+q)), B sampled bilinearly, the sample position
+ *                 clamped to the image;  b = sum It grad A;  u(p) -= G^-1 b.
+ *               The WHOLE window moves with the centre's u.  (The cheaper form that warps each pixel by its own flow and
+ *               box-filters the products diverges with more iterations: it is not this.)
+ *     validity  valid[y,x] = 1 iff (i) the smaller eigenvalue of the level-0 G / (2r+1)^2 >= min_eig, (ii) x + u lies inside
+ *               the image [0, W-1] x [0, H-1], and (iii), with both_directions, |u_ab(x) + u_ba(x + u_ab(x))|_2 <= consistency,
+ *               u_ba the same estimator from b to a (without init), sampled bilinearly.  An invalid pixel KEEPS its u in
+ *               `flow`; the caller marks it (the Python wrappers write NaN, which FL and flow_motion_labels honour).
+ *   fg_optflow_supported: 1 where the shape arguments are inside the ranges below, else 0.
+ *   fg_optflow_workspace_bytes: the workspace of fg_optflow (0 outside the ranges).  Its head is the pyramid of a: level l as
+ *     dense float32 [h_l, w_l] at byte offset sum_{k<l} align256(4 h_k w_k) -- all that fg_optflow_pyramid writes and needs.
+ *   fg_optflow_pyramid: grey conversion and all levels of one image into the workspace.
+ *   fg_optflow: both pyramids, the level loop in one or both directions, validity.  flow float32 [H,W,2], valid uint8 [H,W].
+ *     levels = 1, iters = 1, both_directions = 0 with `init` is ONE update step from init.
+ *   Ranges, FG_ERR_UNSUPPORTED outside: FG_OPTFLOW_MIN_SIDE <= H, W <= FG_OPTFLOW_MAX_SIDE; 1 <= levels <=
+ *     FG_OPTFLOW_MAX_LEVELS with the coarsest level's shorter side >= FG_OPTFLOW_MIN_COARSEST; 1 <= radius <=
+ *     FG_OPTFLOW_MAX_RADIUS; 1 <= iters <= FG_OPTFLOW_MAX_ITERS; a uint8 image has 3 channels.  FG_ERR_INVALID_ARG: sizes or
+ *     counts <= 0, channels not 1 or 3, an unknown dtype, min_eig or (with both_directions) consistency negative or not
+ *     finite, a null or misaligned pointer (floats 4, flow and init 8, workspace 256 bytes), an output or the workspace
+ *     overlapping an input or another output.  FG_ERR_WORKSPACE: workspace_bytes too small.  All before any launch.
+ *   No atomics, fixed summation order: two runs are equal bit for bit, and the flow does not depend on both_directions.
+ *   Asynchronous, capturable: nothing is read back, nothing allocated; 2 levels + levels (x 2) + 1 launches.  Cost:
+ *   profiles/optical_flow.md. */
+#define FG_OPTFLOW_MIN_SIDE 16
+#define FG_OPTFLOW_MAX_SIDE 16384
+#define FG_OPTFLOW_MAX_LEVELS 8
+#define FG_OPTFLOW_MIN_COARSEST 8
+#define FG_OPTFLOW_MAX_RADIUS 7
+#define FG_OPTFLOW_MAX_ITERS 16
+int fg_optflow_supported(int H, int W, int levels, int radius, int iters);
+size_t fg_optflow_workspace_bytes(int H, int W, int levels, int both_directions);
+int fg_optflow_pyramid(int H, int W, int channels, int dtype, const void* img, int levels, void* workspace, size_t workspace_bytes,
+                       fg_stream_t stream);
+int fg_optflow(int H, int W, int channels, int dtype, const void* a, const void* b, int levels, int iters, int radius, float min_eig,
+               int both_directions, float consistency, const float* init, float* flow, uint8_t* valid, void* workspace,
+               size_t workspace_bytes, fg_stream_t stream);
 
 #ifdef __cplusplus
 }
